@@ -2,7 +2,9 @@
 """Headline benchmark: caption decode-steps/sec (B x T per full greedy decode) on MI355X.
 
   python bench.py                                                     # BASELINE config 2, 300 timed decodes (>= 1 s)
-  python bench.py --gpus 1 --steps 20 --warmup 5                      # what the driver runs
+  python bench.py --gpus 1 --steps 20 --warmup 5                      # what the driver runs: the headline measurement only
+  python bench.py --full                                              # + roofline, per-kernel table, CPU baseline, secondary
+  python bench.py --steps 20 --warmup 5 --dump-outputs DIR            # + the last timed step's outputs as DIR/<name>.npy
   python bench.py --gpus 8 [--mode train --config cfg4]               # starts the 8 rank processes itself (torch.distributed.run
                                                                       # child, before anything here touches a GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      # or under a launcher
@@ -15,7 +17,10 @@ features and weights resident in HBM, replayed from one HIP graph.  value = clip
 steps / max-over-ranks wall time.  Clips are independent: ranks decode disjoint batches, no
 collective on the data path (weak scaling).
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; roofline, kernels, cpu_baseline
+and secondary are null / absent there.  --full adds them (and, under a launcher, the all-ranks training secondary).
+
+Extra objects in the JSON line (--full):
   roofline      -- the dominant kernel (largest share of the step's GPU time), achieved
                    algorithmic bytes (or flops) per launch / its average duration measured with HIP
                    events in this process; `kernels` lists every kernel of the step the same way.
@@ -99,6 +104,11 @@ def parse(argv=None):
                         "bench must not hold a GPU box until somebody's outer limit; 0 = off).  SIGTERM writes the stacks as well.")
     p.add_argument("--cpu-repeats", type=int, default=3)
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--full", action="store_true",
+                   help="decode mode: also the per-kernel HIP-event table and roofline, the CPU baseline and the secondary measurements "
+                        "(a plain run times the headline steps only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="decode mode: write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, <= 64 MB")
     return p.parse_args(argv)
 
 
@@ -316,54 +326,32 @@ def spawn_ranks(args) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
-def run_decode(args, d, dev, rank, world, dist_on, beam, steps, warmup, min_warm, cpu_baseline, over, config_name, sd_np=None):
-    """The headline measurement: K timed full decodes of B clips (graph replay), per-kernel HIP-event timing, roofline, CPU oracle.
-    Returns the bench line on rank 0, None elsewhere."""
-    from cvc import synth, hip
-    from cvc.decode import DecodeEngine, DecodeWeights
-    seed = args.seed + rank                       # every rank decodes its own clips
-    if sd_np is None:
-        sd_np = synth.hot_path_state_dict(d, args.seed)
-    feats_np = synth.clip_features(d, seed)
-    W = DecodeWeights({k: torch.from_numpy(v).to(dev) for k, v in sd_np.items()})
-    feats = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in feats_np.items()}
-    eng = DecodeEngine(W, feats, d.T, synth.UNK_IDX, beam=beam,
-                       gate_ksplit=None if args.gate_ksplit is None else (bool(args.gate_ksplit) if args.gate_ksplit < 2 else "fused"),
-                       gsk=None if args.gsk is None else bool(args.gsk), embgate=None if args.embgate is None else bool(args.embgate))
-    gemm_mode = hip.gemm_packed_split(-1)
-    if not args.no_graph:
-        eng.capture()
+DUMP_LIMIT_BYTES = 64 << 20
 
-    def sync_all():
-        torch.cuda.synchronize()
-        if dist_on:
-            import torch.distributed as dist
-            dist.barrier()
-            torch.cuda.synchronize()
 
-    w0 = time.perf_counter()
-    for _ in range(warmup):
-        eng.run()
-    torch.cuda.synchronize()
-    while time.perf_counter() - w0 < min_warm:      # untimed: DVFS / cache warm-up beyond the W steps
-        eng.run()
-        torch.cuda.synchronize()
-    sync_all()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        eng.run()
-    torch.cuda.synchronize()
-    t_local = time.perf_counter() - t0
-    sync_all()
-    elapsed = t_local
-    if dist_on:
-        from cvc.distributed import control_all_reduce
-        elapsed = control_all_reduce([t_local], "max")[0]
-    units = d.B * d.T * world * steps
-    value = units / elapsed
-    if rank != 0:
-        return None
+def dump_outputs(outs, out_dir, seed):
+    """--dump-outputs: every array as out_dir/<name>.npy, floating point as float32, integers as float64 (exact).  Above 64 MB in
+    all, every array keeps the same fixed, seeded sample of its leading-axis rows (the clips), listed in sample_rows.npy."""
+    arrs = {k: np.ascontiguousarray(v.detach().cpu().numpy()) for k, v in outs.items()}
+    arrs = {k: a.astype(np.float32 if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else np.float64) for k, a in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = {a.shape[0] for a in arrs.values()}
+        assert len(rows) == 1, {k: a.shape for k, a in arrs.items()}
+        n = rows.pop()
+        keep = max(1, int(n * (DUMP_LIMIT_BYTES - 8 * n) / total))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["sample_rows"] = idx.astype(np.float64)
+        assert sum(a.nbytes for a in arrs.values()) <= DUMP_LIMIT_BYTES, "--dump-outputs: one row is larger than the limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
+
+def decode_kernel_table(args, d, eng, beam, gemm_mode, over, config_name):
+    """--full: per-kernel durations of one decode (HIP events around every launch of an eager pass over the same buffers) and
+    the roofline of the dominant kernel.  Returns (kernels, roofline)."""
     # ---- per-kernel durations with HIP events on the launch stream (eager pass, same buffers)
     kernels, roof = [], None
     work = algorithmic_work(d, beam)
@@ -440,6 +428,64 @@ def run_decode(args, d, dev, rank, world, dist_on, beam, steps, warmup, min_warm
         roof = dict(kernel=dom["kernel"], bound="hbm", achieved=dom["achieved_GBs"], peak=HBM_PEAK_GBS, unit="GB/s",
                     frac=dom["frac_hbm"], traffic=traffic, traffic_source=traffic_note, avg_us=dom["avg_us"],
                     algorithmic_bytes=dom["algorithmic_bytes"])
+    return kernels, roof
+
+
+def run_decode(args, d, dev, rank, world, dist_on, beam, steps, warmup, min_warm, cpu_baseline, over, config_name, sd_np=None,
+               detail=True, dump_dir=None):
+    """The headline measurement: K timed full decodes of B clips (graph replay); with `detail` the per-kernel HIP-event timing and
+    roofline, with `cpu_baseline` the CPU oracle; `dump_dir`: the last timed decode's outputs (dump_outputs).
+    Returns the bench line on rank 0, None elsewhere."""
+    from cvc import synth, hip
+    from cvc.decode import DecodeEngine, DecodeWeights
+    seed = args.seed + rank                       # every rank decodes its own clips
+    if sd_np is None:
+        sd_np = synth.hot_path_state_dict(d, args.seed)
+    feats_np = synth.clip_features(d, seed)
+    W = DecodeWeights({k: torch.from_numpy(v).to(dev) for k, v in sd_np.items()})
+    feats = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in feats_np.items()}
+    eng = DecodeEngine(W, feats, d.T, synth.UNK_IDX, beam=beam,
+                       gate_ksplit=None if args.gate_ksplit is None else (bool(args.gate_ksplit) if args.gate_ksplit < 2 else "fused"),
+                       gsk=None if args.gsk is None else bool(args.gsk), embgate=None if args.embgate is None else bool(args.embgate))
+    gemm_mode = hip.gemm_packed_split(-1)
+    if not args.no_graph:
+        eng.capture()
+
+    def sync_all():
+        torch.cuda.synchronize()
+        if dist_on:
+            import torch.distributed as dist
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    w0 = time.perf_counter()
+    for _ in range(warmup):
+        eng.run()
+    torch.cuda.synchronize()
+    while time.perf_counter() - w0 < min_warm:      # untimed: DVFS / cache warm-up beyond the W steps
+        eng.run()
+        torch.cuda.synchronize()
+    sync_all()
+    out = None
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        out = eng.run()
+    torch.cuda.synchronize()
+    t_local = time.perf_counter() - t0
+    sync_all()
+    elapsed = t_local
+    if dist_on:
+        from cvc.distributed import control_all_reduce
+        elapsed = control_all_reduce([t_local], "max")[0]
+    units = d.B * d.T * world * steps
+    value = units / elapsed
+    if rank != 0:
+        return None
+    if dump_dir is not None:
+        # views of engine-owned buffers: written before anything else runs on the engine
+        dump_outputs(dict(zip(("seq", "att2_weights", "beam_scores"), out)), dump_dir, args.seed)
+
+    kernels, roof = decode_kernel_table(args, d, eng, beam, gemm_mode, over, config_name) if detail else (None, None)
 
     # ---- CPU baseline: the oracle on this box's host cores, same workload (rank 0, N=1 only)
     cpu = None
@@ -495,7 +541,7 @@ def brief(line):
     """One secondary entry: what was measured, its time and its roofline (the per-kernel table stays with the headline)."""
     keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "config", "roofline", "exchange", "gradient_buckets", "role_split")
     out = {k: line[k] for k in keep if k in line and line[k] is not None}
-    ks = [k for k in line.get("kernels", []) if "kernel" in k][:4]
+    ks = [k for k in line.get("kernels") or [] if "kernel" in k][:4]
     out["top_kernels"] = [{kk: k[kk] for kk in ("kernel", "avg_us", "ms", "ms_per_step", "share", "frac_hbm", "frac_mfma") if kk in k} for k in ks]
     return out
 
@@ -616,6 +662,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs is not None and args.mode != "decode":
+        raise SystemExit("bench.py: --dump-outputs writes the decode mode's outputs (the headline workload) only")
     import faulthandler
     import signal
     faulthandler.register(signal.SIGTERM, all_threads=True, chain=True)      # a launcher that gives up on us learns where we were
@@ -744,8 +792,10 @@ def main():
     elif args.mode == "train":
         line = run_train(args, d, dev, rank, world, comm=comm, always_exchange=args.always_exchange or dist_on)
     else:
-        line = run_decode(args, d, dev, rank, world, dist_on, args.beam, args.steps, args.warmup, args.min_warm_seconds, True, over, args.config)
-        default_cfg = (args.config == "cfg2" and not over and args.beam == 1 and not args.no_secondary and
+        # a plain run: the headline steps only; --full adds the per-kernel table, the CPU baseline and the secondary measurements
+        line = run_decode(args, d, dev, rank, world, dist_on, args.beam, args.steps, args.warmup, args.min_warm_seconds, args.full, over,
+                          args.config, detail=args.full, dump_dir=args.dump_outputs)
+        default_cfg = (args.full and args.config == "cfg2" and not over and args.beam == 1 and not args.no_secondary and
                        args.gsk is None and args.embgate is None and args.gate_ksplit is None and not args.no_graph)
         if default_cfg and world == 1 and not dist_on:
             t0 = time.perf_counter()

@@ -875,7 +875,7 @@ def test_bench_at_two_ranks_still_prints_its_decode_line_when_the_training_secon
     env = dict(_two_rank_env(tmp_path), CVC_BENCH_TEST_HANG_SECONDARY="1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = _launch_two([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0.1",
-                     "--no-cpu-baseline", "--secondary-timeout", "5"], env)
+                     "--no-cpu-baseline", "--secondary-timeout", "5", "--full"], env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
