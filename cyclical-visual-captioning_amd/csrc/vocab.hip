@@ -528,6 +528,7 @@ __global__ __launch_bounds__(WG) void lstm_pointwise_bwd4_kernel(HSrc3 src, cons
                                                                  const float* gates, const float* c_prev, const float* c_new, int M,
                                                                  int R, float* d_gates, float* d_c_prev, float* d_gates_q, float* dg_sum,
                                                                  int q_row0) {
+#pragma clang fp contract(off)          // (every operation rounds on its own: the same bits as the vector form, see below)
     const int j = blockIdx.x * WG + threadIdx.x;
     const int m = blockIdx.y;
     if (j >= R) return;
@@ -561,7 +562,9 @@ __global__ __launch_bounds__(WG) void lstm_pointwise_bwd4_kernel(HSrc3 src, cons
 
 // The same arithmetic, four hidden units per thread: every operand as one 16-byte load, and the K-slice planes of a gradient source
 // requested four at a time before the first is added (the scalar form above walks a source's planes one dependent load after the
-// other -- three sources x 5-8 planes of memory latency in an 11 us launch).  Sums in the same order: same bits.
+// other -- three sources x 5-8 planes of memory latency in an 11 us launch).  Sums in the same order, and contraction into fused
+// multiply-adds switched OFF in both forms (hipcc's device default, -ffp-contract=fast, fused the two forms' dcn differently: 1-2 ulp
+// apart in d_gates i/f/g and d_c_prev): same bits.
 __device__ __forceinline__ f32x4 hsrc_load4(const cvc_grad_src& g, int m, int j) {
     if (g.p == nullptr) return f32x4{0.f, 0.f, 0.f, 0.f};
     const float* p = g.p + (size_t)m * g.ld + j;
@@ -579,6 +582,7 @@ __device__ __forceinline__ void lstm_pointwise_bwd4v_body(const HSrc3& src, cons
                                                           const float* gates, const float* c_prev, const float* c_new, int M,
                                                           int R, float* d_gates, float* d_c_prev, float* d_gates_q, float* dg_sum,
                                                           int q_row0) {
+#pragma clang fp contract(off)
     const int j = (blockIdx.x * blockDim.x + threadIdx.x) * 4;      // (64-thread workgroups: 8 x M of them at R = 2048)
     const int m = blockIdx.y;
     if (j >= R || m >= M) return;
