@@ -1,0 +1,176 @@
+// Sampled decoding: Gumbel-max selection of the next word from softmax(logits / tau) without UNK, n captions per clip.
+// The selection block of the decode engine's sampling mode (cvc/decode/engine.py, sample_n / temperature): one workgroup per row
+// sums the K-slice slabs of the vocabulary GEMM (+ bias) in the finishing pass's order (cvc_tile_linear_finish: slab 0 + slab 1 +
+// ... + bias, so the logits are bit for bit what the greedy / beam selection sees), draws the noise in-kernel from the
+// counter-based hash of csrc/dropout_rng.h and writes the word and its log-prob.
+//
+//   h        = cvc_drop_hash(seed_lo, seed_hi, call, CVC_SAMPLE_SITE + t, r * V + v)
+//   u        = ((h >> 9) + 0.5) * 2^-23                  exactly representable, strictly inside (0, 1)
+//   g        = -logf(-logf(u))                           accurate logf (not __logf)
+//   s        = z[r, v] * inv_tau + g                     product rounded, then the sum (no contraction)
+//   word[r]  = argmax over v != unk of s                 ties -> lower index
+//   logprob  = z[r, word] - logsumexp_v z[r, v]          full V, UNK included, independent of tau
+//
+// The state is 4 words of device memory {seed_lo, seed_hi, call, 0}; cvc_sample_advance adds 1 to `call` (the first launch of a
+// sampled decode, so a graph replay draws fresh noise).  Every reduction runs in a fixed order: the result is bitwise
+// deterministic.  The row's logits stay in registers (NC per thread, V <= 256 * SAMPLE_NC_MAX), loaded as float4 where V % 4 == 0.
+#include "cvc_common.h"
+#include "dropout_rng.h"
+#include <math.h>
+
+namespace {
+
+constexpr int WG = 256;
+constexpr int SAMPLE_NC_MAX = 32;              // logits per thread: V <= 8192, the bound of cvc_beam_select_parts
+
+__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) { return (va > vb) | ((va == vb) & (ia < ib)); }
+
+// the Gumbel perturbation of hash value h (its 23 high bits)
+__device__ __forceinline__ float gumbel(uint32_t h) {
+    const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;
+    return -logf(-logf(u));
+}
+
+// NC logits per thread; NP > 0: that many slabs summed with an unrolled loop, NP == 0: nparts at run time.  VEC (V % 4 == 0,
+// 16-byte aligned operands): NC / 4 float4 groups, element u at column (tid + (u / 4) * WG) * 4 + u % 4; otherwise column tid + u * WG.
+// Both sum a column's slabs in the same order (same bits); only the loads differ.
+template <int NC, int NP, bool VEC>
+__global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, int nparts, long long part_stride, const float* bias,
+                                                           int V, int unk, float inv_tau, const uint32_t* state, uint32_t site,
+                                                           int64_t* word, int wstride, float* logprob) {
+#pragma clang fp contract(off)
+    __shared__ float red_m[4], red_s[4], red_v[4], red_z[4];
+    __shared__ int red_i[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t seed_lo = state[0], seed_hi = state[1], call = state[2];
+    const float* x = parts + (size_t)row * V;
+    float z[NC];
+    auto col = [&](int u) { return VEC ? (tid + (u >> 2) * WG) * 4 + (u & 3) : tid + u * WG; };
+    if constexpr (VEC) {
+#pragma unroll
+        for (int g = 0; g < NC / 4; ++g) {
+            const int e = (tid + g * WG) * 4;
+            f32x4 s = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (e < V) {                                  // V % 4 == 0: the whole group is inside the row
+                if constexpr (NP > 0) {
+                    f32x4 p[NP];
+#pragma unroll
+                    for (int k = 0; k < NP; ++k) p[k] = ld4(x + (size_t)k * part_stride + e);
+                    s = p[0];
+#pragma unroll
+                    for (int k = 1; k < NP; ++k) s += p[k];
+                } else {
+                    s = ld4(x + e);
+                    for (int k = 1; k < nparts; ++k) s += ld4(x + (size_t)k * part_stride + e);
+                }
+                if (bias != nullptr) s += ld4(bias + e);
+            }
+            z[4 * g] = s.x; z[4 * g + 1] = s.y; z[4 * g + 2] = s.z; z[4 * g + 3] = s.w;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            const int v = col(u);
+            float s = -INFINITY;
+            if (v < V) {
+                s = x[v];
+                for (int k = 1; k < nparts; ++k) s += x[(size_t)k * part_stride + v];
+                if (bias != nullptr) s += bias[v];
+            }
+            z[u] = s;
+        }
+    }
+    // perturbed scores: the best (s, v) and its logit; the row's maximum logit
+    float bs = -INFINITY, bz = -INFINITY, m = -INFINITY;
+    int bi = 0x7fffffff;
+    const uint32_t base = (uint32_t)row * (uint32_t)V;
+#pragma unroll
+    for (int u = 0; u < NC; ++u) {
+        const int v = col(u);
+        if (v < V) {
+            m = fmaxf(m, z[u]);
+            if (v != unk) {
+                const float s = z[u] * inv_tau + gumbel(cvc_drop_hash(seed_lo, seed_hi, call, site, base + (uint32_t)v));
+                if (better(s, v, bs, bi)) { bs = s; bi = v; bz = z[u]; }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float os = __shfl_xor(bs, o, 64), oz = __shfl_xor(bz, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (better(os, oi, bs, bi)) { bs = os; bi = oi; bz = oz; }
+    }
+    m = wave_max(m);
+    if (lane == 0) { red_m[wave] = m; red_v[wave] = bs; red_i[wave] = bi; red_z[wave] = bz; }
+    __syncthreads();
+    m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float se = 0.f;
+    if (m != -INFINITY) {
+#pragma unroll
+        for (int u = 0; u < NC; ++u) se += expf(z[u] - m);          // padding: exp(-inf) = 0
+    }
+    se = wave_sum(se);
+    if (lane == 0) red_s[wave] = se;
+    __syncthreads();
+    if (tid == 0) {
+        bs = red_v[0]; bi = red_i[0]; bz = red_z[0];
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[w], red_i[w], bs, bi)) { bs = red_v[w]; bi = red_i[w]; bz = red_z[w]; }
+        const float S = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
+        int w = bi;
+        if (w < 0 || w >= V) w = 0;        // every score NaN: nothing compared better; the word is a gather index next step
+        word[(size_t)row * wstride] = w;
+        if (logprob != nullptr) logprob[row] = bz - (m + logf(S));
+    }
+}
+
+__global__ void sample_advance_kernel(uint32_t* state) {
+    if (threadIdx.x == 0) state[2] = state[2] + 1u;
+}
+
+}  // namespace
+
+extern "C" int cvc_sample_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
+                                       int unk_idx, float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride,
+                                       float* logprob, cvc_stream_t stream) {
+    if (!parts || !rng_state || !word || nparts < 1 || M < 1 || V < 2 || word_stride < 1 || t < 0) return CVC_E_BADARG;
+    if (!(inv_tau > 0.f) || !isfinite(inv_tau)) return CVC_E_BADARG;
+    if (nparts > 1 && part_stride < (long long)M * V) return CVC_E_BADARG;
+    if ((long long)M * V > 0xffffffffLL) return CVC_E_TOOBIG;          // the hash counter r * V + v is one 32-bit word
+    const int nc = (V + WG - 1) / WG;
+    if (nc > SAMPLE_NC_MAX) return CVC_E_TOOBIG;
+    const uint32_t site = CVC_SAMPLE_SITE + (uint32_t)t;
+    const bool vec = (V & 3) == 0 && ((uintptr_t)parts & 15) == 0 && (nparts == 1 || (part_stride & 3) == 0) &&
+                     ((uintptr_t)bias & 15) == 0;
+#define CVC_SS(NC_, NP_, VEC_) hipLaunchKernelGGL((sample_select_kernel<NC_, NP_, VEC_>), dim3(M), dim3(WG), 0, (hipStream_t)stream, \
+                                                  parts, nparts, part_stride, bias, V, unk_idx, inv_tau, rng_state, site, word, \
+                                                  word_stride, logprob)
+#define CVC_SS_NP(NG_) do { switch (nparts) { case 1: CVC_SS(4 * NG_, 1, true); break; case 2: CVC_SS(4 * NG_, 2, true); break; \
+                                              case 4: CVC_SS(4 * NG_, 4, true); break; case 6: CVC_SS(4 * NG_, 6, true); break; \
+                                              case 8: CVC_SS(4 * NG_, 8, true); break; default: CVC_SS(4 * NG_, 0, true); break; } \
+                           } while (0)
+    if (vec) {                                             // float4 groups: V <= NG * 1024
+        const int ng = (V + 4 * WG - 1) / (4 * WG);
+        if (ng <= 1) CVC_SS_NP(1);
+        else if (ng <= 2) CVC_SS_NP(2);
+        else if (ng <= 4) CVC_SS_NP(4);
+        else if (ng <= 5) CVC_SS_NP(5);
+        else CVC_SS_NP(8);
+    } else if (nc <= 1) CVC_SS(1, 0, false);
+    else if (nc <= 2) CVC_SS(2, 0, false);
+    else if (nc <= 4) CVC_SS(4, 0, false);
+    else if (nc <= 8) CVC_SS(8, 0, false);
+    else if (nc <= 16) CVC_SS(16, 0, false);
+    else if (nc <= 20) CVC_SS(20, 0, false);
+    else CVC_SS(32, 0, false);
+#undef CVC_SS_NP
+#undef CVC_SS
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream) {
+    if (!rng_state) return CVC_E_BADARG;
+    hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rng_state);
+    return cvc_launch_status();
+}

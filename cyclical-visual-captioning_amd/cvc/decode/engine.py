@@ -8,6 +8,7 @@ import os
 from typing import Dict, List, Optional, Tuple
 
 
+import numpy as np
 import torch
 
 from .. import hip
@@ -37,7 +38,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
 
     def __init__(self, weights: DecodeWeights, feats: Dict[str, torch.Tensor], T: int, unk_idx: int, beam: int = 1,
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
-                 driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None):
+                 driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
+                 sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -49,11 +51,33 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         gsk: packed path only -- True selects the grouped stream-K schedule (csrc/gemm_gsk.hip; measured slower than the
         embedding-gate schedule, kept selectable and tested; needs R % 64 == 0, split-product arithmetic).
         path: "auto" picks packed (greedy, <= 64 rows) / tile (> 64 rows or beams) / ring (odd widths); "ring" forces the
-        row-major fallback kernels (tests compare the paths).
+        row-major fallback kernels, "tile" the tile path at any row count (tests compare the paths).
         own_features: keep private copies of the clip features, so that the bound launch list (and a captured HIP
-        graph) can be reused for the next batch of the same shape through load_features()."""
+        graph) can be reused for the next batch of the same shape through load_features().
+        temperature: None = the arg-max word (greedy / beam, as always).  A value tau > 0 samples every word from softmax(logits /
+        tau) without UNK (Gumbel-max, csrc/sample.hip), sample_n captions per clip (row b * sample_n + j is sample j of clip b),
+        noise from the engine's own generator state {seed_lo, seed_hi, call, 0} (seed(); every decode first advances `call`).
+        A sampling engine walks its launch list from Python (no C driver); beam > 1, gsk, gate_ksplit, lang_ksx and the packed
+        path without the embedding-gate schedule are refused."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
+        self.sampling = temperature is not None
+        if self.sampling:
+            tau = float(temperature)
+            if not (0.0 < tau < float("inf")):
+                raise RuntimeError(f"DecodeEngine: the sampling temperature must be a positive finite number, got {temperature!r}")
+            if self.beam != 1:
+                raise RuntimeError("DecodeEngine: sampling (temperature) and beam search (beam > 1) exclude each other")
+            if gsk or gate_ksplit or lang_ksx:
+                raise RuntimeError("DecodeEngine: sampling runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
+            if int(sample_n) < 1:
+                raise RuntimeError(f"DecodeEngine: sample_n must be >= 1, got {sample_n}")
+            self.inv_tau = 1.0 / tau
+            gate_ksplit, lang_ksx = False, False
+        elif int(sample_n) != 1:
+            raise RuntimeError("DecodeEngine: sample_n > 1 needs a sampling temperature")
+        # queries per clip: the beams of beam search, the samples of sampled decoding (attention passes, gate_fc rows)
+        self.nq = int(sample_n) if self.sampling else self.beam
         fc, conv, pconv = feats["fc_feats"], feats["conv_feats"], feats["p_conv_feats"]
         pool, ppool = feats["pool_feats"], feats["p_pool_feats"]
         mask = feats["pnt_mask"][:, 1:] if feats["pnt_mask"].shape[1] == pool.shape[1] + 1 else feats["pnt_mask"]
@@ -72,7 +96,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.own_features = own_features
         self.feats = (fc, conv, pconv, pool, ppool)
         nb = lambda t: t.numel() * t.element_size()
-        rows = self.rows = B * self.beam
+        rows = self.rows = B * self.nq
         f32 = dict(device=dev, dtype=torch.float32)
         z = lambda *s: torch.zeros(*s, **f32)
         # ping-pong recurrent state: index t & 1 is read, (t+1) & 1 is written
@@ -93,7 +117,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.logprob = z(self.T, rows)
         # fc is per clip; beams of a clip read the same row through a row-gather index
         self.fc = fc
-        self.clip_of_row = torch.arange(rows, device=dev, dtype=torch.int64) // self.beam
+        self.clip_of_row = torch.arange(rows, device=dev, dtype=torch.int64) // self.nq
+        if self.sampling:
+            self.rng = torch.zeros(4, device=dev, dtype=torch.int32)          # {seed_lo, seed_hi, call, 0} (uint32 bit patterns)
+            self.seed(0 if seed is None else seed)
         if self.beam > 1:
             self.score = z(2, rows)
             self.done = torch.zeros(2, rows, dtype=torch.uint8, device=dev)
@@ -105,7 +132,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
-        self.packed = self.beam == 1 and rows <= 64 and R % 32 == 0 and W.E % 32 == 0 and A % 32 == 0
+        self.packed = self.nq == 1 and rows <= 64 and path != "tile" and R % 32 == 0 and W.E % 32 == 0 and A % 32 == 0
         # packed path: K-split gate GEMMs (activations shared through LDS, csrc/gemm_packed_ks.hip) where the shape allows
         # (True: partial tiles + a finishing launch; "fused": the last-arriving K slice of a tile finishes it in the same launch)
         self.gate_ksplit = GATE_KSPLIT_DEFAULT if gate_ksplit is None else gate_ksplit
@@ -116,11 +143,14 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             raise RuntimeError("DecodeEngine: the stream-K schedule needs the packed path, R % 64 == 0 and cvc_gemm_packed_split(2)")
         self.gsk = False if gsk is None else bool(gsk)
         # more than 64 live rows (beam search, big greedy batches): bf16-fragment tile GEMMs (csrc/gemm_tile.hip)
-        self.tile = (not self.packed) and (self.beam > 1 or rows > 64) and R % 16 == 0 and W.E % 16 == 0 and path != "ring"
+        self.tile = (not self.packed) and (self.nq > 1 or rows > 64 or path == "tile") and R % 16 == 0 and W.E % 16 == 0 and path != "ring"
         eg_ok = (self.packed and not self.gsk and not self.gate_ksplit) or self.tile
         if embgate and not eg_ok:
             raise RuntimeError("DecodeEngine: the embedding-gate schedule needs the packed path (without gsk / gate_ksplit) or the tile path")
         self.embgate = (eg_ok and 4 * V * 4 * R <= EMBGATE_MAX_BYTES) if embgate is None else bool(embgate)
+        if self.sampling and self.packed and not self.embgate:
+            raise RuntimeError("DecodeEngine: sampling on the packed path needs the embedding-gate schedule (the attention cell reads "
+                               "the sampled word from words[t])")
         # what stays in the Infinity Cache between steps: small linear weights, then (embedding-gate schedule on the packed path) the
         # attention cell's gate matrix over K = 2R if it fits, then the largest subset of the feature tensors
         keep = cache_plan(4 * (V * R + A * R), {"ppool": nb(ppool), "pconv": nb(pconv), "pool": nb(pool), "conv": nb(conv)},
@@ -146,13 +176,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.ksx_flags = torch.zeros(R // 8 + 1, device=dev, dtype=torch.int32)
         if self.packed:
             self._alloc_packed()
-            self._launches = self._build_packed()
         elif self.tile:
             self._alloc_tile()
-            self._launches = self._build_tile()
-        else:
-            self._launches = self._build()
-        if driver and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
+        self._launches = self._build_launches()
+        if driver and not self.sampling and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
 
     # ------------------------------------------------------------------ C-ABI decode driver (csrc/decode_driver.hip)
@@ -303,10 +330,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self._launches = None                       # the Python launch list holds the old pointers: rebuilt on demand
         return self
 
+    def _build_launches(self):
+        out = self._build_packed() if self.packed else (self._build_tile() if self.tile else self._build())
+        if self.sampling:            # first entry: a fresh `call` for every decode (and every replay of a captured graph)
+            out.insert(0, ("sample_advance", hip.lib().cvc_sample_advance, (self.rng.data_ptr(),)))
+        return out
+
     def _python_launches(self):
         if self._launches is None:
             self._keep = []
-            self._launches = self._build_packed() if self.packed else (self._build_tile() if self.tile else self._build())
+            self._launches = self._build_launches()
         return self._launches
 
     def run_timed(self):
@@ -339,13 +372,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
+            saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
+            if saved is not None:
+                self.rng.copy_(saved)
             DecodeEngine._warm.add(key)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode=_capture_mode()):
@@ -353,15 +389,28 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.graph = g
         return self
 
+    def seed(self, s: int):
+        """Sampling: the generator state becomes {seed_lo, seed_hi, 0, 0} of the 64-bit seed s (a stream-ordered copy); the k-th
+        decode after it draws its noise with call = k."""
+        if not self.sampling:
+            raise RuntimeError("DecodeEngine.seed: this engine does not sample (temperature=None)")
+        s = int(s) & 0xFFFFFFFFFFFFFFFF
+        words = np.array([s & 0xFFFFFFFF, s >> 32, 0, 0], dtype=np.uint32).view(np.int32)
+        self.rng.copy_(torch.from_numpy(words))
+        return self
+
     def run(self):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
-        engine-owned buffers (clone to keep across runs)."""
+        engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],
+        logprob [B*n, T]), row b * n + j = sample j of clip b."""
         if self.graph is not None:
             self.graph.replay()
         else:
             self._run_once()
             if self.lang_ksx and not self._ksx_checked and self.check_ksx():
                 self._run_once()                           # the fallback's results
+        if self.sampling:
+            return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t()
         if self.beam == 1:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2)
         return self._backtrack()

@@ -173,9 +173,17 @@ class PackedPath:
                                                                  ptr(self.cL[wr]))))
             # (cvc_packed_linear_select_fwd, the one-launch form whose last workgroup merges the records, measured 34.9 us against
             # 20.0 + 7.4 us for these two launches: atomics, fence and a serial merge on one CU cost more than a launch boundary)
-            out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
-                                                            ptr(self.top2_part))))
-            out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
-                                                          ptr(self.logprob[t]), None, 0, None, 0)))
+            if self.sampling:
+                # row-major logits, then the sampling block (the attention cell of step t + 1 reads the word from words[t + 1])
+                out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V,
+                                                                None)))
+                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
+                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
+                                                                       ptr(self.logprob[t]))))
+            else:
+                out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
+                                                                ptr(self.top2_part))))
+                out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
+                                                              ptr(self.logprob[t]), None, 0, None, 0)))
             self._keep.append(sets)
         return out

@@ -17,23 +17,26 @@ class RingPath:
     def _build(self):
         L, W = hip.lib(), self.W
         B, N, Fr, R, A, E, V, rows, beam = self.B, self.N, self.F, W.R, W.A, W.E, W.V, self.rows, self.beam
+        nq, sampling = self.nq, self.sampling          # queries per clip (beams or samples)
         fc, conv, pconv, pool, ppool = self.feats
         ptr = lambda t: None if t is None else t.data_ptr()
         out = []
         # fc_feats does not change over the T steps (decoder_core.py:46): its gate contribution and the
         # two bias vectors are computed once per decode, inside the timed/captured region
-        seg_fc = _segs([(fc, self.clip_of_row if beam > 1 else None, W.w_ih_att[:, R:2 * R], False)])
+        seg_fc = _segs([(fc, self.clip_of_row if nq > 1 else None, W.w_ih_att[:, R:2 * R], False)])
         out.append(("gate_fc", L.cvc_linear_fwd, (seg_fc, 1, ptr(W.b_ih_att), ptr(W.b_hh_att), rows, 4 * R, ptr(self.gate_fc),
                                                   4 * R)))
         self._keep.append(seg_fc)
-        if beam == 1 and rows <= 64:
+        # the embedded word as a row-major buffer (written by the word-selection step): greedy <= 64 rows, and sampling
+        emb_buf = sampling or (beam == 1 and rows <= 64)
+        if emb_buf:
             out.append(("embed_bos", L.cvc_embed_relu_fwd, (ptr(W.embed), ptr(self.words[0]), None, rows, E, ptr(self.emb))))
         for t in range(self.T):
             rd, wr = t & 1, (t + 1) & 1
             # att-LSTM: [h_lang(t-1) | relu(Emb[word_t])] x W_ih  +  h_att(t-1) x W_hh  + gate_fc
-            fused_head = beam == 1 and rows <= 64
+            fused_head = beam == 1 and rows <= 64 and not sampling
             seg_att = _segs([(self.h_lang[rd], None, W.w_ih_att[:, 0:R], False),
-                             (self.emb, None, W.w_ih_att[:, 2 * R:2 * R + E], False) if fused_head else
+                             (self.emb, None, W.w_ih_att[:, 2 * R:2 * R + E], False) if emb_buf else
                              (W.embed, self.words[t], W.w_ih_att[:, 2 * R:2 * R + E], True),
                              (self.h_att[rd], None, W.w_hh_att, False)])
             out.append(("att_lstm", L.cvc_lstm_cell_fwd, (seg_att, 3, None, None, ptr(self.gate_fc), ptr(self.c_att[rd]),
@@ -51,11 +54,11 @@ class RingPath:
                                   self.stream_f)
             if split_q:
                 out.append(("attn_scores", L.cvc_attn_scores_qparts, (W.kind, ptr(self.q_parts), self.QSPLIT, ptr(W.b_h),
-                                                                      ptr(W.w_a), ptr(W.b_a), self.inv_temp, sets, 2, B, beam, A)))
+                                                                      ptr(W.w_a), ptr(W.b_a), self.inv_temp, sets, 2, B, nq, A)))
             else:
                 out.append(("attn_scores", L.cvc_attn_scores, (W.kind, ptr(self.q), ptr(W.w_a), ptr(W.b_a), self.inv_temp, sets,
-                                                               2, B, beam, A)))
-            out.append(("attn_wsum", L.cvc_attn_wsum, (sets, 2, B, beam, R, ptr(self.ctx_sum))))
+                                                               2, B, nq, A)))
+            out.append(("attn_wsum", L.cvc_attn_wsum, (sets, 2, B, nq, R, ptr(self.ctx_sum))))
             seg_lang = _segs([(self.ctx_sum, None, W.w_ih_lang[:, 0:R], False),
                               (self.h_att[wr], None, W.w_ih_lang[:, R:2 * R], False),
                               (self.h_lang[rd], None, W.w_hh_lang, False)])
@@ -63,7 +66,15 @@ class RingPath:
                                                            ptr(self.c_lang[rd]), rows, R, ptr(self.h_lang[wr]),
                                                            ptr(self.c_lang[wr]), None)))
             seg_o = _segs([(self.h_lang[wr], None, W.w_o, False)])
-            if fused_head:
+            if sampling:
+                # finished logits, the sampling block, then next step's embedded word relu(Emb[word])
+                out.append(("logits", L.cvc_linear_fwd, (seg_o, 1, ptr(W.b_o), None, rows, V, ptr(self.logits), V)))
+                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
+                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
+                                                                       ptr(self.logprob[t]))))
+                if t + 1 < self.T:
+                    out.append(("embed", L.cvc_embed_relu_fwd, (ptr(W.embed), ptr(self.words[t + 1]), None, rows, E, ptr(self.emb))))
+            elif fused_head:
                 # vocabulary projection with the top-2 / log-sum-exp partials in its epilogue ([B,V] logits are
                 # never written), then merge + UNK rule + next step's embedded word
                 out.append(("logits", L.cvc_linear_top2_fwd, (seg_o, 1, ptr(W.b_o), rows, V, None, ptr(self.top2_part))))

@@ -63,6 +63,7 @@ class TilePath:
     def _build_tile(self):
         L, W = hip.lib(), self.W
         B, N, Fr, R, A, E, V, rows, beam = self.B, self.N, self.F, W.R, W.A, W.E, W.V, self.rows, self.beam
+        nq = self.nq                                   # queries per clip: the beams, or the samples of sampled decoding
         fc, conv, pconv, pool, ppool = self.feats
         ptr = lambda t: None if t is None else t.data_ptr()
         fp = hip._frag_ptr
@@ -82,7 +83,7 @@ class TilePath:
         zero = ptr(self.t_zero)
         eg = self.embgate
         E_pack = 0 if eg else E                        # embedding-gate form: no embedding segment in XA, the word enters in the finish
-        out.append(("beam_reorder", L.cvc_tile_reorder_pack, (None, ptr(self.words[0]), beam, zero, zero, zero, zero, ptr(W.embed), E_pack, V,
+        out.append(("beam_reorder", L.cvc_tile_reorder_pack, (None, ptr(self.words[0]), nq, zero, zero, zero, zero, ptr(W.embed), E_pack, V,
                                                               ptr(self.t_c_att_prev), ptr(self.t_c_lang_prev), xa_p, xa_s, xl_hlang,
                                                               xl_s, rows, R)))
         for t in range(self.T):
@@ -90,12 +91,12 @@ class TilePath:
                                                       ptr(self.parts_gate), 4 * R, rows * 4 * R)))
             if eg:
                 out.append(("att_finish", L.cvc_tile_lstm_finish_embgate, (ptr(self.parts_gate), self.ks_gate, rows * 4 * R, None, None,
-                                                                           ptr(self.gate_fc_clip), beam, ptr(W.t_embgate), ptr(self.words[t]), V,
+                                                                           ptr(self.gate_fc_clip), nq, ptr(W.t_embgate), ptr(self.words[t]), V,
                                                                            ptr(self.t_c_att_prev), rows, R, ptr(self.t_c_att),
                                                                            ptr(self.t_h_att), xl_hatt, xl_s, None, 0)))
             else:
                 out.append(("att_finish", L.cvc_tile_lstm_finish, (ptr(self.parts_gate), self.ks_gate, rows * 4 * R, None, None,
-                                                                   ptr(self.gate_fc_clip), beam, ptr(self.t_c_att_prev), rows, R,
+                                                                   ptr(self.gate_fc_clip), nq, ptr(self.t_c_att_prev), rows, R,
                                                                    ptr(self.t_c_att), ptr(self.t_h_att), xl_hatt, xl_s, None, 0)))
             out.append(("h2attn", L.cvc_tile_gemm, (ptr(W.t_h), xl_hatt, xl_s, R, rows, A, self.ks_q, ptr(self.parts_q), A, rows * A)))
             sets = (hip.AttnSet * 2)()
@@ -108,8 +109,8 @@ class TilePath:
             out.append(("h2attn_finish", L.cvc_tile_linear_finish, (ptr(self.parts_q), self.ks_q, rows * A, A, ptr(W.b_h), None, rows, A,
                                                                     ptr(self.q), A)))
             out.append(("attn_scores", L.cvc_attn_scores, (W.kind, ptr(self.q), ptr(W.w_a), ptr(W.b_a), self.inv_temp, sets, 2, B,
-                                                           beam, A)))
-            out.append(("attn_wsum", L.cvc_attn_wsum_frag, (sets, 2, B, beam, R, xl_p, xl_s)))
+                                                           nq, A)))
+            out.append(("attn_wsum", L.cvc_attn_wsum_frag, (sets, 2, B, nq, R, xl_p, xl_s)))
             out.append(("lang_lstm", L.cvc_tile_gemm, (ptr(W.t_lang), xl_p, xl_s, 3 * R, rows, 4 * R, self.ks_gate,
                                                        ptr(self.parts_gate), 4 * R, rows * 4 * R)))
             out.append(("lang_finish", L.cvc_tile_lstm_finish, (ptr(self.parts_gate), self.ks_gate, rows * 4 * R, ptr(W.b_ih_lang),
@@ -119,10 +120,16 @@ class TilePath:
             # beams: the selection sums the K-slice slabs itself (in the finishing pass's order: same logits bit for bit), the
             # finished [rows, V] matrix is neither written nor read back; CVC_BEAM_FINISH=1 keeps the separate pass (A/B)
             fused_sel = beam > 1 and self.ks_o in (2, 4, 6, 8) and V % 4 == 0 and os.environ.get("CVC_BEAM_FINISH") != "1"
-            if not fused_sel:
+            if not fused_sel and not self.sampling:
                 out.append(("logits_finish", L.cvc_tile_linear_finish, (ptr(self.parts_o), self.ks_o, rows * V, V, ptr(W.b_o), None, rows, V,
                                                                         ptr(self.logits), V)))
-            if beam == 1:
+            if self.sampling:
+                # the sampling block sums the K-slice slabs itself, in the finishing pass's order
+                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.parts_o), self.ks_o, rows * V, ptr(W.b_o), rows, V,
+                                                                       self.unk, self.inv_tau, ptr(self.rng), t,
+                                                                       ptr(self.words[t + 1]), 1, ptr(self.logprob[t]))))
+                parent = None
+            elif beam == 1:
                 out.append(("word_select", L.cvc_top2_unk, (ptr(self.logits), rows, V, self.unk, ptr(self.words[t + 1]), 1,
                                                             ptr(self.logprob[t]))))
                 parent = None
@@ -135,7 +142,7 @@ class TilePath:
                                                                            ptr(self.done[swr]), ptr(self.beam_ws))))
                 parent = ptr(self.parent[t])
             if t + 1 < self.T:
-                out.append(("beam_reorder", L.cvc_tile_reorder_pack, (parent, ptr(self.words[t + 1]), beam, ptr(self.t_h_att),
+                out.append(("beam_reorder", L.cvc_tile_reorder_pack, (parent, ptr(self.words[t + 1]), nq, ptr(self.t_h_att),
                                                                       ptr(self.t_c_att), ptr(self.t_h_lang), ptr(self.t_c_lang),
                                                                       ptr(W.embed), E_pack, V, ptr(self.t_c_att_prev),
                                                                       ptr(self.t_c_lang_prev), xa_p, xa_s, xl_hlang, xl_s, rows, R)))

@@ -30,7 +30,9 @@ from .trainer import Trainer, build_optimizer
 LAST_TRAINER = None
 
 
-def main(argv=None):
+def main(argv=None, sample=None):
+    """sample: (n, temperature, seed) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample)."""
     parser = cvc_opts.build_parser()
     parser.add_argument("--synthetic_clips", type=int, default=128)
     parser.add_argument("--no_cfg", action="store_true", help="skip the YAML overlay (pure CLI)")
@@ -122,6 +124,13 @@ def main(argv=None):
     trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer)
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
+    if sample is not None:
+        path = trainer.sample(*sample)
+        if rank == 0:
+            print("samples written to %s" % path)
+        if comm is not None:
+            destroy_exchange_comm()
+        return 0
     scheduler = ReduceLROnPlateau(optimizer, 'max', patience=opt.patience, min_lr=opt.min_lr)
     tb = utils.set_tb_logger(opt.tb_log_dir, opt.exp_name, opt.resume) if (rank == 0 and opt.tensorboard and not opt.inference_only) else None
 

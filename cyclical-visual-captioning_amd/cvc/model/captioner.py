@@ -90,6 +90,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.xe_criterion = utils.LanguageCriterion()
         self.beam_size = int(getattr(opts, "beam_size", 1))
         self.use_hip_graph = bool(getattr(opts, "hip_graph", False))
+        # decoding rule of _sample: sample_max = 1 takes the arg-max word (greedy / beam); sample_max = 0 samples from
+        # softmax(logits / sample_temperature) without UNK, sample_n captions per clip, noise seeded with sample_seed
+        self.sample_max = int(getattr(opts, "sample_max", 1))
+        self.sample_temperature = float(getattr(opts, "temperature", 1.0))
+        self.sample_n = int(getattr(opts, "sample_n", 1))
+        self.sample_seed = int(getattr(opts, "sample_seed", 0))
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
         # output_seq) that the reference computes as locals of _forward_3_loops and never returns
         self.debug_collect: Optional[dict] = None
@@ -448,20 +454,28 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
 
     @torch.no_grad()
     def _sample(self, segs_feat, seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats, frm_mask, sample_idx,
-                pnt_mask, beam_size: Optional[int] = None):
+                pnt_mask, beam_size: Optional[int] = None, sample_max: Optional[int] = None, temperature: Optional[float] = None,
+                sample_n: Optional[int] = None, seed: Optional[int] = None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
-        suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None)."""
+        suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
+        sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
+        UNK, sample_n captions per clip -> (seq [B*n, T], att2_weights [B*n, T, N], logprob [B*n, T]), row b * n + j = sample j of
+        clip b.  The sampling engine is seeded once, when it is created (seed); later batches draw fresh noise."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
             segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
                      pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
         beam = self.beam_size if beam_size is None else int(beam_size)
         temp = float(getattr(self.opts, "softmax_temp", 1.0))
+        sampling = (self.sample_max if sample_max is None else int(sample_max)) == 0
+        tau = (self.sample_temperature if temperature is None else float(temperature)) if sampling else None
+        n = (self.sample_n if sample_n is None else int(sample_n)) if sampling else 1
+        s_seed = (self.sample_seed if seed is None else int(seed)) if sampling else None
         weights = self.decode_weights()
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph)
+               self.use_hip_graph, tau, n, s_seed)
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -473,9 +487,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             else:
                 engine.load_features(feats)
         else:
-            engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True)
+            engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
+                                  sample_n=n, temperature=tau, seed=s_seed)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)
         res = engine.run()
+        if sampling:
+            return res[0].clone(), res[1].clone(), res[2].clone()
         return res[0].clone(), res[1].clone(), None

@@ -550,6 +550,44 @@ class Trainer:
         self.predictions = predictions
         return lang_stats
 
+    def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None):
+        """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
+        without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise).
+        Writes <results_dir>/<stem>_samples.json (rank 0, as eval does; stem defaults to densecap-<val_split>-<id>):
+            {video: [{"segment": seg_idx, "timestamp": [start, end], "sentences": [n], "logprobs": [n]}]}
+        logprobs[j]: the sum of the log-probs of sample j's words up to and including its first EOS (all T steps without one).
+        Returns the path (None on the other ranks)."""
+        model = getattr(self.model, "module", self.model)
+        model.eval()
+        o, ds = self.opts, self.dataset
+        timestamps = self._segment_timestamps()
+        samples = defaultdict(list)
+        n = int(n)
+        with torch.no_grad():
+            for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
+                seq, _, logprob = model._sample(b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"],
+                                                b["gt_bboxs"], b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"],
+                                                sample_max=0, temperature=temperature, sample_n=n, seed=seed)
+                sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
+                                              getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
+                # sequence log-prob: the steps up to and including the first EOS (word 0)
+                ended = torch.cumsum((seq == 0).to(torch.int32), 1) - (seq == 0).to(torch.int32)
+                seq_lp = (logprob * (ended == 0).to(logprob.dtype)).sum(1).tolist()
+                for k, seg_id in enumerate(b["seg_id"]):
+                    vid_idx, entry = densecap_entry(sents[k * n], seg_id, timestamps)
+                    samples[vid_idx].append({"segment": entry["segment"], "timestamp": entry["timestamp"],
+                                             "sentences": sents[k * n:(k + 1) * n], "logprobs": seq_lp[k * n:(k + 1) * n]})
+        samples, _ = gather_eval_outputs(samples, {})
+        self.samples = samples
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
+            return None
+        d = getattr(o, "results_dir", "results")
+        os.makedirs(d, exist_ok=True)
+        path = os.path.join(d, (stem or "densecap-%s-%s" % (o.val_split, o.id)) + "_samples.json")
+        with open(path, "w") as f:
+            json.dump(samples, f)
+        return path
+
     def _collect_grounding(self, b, seq, att2_weights, grd_output):
         """Per generated word, the most attended proposal of every sampled frame (trainer.py:217-248)."""
         o = self.opts

@@ -125,6 +125,20 @@ int cvc_beam_select_parts(const float* parts, int nparts, long long part_stride,
                           const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx,
                           int first_step, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
                           float* workspace, cvc_stream_t stream);
+/* Sampled decoding (csrc/sample.hip): Gumbel-max sampling from softmax(z / tau) without UNK, one workgroup per row.
+ *   z[r, :]  = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish (nparts = 1, bias = NULL:
+ *              a finished [M, V] logit matrix); slab p starts part_stride floats after slab p-1
+ *   h        = cvc_drop_hash(seed_lo, seed_hi, call, CVC_SAMPLE_SITE + t, r * V + v)      (csrc/dropout_rng.h)
+ *   u        = ((h >> 9) + 0.5) * 2^-23,  g = -logf(-logf(u)),  s = z[r, v] * inv_tau + g
+ *   word[r * word_stride] = argmax over v != unk_idx of s (ties -> lower index)
+ *   logprob[r] = z[r, word] - logsumexp_v z[r, v] (nullable; full V, independent of tau)
+ * rng_state: 4 words of device memory {seed_lo, seed_hi, call, 0}; cvc_sample_advance adds 1 to `call` on the stream.
+ * V <= 8192, M * V < 2^32; bitwise deterministic. */
+#define CVC_SAMPLE_SITE 0x53000000u
+int cvc_sample_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V, int unk_idx,
+                            float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
+                            cvc_stream_t stream);
+int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream);
 int cvc_tile_lstm_finish(const float* parts, int nparts, long long part_stride, const float* b_ih, const float* b_hh,
                          const float* gate_bias, int gb_div, const float* c_prev, int M, int R, float* c_out,
                          float* h_out, void* frag1, long long frag1_stride, void* frag2, long long frag2_stride,
