@@ -60,6 +60,13 @@ const Entry table[] = {
     CVC_B(cvc_stable_order),
     CVC_B(cvc_col_sum),
     CVC_B(cvc_col_sum_ws),
+    CVC_B(cvc_lstm_persistent_sync_words),
+    CVC_B(cvc_lstm_seq_persistent_fwd),
+    CVC_B(cvc_lstm_seq_persistent_train_fwd),
+    CVC_B(cvc_lstm_seq_fwd),
+    CVC_B(cvc_lstm_seq_train_fwd),
+    CVC_B(cvc_lstm_seq_bwd_work),
+    CVC_B(cvc_lstm_seq_bwd),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

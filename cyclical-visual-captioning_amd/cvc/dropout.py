@@ -60,9 +60,11 @@ def keep_mask(site: str, shape, p: float, device) -> torch.Tensor:
 IN_KERNEL = os.environ.get("CVC_DROPOUT_KERNEL", "1") != "0"        # False: masks as tensors from torch.bernoulli (A/B)
 _SITES = {"emb_a": 1, "emb_b": 2, "emb_c": 3, "vis_embed": 4,
           # the once-per-clip encoder's dropouts in train() (model/backbone.py:55-79, 103-106): Linear -> ReLU -> Dropout blocks, the class
-          # table's dropout inside the class similarity, the GRU's inter-layer dropout
+          # table's dropout inside the class similarity, the GRU's / LSTM's inter-layer dropout
           "enc.loc_fc": 16, "enc.fc_embed": 17, "enc.seg_info": 18, "enc.att0": 19, "enc.att1": 20, "enc.pool_embed": 21,
-          "enc.ctx2pool_grd": 22, "enc.vis_table": 23, "enc.gru.0": 24, "enc.gru.1": 25, "enc.gru.2": 26}
+          "enc.ctx2pool_grd": 22, "enc.vis_table": 23, "enc.gru.0": 24, "enc.gru.1": 25, "enc.gru.2": 26,
+          # nn.LSTM's inter-layer dropout of the `bilstm` frame encoder (cvc/lstm_seq.py)
+          "enc.lstm.0": 27, "enc.lstm.1": 28, "enc.lstm.2": 29}
 _states = {}
 _seed: Optional[int] = None
 

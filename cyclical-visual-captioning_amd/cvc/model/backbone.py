@@ -4,9 +4,10 @@ side of the hot path.  Mirrors the reference's `RegionalFeatureExtractorGVD`
 `state_dict` keys, same 10-tuple returned to the captioner (backbone.py:350-351).
 
 It runs once per clip (not once per decode step).  Its heavy pieces run on the build's own kernels: the 2-layer bidirectional
-frame-context GRU (cvc/gru.py: tile-GEMM input projections + persistent recurrence, inference and autograd) and the dense layers
-over the B*F frame rows / B*N region rows (cvc/dense.py on the tile GEMM); whatever falls outside their range (CPU tensors, an
-nn.LSTM frame encoder, odd widths, a HIP graph under capture) uses the library module and says so once (cvc.hip.warn_once).
+frame-context RNN -- `bigru` on cvc/gru.py, `bilstm` on cvc/lstm_seq.py: tile-GEMM input projections + persistent recurrence,
+inference and autograd -- and the dense layers over the B*F frame rows / B*N region rows (cvc/dense.py on the tile GEMM); whatever
+falls outside their range (CPU tensors, odd widths, a HIP graph under capture outside deferred mode) uses the library module and
+says so once (cvc.hip.warn_once).
 What differs from the reference's formulation:
 
   * the class-similarity logits are one `[DET+1, G] x [B, G, N]` product instead of a product
@@ -27,9 +28,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import dense, encoder_ops, hip, gru as gru_hip
+from .. import dense, encoder_ops, hip, gru as gru_hip, lstm_seq as lstm_hip
 
-HIP_GRU = True     # inference: frame-context GRU on the HIP kernels (cvc/gru.py); False = the library module everywhere
+HIP_GRU = True     # frame-context recurrence (nn.GRU: cvc/gru.py, nn.LSTM: cvc/lstm_seq.py) on the HIP kernels; False = the library module everywhere
+
+
+def _hip_rnn_module(enc) -> bool:
+    """module-level conditions of the HIP recurrences (cvc.gru.supported / cvc.lstm_seq.supported without the input tensor)"""
+    if not (isinstance(enc, (nn.GRU, nn.LSTM)) and enc.batch_first and enc.bias and enc.hidden_size % 8 == 0):
+        return False
+    return not isinstance(enc, nn.LSTM) or getattr(enc, "proj_size", 0) == 0
 
 GLOVE_DIM = 300          # backbone.py:43,46
 SEG_INFO_SIZE = 50       # backbone.py:29
@@ -214,22 +222,24 @@ class RegionalFeatureExtractorGVD(nn.Module):
                 per_caption(pnt_mask), per_caption(overlaps), sample_idx_mask, cls_pred, cls_loss)
 
     def reports_error_words(self) -> bool:
-        """the frame-context GRU's persistent forms (csrc/gru_persistent.hip, gru_bwd_persistent.hip) raise an error word on a
-        barrier time-out"""
-        return HIP_GRU and isinstance(self.context_enc, nn.GRU) and self.att_input_mode in ('both', 'featmap')
+        """the frame-context recurrence's persistent forms (csrc/gru_persistent.hip, gru_bwd_persistent.hip, lstm_seq.hip) raise an
+        error word on a barrier time-out"""
+        enc = self.context_enc
+        return (HIP_GRU and (isinstance(enc, nn.GRU) or (isinstance(enc, nn.LSTM) and _hip_rnn_module(enc)))
+                and self.att_input_mode in ('both', 'featmap'))
 
     def step_capturable(self, deferred_errors: bool = False) -> bool:
         """Can a training step through this encoder be captured into a HIP graph?  Everything here is stream work -- dense layers on
         the tile GEMM, the fused encoder kernels, the GRU's recurrences -- except: (i) the persistent recurrences' error words, read
-        by the host unless the caller runs in deferred mode; (ii) the library fallbacks (an nn.LSTM frame encoder or a GRU width
-        outside H % 8 == 0 runs in MIOpen, whose workspace handling is not ours to capture); (iii) collect_cls_pred's boolean
+        by the host unless the caller runs in deferred mode; (ii) the library fallbacks (a width outside H % 8 == 0 or an nn.LSTM with
+        projections runs in MIOpen, whose workspace handling is not ours to capture); (iii) collect_cls_pred's boolean
         gathers (host-sized outputs)."""
         if self.collect_cls_pred:
             return False
         if self.att_input_mode not in ('both', 'featmap'):
             return True                                        # no frame path, no recurrence
         enc = self.context_enc
-        if not (HIP_GRU and isinstance(enc, nn.GRU) and enc.batch_first and enc.bias and enc.hidden_size % 8 == 0):
+        if not (HIP_GRU and _hip_rnn_module(enc)):
             return False
         return bool(deferred_errors)
 
@@ -239,9 +249,13 @@ class RegionalFeatureExtractorGVD(nn.Module):
         enc = self.context_enc
         # (a capture may contain the HIP recurrence only in deferred mode: no host read of the persistent forms' error words)
         capturing = x.is_cuda and torch.cuda.is_current_stream_capturing() and not hip.errors_deferred()
-        if HIP_GRU and not torch.is_grad_enabled() and gru_hip.supported(enc, x):
-            return gru_hip.gru_forward(enc, x)                        # inference: persistent / per-step recurrence + tile GEMM
-        if HIP_GRU and torch.is_grad_enabled() and gru_hip.supported_train(enc, x) and not capturing:
+        mod = lstm_hip if isinstance(enc, nn.LSTM) else gru_hip     # same conditions, same switch for both recurrences
+        if HIP_GRU and not torch.is_grad_enabled() and mod.supported(enc, x):
+            # inference: persistent / per-step recurrence + tile GEMM
+            return lstm_hip.lstm_forward(enc, x) if mod is lstm_hip else gru_hip.gru_forward(enc, x)
+        if HIP_GRU and torch.is_grad_enabled() and mod.supported_train(enc, x) and not capturing:
+            if mod is lstm_hip:
+                return lstm_hip.lstm_forward_train(enc, x)            # autograd on the same kernels (cvc_lstm_seq_bwd)
             try:
                 return gru_hip.gru_forward_train(enc, x)              # autograd on the same kernels (cvc_gru_seq_bwd)
             except gru_hip.GruUnavailable as e:                       # barrier time-out / grid not co-resident: keep training
@@ -249,7 +263,7 @@ class RegionalFeatureExtractorGVD(nn.Module):
         elif x.is_cuda and HIP_GRU:
             why = ("a HIP graph is being captured (the persistent recurrence reports time-outs through a host read)" if capturing else
                    f"{type(enc).__name__} / hidden size {enc.hidden_size} is outside the HIP recurrence's range "
-                   "(nn.GRU, batch_first, bias, H % 8 == 0)")
+                   "(nn.GRU or nn.LSTM without projections, batch_first, bias, H % 8 == 0)")
             hip.warn_once("gru-library:" + why[:24], "frame-context RNN runs on the library module (MIOpen): " + why)
         enc.flatten_parameters()
         return enc(x)[0]

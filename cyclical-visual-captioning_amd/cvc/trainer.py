@@ -327,13 +327,14 @@ class Trainer:
         optimizer pass left the parameters alone.  They are taken again here, eagerly, on the per-step forms (which have no barrier)
         with host-checked error words.  Every rank of a multi-GPU run calls this with the same number of batches (the status word
         travels with the gradient exchange).  Returns the five loss values of each re-run step."""
-        from . import gru, hip
+        from . import gru, hip, lstm_seq
         hip.warn_once("trainer.void-steps", "a persistent recurrence kernel reported a barrier time-out inside a captured training step; "
                       "the step left the parameters untouched and is re-run on the per-step forms (reported once; counts in "
                       "Trainer.deferred_stats)")
         keep = (gru.PERSISTENT, gru.BWD_PERSISTENT, self._status)
+        keep_lstm = lstm_seq.PERSISTENT
         hip.defer_errors(None)
-        gru.PERSISTENT = gru.BWD_PERSISTENT = False
+        gru.PERSISTENT = gru.BWD_PERSISTENT = lstm_seq.PERSISTENT = False
         self._status = None
         out = []
         try:
@@ -342,6 +343,7 @@ class Trainer:
                 self.deferred_stats["rerun_steps"] += 1
         finally:
             gru.PERSISTENT, gru.BWD_PERSISTENT, self._status = keep
+            lstm_seq.PERSISTENT = keep_lstm
             if self._status is not None:
                 hip.defer_errors(self._status)
         return out

@@ -200,6 +200,49 @@ int cvc_stable_order(const int64_t* key, int n, int64_t* order, cvc_stream_t str
 long long cvc_col_sum_ws(int S, int n);
 int cvc_col_sum(const float* x, long long ld, int S, int n, float* out, float* out2, float* ws, cvc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * LSTM recurrence of the frame-context encoder in its `bilstm` mode (csrc/lstm_seq.hip; reference backbone.py:94-106, 335-338):
+ * the recurrent half of nn.LSTM(batch_first, bias) with h0 = c0 = 0, gate order (i, f, g, o), one or two directions (direction 1
+ * walks the sequence from the end).  Operands as the GRU entry points of cvc_hip.h have them:
+ *   wp     packed W_hh [ndir][H/8][Kp/4][32][4], Kp = H rounded up to 32 (cvc.lstm_seq.pack_lstm_weights: block b, row 8 g + u =
+ *          gate g of hidden unit 8 b + u -- no zero rows);
+ *   gi     the input projections W_ih x WITHOUT bias: row of (clip m, step t) at gi + m * gi_ld_m + t * gi_ld_t, columns [ndir][4][H];
+ *   b_ih, b_hh  [ndir][4H];   y  h_t at y + m * y_ld_m + t * y_ld_t, columns [ndir][H].
+ * Training forms additionally write, for every step and direction, what autograd needs:
+ *   gates  ACTIVATED (i, f, g, o) at gates + m * g_ld_m + t * g_ld_t + d * 4H + {0, H, 2H, 3H};
+ *   c      c_t at c + m * c_ld_m + t * c_ld_t + d * H.
+ * Every pointer 16-byte aligned, every stride a multiple of 4 floats, M <= 64; CVC_E_BADARG without launching otherwise.
+ *
+ * cvc_lstm_seq_persistent_fwd / _train_fwd: one launch for the whole sequence, W_hh in registers, c in the registers of the
+ *   workgroup that owns the unit (it never reaches memory in the inference form).  H % 128 == 0, H <= 1024, and a grid of
+ *   (H/8, ndir) workgroups that is co-resident; CVC_E_BADARG without launching otherwise.  hq = (F + 1) * ndir * H * 64 floats (one
+ *   state slot per step), sync = cvc_lstm_persistent_sync_words() words: arrival counters and, at word 4, an error word that is
+ *   non-zero afterwards when a bounded barrier wait timed out -- the outputs are then invalid: repeat with the per-step form.
+ * cvc_lstm_seq_fwd / _train_fwd: one launch per time step, any H % 8 == 0.  hq = 3 * ndir * Kp * 64 floats of workspace.
+ *   Interchangeable with the persistent form within rounding (the two sum k in different orders), not bit for bit.
+ * cvc_lstm_seq_bwd: walks the sequence backwards; per step and direction the gate gradients (dh = dY_t + dgates_{next} W_hh, dc
+ *   carried through f) and dgates_t W_hh (cvc_linear_nn_planes_fwd on w_hh [ndir][4H, H], the checkpoint layout).  Output
+ *   dg [F * M rows (t * M + m), ndir * 4H]: the pre-activation gradients -- b_ih and b_hh enter the same sum, so this one matrix
+ *   gives dW_ih, dX, dW_hh and both biases in dense products over all steps.  work = cvc_lstm_seq_bwd_work(M, H, ndir) floats. */
+int cvc_lstm_persistent_sync_words(void);
+int cvc_lstm_seq_persistent_fwd(const float* wp, const float* gi, long long gi_ld_m, long long gi_ld_t, const float* b_ih,
+                                const float* b_hh, int M, int F, int H, int ndir, float* hq, float* y, long long y_ld_m,
+                                long long y_ld_t, unsigned* sync, cvc_stream_t stream);
+int cvc_lstm_seq_persistent_train_fwd(const float* wp, const float* gi, long long gi_ld_m, long long gi_ld_t, const float* b_ih,
+                                      const float* b_hh, int M, int F, int H, int ndir, float* hq, float* y, long long y_ld_m,
+                                      long long y_ld_t, float* gates, long long g_ld_m, long long g_ld_t, float* c, long long c_ld_m,
+                                      long long c_ld_t, unsigned* sync, cvc_stream_t stream);
+int cvc_lstm_seq_fwd(const float* wp, const float* gi, long long gi_ld_m, long long gi_ld_t, const float* b_ih, const float* b_hh,
+                     int M, int F, int H, int ndir, float* hq, float* y, long long y_ld_m, long long y_ld_t, cvc_stream_t stream);
+int cvc_lstm_seq_train_fwd(const float* wp, const float* gi, long long gi_ld_m, long long gi_ld_t, const float* b_ih,
+                           const float* b_hh, int M, int F, int H, int ndir, float* hq, float* y, long long y_ld_m, long long y_ld_t,
+                           float* gates, long long g_ld_m, long long g_ld_t, float* c, long long c_ld_m, long long c_ld_t,
+                           cvc_stream_t stream);
+int cvc_lstm_seq_bwd_work(int M, int H, int ndir);
+int cvc_lstm_seq_bwd(const float* dy, long long dy_ld_m, long long dy_ld_t, const float* gates, long long g_ld_m, long long g_ld_t,
+                     const float* c, long long c_ld_m, long long c_ld_t, const float* w_hh, int M, int F, int H, int ndir, float* dg,
+                     float* work, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -679,6 +679,39 @@ def g10_vocab_plus_1(path):
     print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
+def g11_encoder_bilstm(path):
+    """g8_encoder_wide's shape (rnn_size 256 -> hidden size 128: the persistent recurrence's smallest width) with
+    t_attn_mode="bilstm" (reference backbone.py:94-106: nn.LSTM instead of nn.GRU), seq_per_img 1, eval mode: the eight encoder
+    outputs for both test_mode settings and, for the non-test case, the norm of every parameter gradient of encoder_probe_loss (as
+    g5 stores them).  Inputs and weights come from cvc.synth (same seed) on the test side."""
+    import dataclasses
+    import misc.utils as ref_utils
+    d = dataclasses.replace(synth.CONFIGS["tiny"], **WIDE)
+    seed = 1241
+    tables = synth.detectron_tables(d, seed)
+    inp = synth.encoder_inputs(d, seed)
+    out = OrderedDict()
+    out["meta.seed"] = np.asarray(seed)
+    bt = {k: t(v) for k, v in inp.items()}
+    overlaps = ref_utils.bbox_overlaps(bt["proposals"], bt["gt_bboxs"], (bt["frm_mask"] | bt["pnt_mask_in"][:, 1:].unsqueeze(-1)))
+    for name, over in (("train.", {}), ("test.", dict(test_mode=True))):
+        enc, ctor = build_reference_encoder(d, tables, seed, 1, t_attn_mode="bilstm", **over)
+        assert isinstance(enc.context_enc, nn.LSTM)
+        res = enc(bt["segs_feat"], bt["proposals"], bt["num"], bt["box_mask"], bt["region_feats"], bt["gt_bboxs"], overlaps,
+                  bt["sample_idx"])
+        put(out, name + "out.", dict(zip(ENC_OUT, res[:8])))
+        out[name + "out.cls_loss"] = res[9].detach().numpy()
+        if not over:
+            encoder_probe_loss(res).backward()
+            for n, p in enc.named_parameters():
+                if p.grad is None:
+                    out[name + "grad." + n + ".is_none"] = np.asarray(1)
+                else:
+                    out[name + "grad." + n + ".norm"] = np.asarray(p.grad.double().norm().item())
+    np.savez_compressed(path, **out)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
@@ -692,7 +725,8 @@ if __name__ == "__main__":
             "g7": lambda: g7_sentinel(os.path.join(gdir, "g7_sentinel.npz")),
             "g8": lambda: g8_encoder_wide(os.path.join(gdir, "g8_encoder_wide.npz")),
             "g9": lambda: g9_fullsize_ref(os.path.join(gdir, "g9_fullsize_ref.npz")),      # ~10 min, 30 GB: only when named
-            "g10": lambda: g10_vocab_plus_1(os.path.join(gdir, "g10_vocab_plus_1.npz"))}
+            "g10": lambda: g10_vocab_plus_1(os.path.join(gdir, "g10_vocab_plus_1.npz")),
+            "g11": lambda: g11_encoder_bilstm(os.path.join(gdir, "g11_encoder_bilstm.npz"))}
     if "--fullsize" in only:
         only = [x for x in only if x != "--fullsize"] + ["g9"]
     for name, job in jobs.items():
