@@ -70,7 +70,8 @@ def up_to_date() -> bool:
 # see through): their registers must never travel through scratch, where a value still in flight would be stored stale.  The
 # build FAILS if the compiler reports scratch or spills for one of them (hipcc -Rpass-analysis=kernel-resource-usage), so that a
 # compiler bump cannot regress this silently; the 128-row-vs-64-row bit-equality test in the default GPU suite is the other guard.
-NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",)}
+# (gemm_packed_bf16w.hip: no inline assembly, but a register ring of 214-230 VGPRs at 64 rows -- a spill there is a silent 2x)
+NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed_bf16w.hip": ("packed_bf16w_kernel",)}
 
 
 def check_no_scratch(src: str, remarks: str):

@@ -67,6 +67,8 @@ const Entry table[] = {
     CVC_B(cvc_lstm_seq_train_fwd),
     CVC_B(cvc_lstm_seq_bwd_work),
     CVC_B(cvc_lstm_seq_bwd),
+    CVC_B(cvc_packed_lstm_bf16w_fwd),
+    CVC_B(cvc_packed_linear_bf16w_fwd),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

@@ -39,7 +39,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def __init__(self, weights: DecodeWeights, feats: Dict[str, torch.Tensor], T: int, unk_idx: int, beam: int = 1,
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
-                 sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None):
+                 sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32"):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -58,9 +58,36 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         tau) without UNK (Gumbel-max, csrc/sample.hip), sample_n captions per clip (row b * sample_n + j is sample j of clip b),
         noise from the engine's own generator state {seed_lo, seed_hi, call, 0} (seed(); every decode first advances `call`).
         A sampling engine walks its launch list from Python (no C driver); beam > 1, gsk, gate_ksplit, lang_ksx and the packed
-        path without the embedding-gate schedule are refused."""
+        path without the embedding-gate schedule are refused.
+        weights_dtype: "fp32" (default) or "bf16" -- a precision setting, not a speed switch: the six weight matrices
+        (BF16_ROUNDED_KEYS) are rounded to bf16 (nearest even) when the engine binds the checkpoint and stored as bf16 packs
+        (csrc/gemm_packed_bf16w.hip: half the weight bytes per step, three MFMAs per product instead of six); the decode computes
+        what the fp32 engine computes on a checkpoint that holds the rounded values -- activations, state, accumulation, softmax
+        and word selection stay fp32.  Packed path with the embedding-gate schedule only (greedy or sampling with sample_n = 1,
+        <= 64 rows); the engine walks its launch list from Python (no C driver) and capture() turns it into a HIP graph.  Every
+        other configuration is refused with a RuntimeError -- the mode never runs in fp32 instead."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
+        if weights_dtype not in WEIGHTS_DTYPES:
+            raise RuntimeError(f"DecodeEngine: weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
+        self.weights_dtype = weights_dtype
+        self.bf16w = weights_dtype == "bf16"
+        if self.bf16w:
+            why = None
+            if self.beam != 1:
+                why = f"beam search (beam = {self.beam}) runs on the tile path"
+            elif int(sample_n) != 1:
+                why = f"sample_n = {sample_n} > 1 runs on the tile path"
+            elif path in ("tile", "ring"):
+                why = f'path="{path}" was asked for'
+            elif gsk or gate_ksplit or lang_ksx:
+                why = "gsk / gate_ksplit / lang_ksx are experimental schedules of the fp32 kernels"
+            elif embgate is not None and not embgate:
+                why = "embgate=False: the packed path without the embedding-gate schedule"
+            if why is not None:
+                raise RuntimeError(f'DecodeEngine: weights_dtype="bf16" covers the packed path with the embedding-gate schedule only '
+                                   f"(beam = 1, one caption per clip, <= 64 rows); refused: {why}")
+            gsk, gate_ksplit, lang_ksx = False, False, False
         self.sampling = temperature is not None
         if self.sampling:
             tau = float(temperature)
@@ -84,6 +111,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.B, self.N, self.F = pool.shape[0], pool.shape[1], conv.shape[1]
         B, N, Fr, R, A, V = self.B, self.N, self.F, W.R, W.A, W.V
         dev = pool.device
+        if self.bf16w and (B * self.nq > 64 or R % 32 or W.E % 32 or A % 32):          # (before anything is copied or allocated)
+            raise RuntimeError(f'DecodeEngine: weights_dtype="bf16" covers the packed path only: at most 64 rows and R, E, A '
+                               f"multiples of 32 (got {B * self.nq} rows, R = {R}, E = {W.E}, A = {A})")
         for name, t, shape in (("fc_feats", fc, (B, R)), ("conv_feats", conv, (B, Fr, R)), ("p_conv_feats", pconv, (B, Fr, A)),
                                ("pool_feats", pool, (B, N, R)), ("p_pool_feats", ppool, (B, N, A))):
             if tuple(t.shape) != shape:
@@ -153,9 +183,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                                "the sampled word from words[t])")
         # what stays in the Infinity Cache between steps: small linear weights, then (embedding-gate schedule on the packed path) the
         # attention cell's gate matrix over K = 2R if it fits, then the largest subset of the feature tensors
-        keep = cache_plan(4 * (V * R + A * R), {"ppool": nb(ppool), "pconv": nb(pconv), "pool": nb(pool), "conv": nb(conv)},
-                          gate_weight_bytes=4 * 4 * R * 2 * R if (self.packed and self.embgate and rows > 32) else None)
+        if self.bf16w and not (self.packed and self.embgate):
+            raise RuntimeError('DecodeEngine: weights_dtype="bf16" needs the embedding-gate schedule, and its table '
+                               f"({4 * V * 4 * R} bytes) is over EMBGATE_MAX_BYTES")
+        bpw = 2 if self.bf16w else 4                       # bytes per stored weight
+        keep = cache_plan(bpw * (V * R + A * R), {"ppool": nb(ppool), "pconv": nb(pconv), "pool": nb(pool), "conv": nb(conv)},
+                          gate_weight_bytes=bpw * 4 * R * 2 * R if (self.packed and self.embgate and (rows > 32 or self.bf16w)) else None,
+                          lang_weight_bytes=bpw * 4 * R * 3 * R if self.bf16w else None)
+        self.cache_keep = keep
         self.att_w_cached = bool(keep.get("att_w", False))
+        self.lang_w_cached = bool(keep.get("lang_w", False))
         # cvc_attn_set.stream: bit 0 = proj read non-temporally, bit 1 = ctx
         self.stream_r = (0 if keep["ppool"] else 1) | (0 if keep["pool"] else 2)
         self.stream_f = (0 if keep["pconv"] else 1) | (0 if keep["conv"] else 2)
@@ -169,7 +206,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                   hip.gemm_packed_split(-1) == 2 and int(hip.lib().cvc_packed_lstm_ks_slices(3 * R, R)) == 8)
         if lang_ksx and not ksx_ok:
             raise RuntimeError("DecodeEngine: lang_ksx needs the packed path at R = 2048, T > 1, split-product arithmetic")
-        self.lang_ksx = ksx_ok and (LANG_KSX_DEFAULT if lang_ksx is None else bool(lang_ksx))
+        self.lang_ksx = ksx_ok and not self.bf16w and (LANG_KSX_DEFAULT if lang_ksx is None else bool(lang_ksx))
         self._ksx_checked = False
         if self.lang_ksx:
             self.ksx_slab = torch.empty(8 * (R // 8) * 2048, device=dev, dtype=torch.float32)
@@ -179,7 +216,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         elif self.tile:
             self._alloc_tile()
         self._launches = self._build_launches()
-        if driver and not self.sampling and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
+        if driver and not self.sampling and not self.bf16w and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
 
     # ------------------------------------------------------------------ C-ABI decode driver (csrc/decode_driver.hip)
@@ -372,7 +409,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode

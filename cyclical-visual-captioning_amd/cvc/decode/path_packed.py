@@ -24,13 +24,15 @@ class PackedPath:
         dev = self.fc.device
         # derived copies are built per schedule, on its first use with this checkpoint binding (the default embedding-gate schedule
         # never builds the full-K attention-cell pack: 168 MB at cfg2)
+        if self.bf16w:
+            bind_bf16(W)                 # bf16 packs + the rounded fp32 views; no fp32 pack is built for this mode
         if not self.embgate and not hasattr(W, "p_att"):
             W.p_att = pack_weights(torch.cat([W.w_ih_att[:, 0:R], W.w_ih_att[:, 2 * R:2 * R + E], W.w_hh_att], 1), R)
-        if not hasattr(W, "p_lang"):
+        if not self.bf16w and not hasattr(W, "p_lang"):
             W.p_lang = pack_weights(torch.cat([W.w_ih_lang, W.w_hh_lang], 1), R)
             W.p_h = pack_weights(W.w_h)
             W.p_o = pack_weights(W.w_o)
-        if self.embgate and not hasattr(W, "p_att2"):
+        if self.embgate and not self.bf16w and not hasattr(W, "p_att2"):
             W.p_att2 = pack_weights(torch.cat([W.w_ih_att[:, 0:R], W.w_hh_att], 1), R)        # K = 2R: [h_lang | h_att]
             W.t_embgate = embgate_table(W)
         zq = lambda k: torch.zeros(k // 4, 64, 4, device=dev, dtype=torch.float32)
@@ -73,13 +75,15 @@ class PackedPath:
         ptr = lambda t: None if t is None else t.data_ptr()
         qoff = lambda buf, k0: buf.data_ptr() + (k0 // 4) * 64 * 4 * 4        # byte address of quad k0/4
         out = []
-        seg_fc = _segs([(fc, None, W.w_ih_att[:, R:2 * R], False)])
+        seg_fc = _segs([(fc, None, W.r_w_fc if self.bf16w else W.w_ih_att[:, R:2 * R], False)])
         out.append(("gate_fc", L.cvc_linear_fwd, (seg_fc, 1, ptr(W.b_ih_att), ptr(W.b_hh_att), rows, 4 * R, ptr(self.gate_fc),
                                                   4 * R)))
         self._keep.append(seg_fc)
         nblk_v = (V + 31) // 32
         if self.gsk:
             return out + self._build_gsk_steps()
+        if self.bf16w:
+            return out + self._build_bf16w_steps()
         if self.embgate:
             return out + self._build_embgate_steps()
         for t in range(self.T):
@@ -183,6 +187,55 @@ class PackedPath:
             else:
                 out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
                                                                 ptr(self.top2_part))))
+                out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
+                                                              ptr(self.logprob[t]), None, 0, None, 0)))
+            self._keep.append(sets)
+        return out
+
+    def _build_bf16w_steps(self):
+        """The T steps of the embedding-gate schedule with bf16-stored weights (weights_dtype="bf16"): the launch list of
+        _build_embgate_steps, same names, with the four GEMMs on csrc/gemm_packed_bf16w.hip; attention passes and word selection
+        are the fp32 engine's own launches."""
+        L, W = hip.lib(), self.W
+        B, N, Fr, R, A, V, rows = self.B, self.N, self.F, W.R, W.A, W.V, self.rows
+        fc, conv, pconv, pool, ppool = self.feats
+        ptr = lambda t: None if t is None else t.data_ptr()
+        qoff = lambda buf, k0: buf.data_ptr() + (k0 // 4) * 64 * 4 * 4
+        out = []
+        nblk_v = (V + 31) // 32
+        for t in range(self.T):
+            rd, wr = t & 1, (t + 1) & 1
+            XA_r, XA_w, XL_r, XL_w = self.XA[rd], self.XA[wr], self.XL[rd], self.XL[wr]
+            # step 0 multiplies the all-zero initial state (an exact zero times a finite weight adds nothing): one chunk of the
+            # attention cell's K, the language cell without its h_lang columns
+            first = t == 0
+            out.append(("att_lstm", L.cvc_packed_lstm_bf16w_fwd, (ptr(W.pb_att2), 2 * R * 32, ptr(XA_r), 32 if first else 2 * R, None, None,
+                                                                  ptr(self.gate_fc), ptr(W.r_embgate), ptr(self.words[t]), ptr(self.cA[rd]),
+                                                                  rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
+                                                                  1 if self.att_w_cached else 0)))
+            out.append(("h2attn", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT,
+                                                                  ptr(self.q_parts), A, None)))
+            sets = (hip.AttnSet * 2)()
+            sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
+                                  ptr(self.att_steps[t]), None, N, self.stream_r)
+            sets[1] = hip.AttnSet(ptr(pconv), ptr(conv), None, None, ptr(self.scores_f), None, ptr(self.attn_f), None, Fr,
+                                  self.stream_f)
+            out.append(("attn_scores", L.cvc_attn_scores_qparts, (W.kind, ptr(self.q_parts), self.QSPLIT, ptr(W.b_h), ptr(W.w_a),
+                                                                  ptr(W.b_a), self.inv_temp, sets, 2, B, 1, A)))
+            out.append(("attn_wsum", L.cvc_attn_wsum_quad, (sets, 2, B, 1, R, ptr(XL_r))))
+            out.append(("lang_lstm", L.cvc_packed_lstm_bf16w_fwd, (ptr(W.pb_lang), 3 * R * 32, ptr(XL_r), 2 * R if first else 3 * R,
+                                                                   ptr(W.b_ih_lang), ptr(W.b_hh_lang), None, None, None, ptr(self.cL[rd]),
+                                                                   rows, R, ptr(XA_w), qoff(XL_w, 2 * R), ptr(self.cL[wr]),
+                                                                   1 if self.lang_w_cached else 0)))
+            if self.sampling:
+                out.append(("logits", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits),
+                                                                      V, None)))
+                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
+                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
+                                                                       ptr(self.logprob[t]))))
+            else:
+                out.append(("logits", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
+                                                                      ptr(self.top2_part))))
                 out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
                                                               ptr(self.logprob[t]), None, 0, None, 0)))
             self._keep.append(sets)

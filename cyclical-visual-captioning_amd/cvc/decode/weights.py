@@ -93,7 +93,71 @@ def lstm_packed_rows(R: int, device) -> torch.Tensor:
     return (((i >> 3) * R + (i & 7)).view(1, 32) + (torch.arange(R // 8, device=device) * 8).view(-1, 1)).reshape(-1)
 
 
-EMBGATE_MAX_BYTES = 1 << 30      # largest embedding-gate table the engine builds on its own (cfg2: 164 MB, cfg5: 328 MB)
+# ------------------------------------------------------------------ bf16-stored weights (csrc/gemm_packed_bf16w.hip)
+WEIGHTS_DTYPES = ("fp32", "bf16")
+# the six matrices DecodeEngine(weights_dtype="bf16") rounds when it binds a checkpoint (state_dict names)
+BF16_ROUNDED_KEYS = ("decoder_core.att_lstm.weight_ih", "decoder_core.att_lstm.weight_hh", "decoder_core.lang_lstm.weight_ih",
+                     "decoder_core.lang_lstm.weight_hh", "decoder_core.soft_attn.h2attn.weight", "logit.weight")
+
+
+def bf16_round(t: torch.Tensor) -> torch.Tensor:
+    """fp32 -> the nearest bf16 value, ties to even, returned as fp32 (what tensor.bfloat16().float() gives; integer arithmetic
+    on the bit pattern: add 0x7fff + the kept mantissa's last bit, drop the low 16 bits).  NaN stays NaN; a finite value beyond
+    the largest bf16 rounds to infinity."""
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"bf16_round: fp32 in, fp32 out (got {t.dtype})")
+    u = t.contiguous().view(torch.int32)
+    r = ((u + (((u >> 16) & 1) + 0x7FFF)) & -65536).view(torch.float32)
+    return torch.where(torch.isnan(t), t, r)
+
+
+def pack_weights_bf16(w: torch.Tensor, lstm_R: Optional[int] = None) -> torch.Tensor:
+    """[Nout, K] row-major fp32 -> [ceil(Nout/32)][K/8][32 rows][8 k] torch.bfloat16 of bf16_round(w): the layout
+    cvc_packed_lstm_bf16w_fwd / cvc_packed_linear_bf16w_fwd read (a lane's 16 bytes are its MFMA operand of one K = 16 step).
+    Row order of `pack_weights`: for an LSTM gate matrix (Nout = 4R) block b holds the 4 gates of hidden units 8b..8b+7;
+    otherwise rows beyond Nout are zero."""
+    n, k = w.shape
+    assert k % 32 == 0, k
+    if lstm_R is not None:
+        assert n == 4 * lstm_R and lstm_R % 8 == 0
+        w = w[lstm_packed_rows(lstm_R, w.device)]
+        nb = lstm_R // 8
+    else:
+        nb = (n + 31) // 32
+        if nb * 32 != n:
+            w = torch.cat([w, w.new_zeros(nb * 32 - n, k)], 0)
+    return bf16_round(w).to(torch.bfloat16).view(nb, 32, k // 8, 8).permute(0, 2, 1, 3).contiguous()
+
+
+def unpack_weights_bf16(p: torch.Tensor, n: Optional[int] = None, lstm_R: Optional[int] = None) -> torch.Tensor:
+    """inverse of pack_weights_bf16: the rounded matrix as fp32 [n, K] (n = all packed rows when None; checkpoint row order
+    when lstm_R is given)."""
+    nb, k8 = p.shape[0], p.shape[1]
+    w = p.permute(0, 2, 1, 3).reshape(nb * 32, k8 * 8).float()
+    if lstm_R is not None:
+        out = torch.empty_like(w)
+        out[lstm_packed_rows(lstm_R, w.device)] = w
+        w = out
+    return w if n is None else w[:n]
+
+
+def bind_bf16(W: "DecodeWeights") -> "DecodeWeights":
+    """The derived copies of the bf16 mode, built on its first use with this checkpoint binding and cached on W like the fp32
+    packs: the four bf16 packs, and -- everything that is derived from a rounded matrix is derived from the ROUNDED values -- the
+    rounded fc columns of the attention cell (gate_fc) and the embedding-gate table, both fp32.  Builds no fp32 pack."""
+    if hasattr(W, "pb_lang"):
+        return W
+    R, E = W.R, W.E
+    W.pb_att2 = pack_weights_bf16(torch.cat([W.w_ih_att[:, 0:R], W.w_hh_att], 1), R)          # K = 2R: [h_lang | h_att]
+    W.pb_h = pack_weights_bf16(W.w_h)
+    W.pb_o = pack_weights_bf16(W.w_o)
+    W.r_w_fc = bf16_round(W.w_ih_att[:, R:2 * R])                                            # [4R, R]
+    W.r_embgate = hip.tile_mm(torch.relu(W.embed), bf16_round(W.w_ih_att[:, 2 * R:2 * R + E]))   # [V, 4R]
+    W.pb_lang = pack_weights_bf16(torch.cat([W.w_ih_lang, W.w_hh_lang], 1), R)
+    return W
+
+
+EMBGATE_MAX_BYTES = 1 << 30     # largest embedding-gate table the engine builds on its own (cfg2: 164 MB, cfg5: 328 MB)
 
 
 def embgate_table(W: "DecodeWeights") -> torch.Tensor:
@@ -175,11 +239,13 @@ CACHE_BUDGET = int(os.environ.get("CVC_CACHE_BUDGET_MB", "208")) << 20
 # steps/s without it, 326.1 / 323.5 k with it on one box: the 16.8 MB of partial tiles pass through the L2 / Infinity Cache that
 # holds the attention cell's weights, whose launch slows down by 1.5 us).  CVC_LANG_KSX=1 or lang_ksx=True switches it on.
 LANG_KSX_DEFAULT = os.environ.get("CVC_LANG_KSX", "0") == "1"
+# is the language cell's gate matrix a candidate of the cache plan where the caller offers it (bf16 mode: 101 MB at cfg2)?  (A/B: CVC_LANG_W_CACHED=0)
+CACHE_LANG_GATE_WEIGHTS = os.environ.get("CVC_LANG_W_CACHED", "1") != "0"
 CACHE_GATE_WEIGHTS = os.environ.get("CVC_ATT_W_CACHED", "1") != "0"       # False: gate weights always stream (A/B)
 
 
 def cache_plan(linear_weight_bytes: int, feature_bytes: Dict[str, int], budget: int = CACHE_BUDGET,
-               gate_weight_bytes: Optional[int] = None) -> Dict[str, bool]:
+               gate_weight_bytes: Optional[int] = None, lang_weight_bytes: Optional[int] = None) -> Dict[str, bool]:
     """Which per-step streams stay cacheable (True) and which are read non-temporally (False).
 
     A decode step re-reads the same ~0.85 GB; the Infinity Cache holds 256 MiB of it.  The small linear weights (vocabulary
@@ -187,7 +253,9 @@ def cache_plan(linear_weight_bytes: int, feature_bytes: Dict[str, int], budget: 
     (key "att_w" of the result) -- it goes first when it fits next to them: the gate GEMM is bound by the latency of its
     weight loads, not by bandwidth, so a cached byte buys more there than in the attention passes, which stream at the
     memory's rate either way (measured at cfg2: its launch 40.3 -> 35.4 us; decode 322 -> 328 k steps/s).  The language
-    cell's matrix (201 MB at cfg2) never fits and always streams.  Of the four feature tensors the subset with the most
+    cell's matrix (201 MB at cfg2 in fp32) never fits there and always streams; callers whose weights are narrower (bf16: 101 MB)
+    pass it as lang_weight_bytes (key "lang_w"): it is a candidate after the attention cell's, and only when that one stays (the
+    byte counts are the caller's: elements x bytes per stored weight).  Of the four feature tensors the subset with the most
     bytes that still fits the remaining room stays cacheable, the rest is marked `stream` in its cvc_attn_set.
     Measured at cfg2: nothing streamed 283 k steps/s, features only 302-304 k (round 2) / 322 k (round 3 kernels)."""
     names = list(feature_bytes)
@@ -197,6 +265,10 @@ def cache_plan(linear_weight_bytes: int, feature_bytes: Dict[str, int], budget: 
         plan["att_w"] = bool(CACHE_GATE_WEIGHTS and 0 < gate_weight_bytes <= room)
         if plan["att_w"]:
             room -= gate_weight_bytes
+    if lang_weight_bytes is not None:
+        plan["lang_w"] = bool(CACHE_GATE_WEIGHTS and CACHE_LANG_GATE_WEIGHTS and plan.get("att_w", False) and 0 < lang_weight_bytes <= room)
+        if plan["lang_w"]:
+            room -= lang_weight_bytes
     best, best_bytes = (), 0
     for pick in range(1 << len(names)):
         chosen = [n for i, n in enumerate(names) if pick >> i & 1]

@@ -234,6 +234,9 @@ SIGNATURES = {
     "cvc_beam_select_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "cvc_sample_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P],
     "cvc_sample_advance": [_P, _P],
+    # packed GEMMs with bf16-stored weights (csrc/gemm_packed_bf16w.hip; building blocks)
+    "cvc_packed_lstm_bf16w_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P],
+    "cvc_packed_linear_bf16w_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -275,7 +278,8 @@ BLOCKS = {
     "cvc_tile_lstm_finish_embgate", "cvc_tile_reorder_pack", "cvc_decode_num_launches", "cvc_gemm_force_generic",
     "cvc_tile_gemm_loaders", "cvc_gru_persistent_waves8", "cvc_relu_dropout_fwd", "cvc_relu_dropout_bwd", "cvc_bn_workspace",
     "cvc_bn_relu_train_fwd", "cvc_bn_relu_train_bwd", "cvc_class_softmax_bwd", "cvc_layernorm_cat_bwd", "cvc_stable_order", "cvc_col_sum", "cvc_col_sum_ws", "cvc_attn_weighted_rows",
-    "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd"}
+    "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
+    "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",

@@ -35,6 +35,9 @@ def main(argv=None, sample=None):
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample)."""
     parser = cvc_opts.build_parser()
     parser.add_argument("--synthetic_clips", type=int, default=128)
+    parser.add_argument("--decode_weights", choices=("fp32", "bf16"), default="fp32",
+                        help="precision of the caption decode's weight matrices: bf16 stores the six GEMM matrices rounded to bf16 "
+                             "(greedy / one sample per clip, <= 64 rows; other decodes are refused, never run in fp32 instead)")
     parser.add_argument("--no_cfg", action="store_true", help="skip the YAML overlay (pure CLI)")
     parser.add_argument("--synthetic_raw", action="store_true",
                         help="feed raw frame / region features through the once-per-clip encoder (model/backbone.py) "

@@ -243,6 +243,22 @@ int cvc_lstm_seq_bwd(const float* dy, long long dy_ld_m, long long dy_ld_t, cons
                      const float* c, long long c_ld_m, long long c_ld_t, const float* w_hh, int M, int F, int H, int ndir, float* dg,
                      float* work, cvc_stream_t stream);
 
+/* ---- packed GEMMs with bf16-STORED weights (csrc/gemm_packed_bf16w.hip; DecodeEngine(weights_dtype="bf16")).
+ * wp: [ceil(Nout/32)][K/8][32 rows][8 k] bf16 (cvc.decode.pack_weights_bf16; row order of the fp32 pack), 16-byte aligned.
+ * Activations, biases, state, accumulation and outputs are fp32 as in cvc_packed_lstm_embgate_ex_fwd / cvc_packed_linear_fwd;
+ * every product is w * (x.hi + x.mid + x.lo), all three terms.  Bitwise equal (up to the sign of zero) to the fp32 entry points
+ * in split mode 2 on a pack of the same, bf16-exact weights.
+ *   lstm: emb_gate / word both set or both null; w_blk_stride = bf16 elements between 32-row blocks (0: dense, K * 32), K may
+ *         stop short of the pack; w_cached: the weights keep the default cache policy instead of streaming non-temporally.
+ *   linear: ksplit K slices into y + s * M * ldy (bias in slice 0), or row-major y, and / or top2_part records (ksplit == 1).
+ * K % 32 == 0, 1 <= M <= 64, R % 8 == 0: else CVC_E_BADARG, before any launch. */
+int cvc_packed_lstm_bf16w_fwd(const uint16_t* wp, long long w_blk_stride, const float* xq, int K, const float* b_ih,
+                              const float* b_hh, const float* gate_bias, const float* emb_gate, const int64_t* word,
+                              const float* c_prev_q, int M, int R, float* h_dst1_q, float* h_dst2_q, float* c_out_q,
+                              int w_cached, cvc_stream_t stream);
+int cvc_packed_linear_bf16w_fwd(const uint16_t* wp, const float* xq, int K, const float* bias, int M, int Nout, int ksplit,
+                                float* y, int ldy, float* top2_part, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
