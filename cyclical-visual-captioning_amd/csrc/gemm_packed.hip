@@ -17,14 +17,28 @@
 // Layouts ("quad" = 4 consecutive k):
 //   weights  Wp[blk][quad][32][4]   blk = 32 output rows (LSTM: the 4 gates x 8 hidden units of
 //            workgroup blk, i.e. row (i>>3)*R + blk*8 + (i&7)), packed once when the engine binds
-//            the checkpoint (cvc/decode.py::pack_weights); the concat over K segments is baked in.
+//            the checkpoint (cvc.decode.pack_weights); the concat over K segments is baked in.
 //   activations XQ[quad][64][4]     written in this form by the producers (this kernel's own
 //            epilogue, attn_wsum, top2_final), 64 = padded batch rows.
 // Lane l (i = l & 31, kh = l >> 5) of a wave handling chunk c (32 k = 8 quads) loads quads
 // 8c + 4kh + {0..3}: each half-wave reads 512 contiguous bytes per instruction.
+//
+// bf16-STORED weights (template mode WB16; DecodeEngine(weights_dtype="bf16"), building blocks cvc_packed_lstm_bf16w_fwd /
+// cvc_packed_linear_bf16w_fwd of include/cvc_hip_blocks.h): the weight operand is ONE bf16 term, rounded once when the engine
+// binds the checkpoint; the activations stay fp32 in the quad layout above and keep the exact three-way split of gemm_split.h.
+// A product w~ * x is w~ * x.lo + w~ * x.mid + w~ * x.hi -- all three cross terms, so it is fp32-grade -- on three
+// v_mfma_f32_32x32x16_bf16 instead of the fp32 path's six, with no VALU work on the weights and half their bytes.
+//   weights  Wb[blk][K/8][32 rows][8 k]  (bf16, cvc.decode.pack_weights_bf16), blk and its row order as in the fp32 pack.
+// Lane (i, kh) of the wave that handles chunk c loads k-octets 4c + 2kh + {0, 1} of row i: 16 bytes each, its A operand of one
+// K = 16 MFMA step as stored, 512 contiguous bytes per half-wave and instruction.  Octet 4c + 2kh + s holds the k of activation
+// quads 8c + 4kh + 2s and + 2s + 1: W and X sit on the same k-slot map as in split8.
+// The mode shares every line of the 8-wave split-product form outside the K loop's load and multiply, and issues its three MFMAs
+// in the order lo, mid, hi -- the order in which that form issues the three products a bf16-exact weight leaves non-zero (its
+// split is (w~, 0, 0)).  The result is therefore bitwise the fp32 kernel's on a pack of the rounded weights, up to the sign of
+// zero (tests/test_gpu_decode_bf16.py).
 // ==========================================================================================
 struct PackedArgs {
-    const float* wp;          // packed weights of this GEMM
+    const float* wp;          // packed weights of this GEMM (WB16: bf16 elements behind the pointer)
     const float* xq;          // packed activations, first quad of this GEMM's K range
     int nquad;                // K / 4 (multiple of 8)
     int M, Nout, R;
@@ -65,7 +79,7 @@ struct PackedArgs {
     int64_t* sel_word; int sel_word_stride; float* sel_logprob; int sel_unk;
     int w_cached;             // lstm decode form: 1 = the gate weights keep the default cache policy (Infinity-Cache resident by plan)
     DropSpec h3_drop;         // training form: h_rm3 receives nn.Dropout(h') with the counter-based mask of element m * R + j
-    long long wstride;        // floats between consecutive 32-row blocks of wp (0: dense, nquad * 128)
+    long long wstride;        // elements (floats; WB16: bf16) between consecutive 32-row blocks of wp (0: dense, nquad * 128)
     GskSegs early;            // SLAB form (cvc_packed_lstm_late_fwd): partial tiles of the K range a stream-K launch already covered
 };
 
@@ -92,6 +106,11 @@ struct PFrag {
 #if defined(CVC_PABL) && CVC_PABL == 6
     f32x4 x2[MT][2];     // ablation: the extra 50 % of activation bytes a pre-split (3 x bf16) operand would bring in
 #endif
+};
+template <int MT>
+struct BFrag {
+    u32x4 w[2];               // 2 x 8 bf16: the lane's A operands of the chunk's two K = 16 steps
+    f32x4 x[MT][4];
 };
 
 // NW waves split K (chunk c goes to wave c % NW).  NW = 8 puts two waves on every SIMD, each with a shallower
@@ -130,8 +149,12 @@ __device__ __forceinline__ SelState sel_merge(SelState s, float u1, int k1, floa
 // earlier by the grouped stream-K kernel (gemm_gsk.hip), are summed in segment order and join the cross-wave reduction as a
 // ninth partial.
 // WC: the LSTM gate weights keep the default cache policy instead of streaming non-temporally (experiment: cvc_packed_lstm_cached_weights)
-template <int MT, bool LSTM, int DEPTH, bool SPLIT, int NW, bool GRU = false, int NB = 1, bool SLAB = false, bool WC = false>
+// WB16: bf16-stored weights (see the head of the file); differs in the K loop's fragment, load, multiply and issue pattern only
+template <int MT, bool LSTM, int DEPTH, bool SPLIT, int NW, bool GRU = false, int NB = 1, bool SLAB = false, bool WC = false, bool WB16 = false>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs a) {
+    static_assert(!WB16 || (SPLIT && NW == 8 && !GRU && NB == 1 && !SLAB), "bf16-stored weights: 8-wave split-product form only");
+    using Frag = std::conditional_t<WB16, BFrag<MT>, PFrag<MT>>;
+    using WT = std::conditional_t<WB16, uint16_t, float>;      // element type of the weight pack
     static_assert(!GRU || LSTM, "the GRU step shares the LSTM form's work split");
     static_assert(!SLAB || (LSTM && !GRU && NB == 1 && NW == 8), "slab sum: LSTM decode form, 8 waves, one block per workgroup");
     static_assert(NB == 1 || (LSTM && !GRU && NW == 8 && NB == 2), "two blocks per workgroup: LSTM form, 8 waves");
@@ -163,16 +186,18 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
     }
     const int wblk = NB == 1 ? 0 : wave / NWK, kw = NB == 1 ? wave : wave % NWK;       // this wave's block and K slot
     const int n_my = nchunk > kw ? (nchunk - kw + NWK - 1) / NWK : 0;     // chunks c0 + kw + NWK*j
-    // per-lane bases: quad q of this block lives at wp + ((blk * nquad + q) * 32 + i) * 4
-    const float* wl = a.wp + (size_t)((int)blockIdx.x * NB + wblk) * a.wstride + (size_t)i * 4 + (size_t)(c0 + kw) * 8 * 128 + kh * 4 * 128;
+    // per-lane bases: quad q of this block lives at wp + ((blk * nquad + q) * 32 + i) * 4; WB16: k-octet o at wp + blk * wstride +
+    // (o * 32 + i) * 8 -- a chunk and a lane half's share of it are 1024 and 512 elements in both packs
+    const WT* wl = reinterpret_cast<const WT*>(a.wp) + (size_t)((int)blockIdx.x * NB + wblk) * a.wstride + (size_t)i * (WB16 ? 8 : 4) +
+                   (size_t)(c0 + kw) * 8 * 128 + kh * 4 * 128;
     const float* xl = a.xq + (size_t)i * 4 + (size_t)(c0 + kw) * 8 * 256 + kh * 4 * 256;
-    constexpr size_t WSTEP = (size_t)NWK * 8 * 128, XSTEP = (size_t)NWK * 8 * 256;   // floats per wave-chunk step
+    constexpr size_t WSTEP = (size_t)NWK * 8 * 128, XSTEP = (size_t)NWK * 8 * 256;   // elements per wave-chunk step
 #ifndef CVC_ROT_MUL
 #define CVC_ROT_MUL 5
 #endif
     const int rot = n_my > 0 ? (int)((blockIdx.x * CVC_ROT_MUL) % (unsigned)n_my) : 0;
 
-    auto load = [&](PFrag<MT>& f, int j) __attribute__((always_inline)) {
+    auto load = [&](Frag& f, int j) __attribute__((always_inline)) {
 #if defined(CVC_PABL) && CVC_PABL == 1
         if (j > 0) { asm volatile("" : "+v"(f.w[0])); return; }     // ablation: only the first chunk is ever loaded (MFMA side only)
 #endif
@@ -181,35 +206,48 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
         // with the block index, the result of a given block is still deterministic)
         int jr = j + rot;
         jr = jr >= n_my ? jr - n_my : jr;
-        const float* w = wl + (size_t)jr * WSTEP;
+        const WT* w = wl + (size_t)jr * WSTEP;
 #if defined(CVC_PABL) && CVC_PABL == 4
         const float* x = a.xq + (size_t)i * 4 + kh * 4 * 256;     // ablation: every wave re-reads ONE activation chunk (L1 hits)
 #else
         const float* x = xl + (size_t)jr * XSTEP;
 #endif
+        if constexpr (WB16) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            // gate weights (369 MB per step) are streamed; the small linear layers' weights (vocabulary head, h2attn:
-            // 49 MB) keep the default policy so that they can stay in the Infinity Cache between steps
-            if constexpr (((LSTM && !GRU) || CVC_LIN_W_NT) && !WC) f.w[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(w + q * 128));
-            else f.w[q] = ld4(w + q * 128);
+            for (int s2 = 0; s2 < 2; ++s2) {
+                // (streamed for the gate matrices as below; CVC_LIN_W_NT does not apply to this mode)
+                if constexpr (LSTM && !WC) f.w[s2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(w + s2 * 256));
+                else f.w[s2] = *reinterpret_cast<const u32x4*>(w + s2 * 256);
+#pragma unroll
+                for (int q = 2 * s2; q < 2 * s2 + 2; ++q)
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) f.x[mt][q] = ld4(x + q * 256 + mt * 128);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                // gate weights (369 MB per step) are streamed; the small linear layers' weights (vocabulary head, h2attn:
+                // 49 MB) keep the default policy so that they can stay in the Infinity Cache between steps
+                if constexpr (((LSTM && !GRU) || CVC_LIN_W_NT) && !WC) f.w[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(w + q * 128));
+                else f.w[q] = ld4(w + q * 128);
 #if defined(CVC_PABL) && CVC_PABL == 3
-            if (j > 0) continue;                                     // ablation: stream the weights only
+                if (j > 0) continue;                                     // ablation: stream the weights only
 #endif
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) f.x[mt][q] = ld4(x + q * 256 + mt * 128);
-        }
+                for (int mt = 0; mt < MT; ++mt) f.x[mt][q] = ld4(x + q * 256 + mt * 128);
+            }
 #if defined(CVC_PABL) && CVC_PABL == 6
-        {
-            int ja = jr + (n_my >> 1);
-            ja = ja >= n_my ? ja - n_my : ja;
-            const float* xa = xl + (size_t)ja * XSTEP;                // lines this workgroup touched half a loop ago: L2 hits
+            {
+                int ja = jr + (n_my >> 1);
+                ja = ja >= n_my ? ja - n_my : ja;
+                const float* xa = xl + (size_t)ja * XSTEP;                // lines this workgroup touched half a loop ago: L2 hits
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
+                for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) f.x2[mt][s2] = ld4(xa + (s2 + 2) * 256 + mt * 128 + 64);
-        }
+                    for (int mt = 0; mt < MT; ++mt) f.x2[mt][s2] = ld4(xa + (s2 + 2) * 256 + mt * 128 + 64);
+            }
 #endif
+        }
     };
 
     // embedding-gate form: the table row of this thread's epilogue work item (batch row tid & 63, hidden quad (tid >> 6) & 1) is
@@ -235,51 +273,64 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
 
-    auto mma = [&](const PFrag<MT>& f) __attribute__((always_inline)) {
-#if defined(CVC_PABL) && CVC_PABL >= 2 && CVC_PABL <= 4
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                               // ablation: memory side only, keep the loads live
-            asm volatile("" ::"v"(f.w[q]));
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) asm volatile("" ::"v"(f.x[mt][q]));
-        }
-        return;
-#endif
-        if constexpr (SPLIT) {
-            // the lane half's 4 quads = 16 k-slots = two K=16 steps (quads 2s, 2s+1); W and X use the same slot map
+    auto mma = [&](const Frag& f) __attribute__((always_inline)) {
+        if constexpr (WB16) {
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const Split3 W = split8(f.w[2 * s2], f.w[2 * s2 + 1]);
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-#if defined(CVC_PABL) && (CVC_PABL == 5 || CVC_PABL == 6)
-                    // ablation: activations arrive pre-split (no VALU work on them; 5: same bytes, 6: 1.5 x the bytes) -- timing only
-                    Split3 X;
-                    X.hi = __builtin_bit_cast(u32x4, f.x[mt][2 * s2]); X.mid = __builtin_bit_cast(u32x4, f.x[mt][2 * s2 + 1]);
-#if CVC_PABL == 6
-                    X.lo = __builtin_bit_cast(u32x4, f.x2[mt][s2]);
-#else
-                    X.lo = X.hi;
-#endif
-#else
                     const Split3 X = split8(f.x[mt][2 * s2], f.x[mt][2 * s2 + 1]);
-#endif
-                    acc[mt] = mfma_bf16(W.mid, X.mid, acc[mt]);
-                    acc[mt] = mfma_bf16(W.lo, X.hi, acc[mt]);
-                    acc[mt] = mfma_bf16(W.hi, X.lo, acc[mt]);
-                    acc[mt] = mfma_bf16(W.mid, X.hi, acc[mt]);
-                    acc[mt] = mfma_bf16(W.hi, X.mid, acc[mt]);
-                    acc[mt] = mfma_bf16(W.hi, X.hi, acc[mt]);
+                    acc[mt] = mfma_bf16(f.w[s2], X.lo, acc[mt]);
+                    acc[mt] = mfma_bf16(f.w[s2], X.mid, acc[mt]);
+                    acc[mt] = mfma_bf16(f.w[s2], X.hi, acc[mt]);
                 }
             }
         } else {
+#if defined(CVC_PABL) && CVC_PABL >= 2 && CVC_PABL <= 4
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
+            for (int q = 0; q < 4; ++q) {                               // ablation: memory side only, keep the loads live
+                asm volatile("" ::"v"(f.w[q]));
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
+                for (int mt = 0; mt < MT; ++mt) asm volatile("" ::"v"(f.x[mt][q]));
+            }
+            return;
+#endif
+            if constexpr (SPLIT) {
+                // the lane half's 4 quads = 16 k-slots = two K=16 steps (quads 2s, 2s+1); W and X use the same slot map
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-                        acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w[q][e], f.x[mt][q][e], acc[mt], 0, 0, 0);
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const Split3 W = split8(f.w[2 * s2], f.w[2 * s2 + 1]);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+#if defined(CVC_PABL) && (CVC_PABL == 5 || CVC_PABL == 6)
+                        // ablation: activations arrive pre-split (no VALU work on them; 5: same bytes, 6: 1.5 x the bytes) -- timing only
+                        Split3 X;
+                        X.hi = __builtin_bit_cast(u32x4, f.x[mt][2 * s2]); X.mid = __builtin_bit_cast(u32x4, f.x[mt][2 * s2 + 1]);
+#if CVC_PABL == 6
+                        X.lo = __builtin_bit_cast(u32x4, f.x2[mt][s2]);
+#else
+                        X.lo = X.hi;
+#endif
+#else
+                        const Split3 X = split8(f.x[mt][2 * s2], f.x[mt][2 * s2 + 1]);
+#endif
+                        acc[mt] = mfma_bf16(W.mid, X.mid, acc[mt]);
+                        acc[mt] = mfma_bf16(W.lo, X.hi, acc[mt]);
+                        acc[mt] = mfma_bf16(W.hi, X.lo, acc[mt]);
+                        acc[mt] = mfma_bf16(W.mid, X.hi, acc[mt]);
+                        acc[mt] = mfma_bf16(W.hi, X.mid, acc[mt]);
+                        acc[mt] = mfma_bf16(W.hi, X.hi, acc[mt]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+                            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w[q][e], f.x[mt][q][e], acc[mt], 0, 0, 0);
+            }
         }
     };
 
@@ -287,7 +338,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
     // The steady-state loop issues its loads UNCONDITIONALLY: with a conditional load on any path the
     // compiler's s_waitcnt insertion has to assume the fewest loads outstanding and degrades the
     // counted vmcnt(N) of the oldest slot to a near-full drain.
-    PFrag<MT> ring[DEPTH];
+    Frag ring[DEPTH];
     if (n_my >= DEPTH) {
         // slots 0 .. DEPTH-2 are filled up front; every step multiplies slot s while it (re)fills the slot
         // consumed one step earlier, the 12 loads spread between the 32 MFMAs of the step
@@ -302,7 +353,21 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
 #ifdef CVC_TS
                 if (s == 0 && j == 0) CVC_TS_MARK(1);
 #endif
-                if constexpr (SPLIT) {
+                if constexpr (WB16) {
+                    // 2 + 4 MT loads, 6 MT MFMAs and the activation split (~36 VALU per split8) of one slot, interleaved
+#pragma unroll
+                    for (int g = 0; g < 2 * MT - 2; ++g) {
+                        __builtin_amdgcn_sched_group_barrier(0x002, 15, 0);   // VALU (operand split + addresses)
+                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);    // MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);    // VMEM read
+                    }
+#pragma unroll
+                    for (int g = 2 * MT - 2; g < 2 + 4 * MT; ++g) {
+                        __builtin_amdgcn_sched_group_barrier(0x002, 15, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    }
+                } else if constexpr (SPLIT) {
 #pragma unroll
                     for (int g = 0; g < 4 + 4 * MT; ++g) {
                         __builtin_amdgcn_sched_group_barrier(0x002, 18, 0);  // VALU (operand split + addresses)
@@ -612,6 +677,9 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
 #ifndef CVC_PACKED_DEPTH8
 #define CVC_PACKED_DEPTH8 3
 #endif
+#ifndef CVC_BF16W_DEPTH
+#define CVC_BF16W_DEPTH 4       // WB16, chunks in flight per wave: 2 KB of weights + 4 / 8 KB of activations each (M <= 32 / 64 rows)
+#endif
 
 static int cvc_packed_lstm_blocks = 1;
 // A/B + test hook: weight blocks per workgroup of the decode LSTM gate GEMM (1 = default, or 2); returns the previous setting,
@@ -660,6 +728,23 @@ static int launch_packed(const PackedArgs& a_in, int blocks, hipStream_t st) {
     return cvc_launch_status();
 }
 
+// bf16-stored weights: one form, whatever cvc_gemm_split_mode and cvc_packed_lstm_blocks say
+template <bool LSTM>
+static int launch_packed_bf16w(PackedArgs a, int blocks, hipStream_t st) {
+    if (a.wstride == 0) a.wstride = (long long)a.nquad * 128;
+    const dim3 grid(blocks, LSTM || a.ksplit < 1 ? 1 : a.ksplit);
+    if constexpr (LSTM) {
+        if (a.w_cached) {
+            if (a.M <= 32) hipLaunchKernelGGL((skinny_gemm_packed_kernel<1, true, CVC_BF16W_DEPTH, true, 8, false, 1, false, true, true>), grid, dim3(512), 0, st, a);
+            else hipLaunchKernelGGL((skinny_gemm_packed_kernel<2, true, CVC_BF16W_DEPTH, true, 8, false, 1, false, true, true>), grid, dim3(512), 0, st, a);
+            return cvc_launch_status();
+        }
+    }
+    if (a.M <= 32) hipLaunchKernelGGL((skinny_gemm_packed_kernel<1, LSTM, CVC_BF16W_DEPTH, true, 8, false, 1, false, false, true>), grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((skinny_gemm_packed_kernel<2, LSTM, CVC_BF16W_DEPTH, true, 8, false, 1, false, false, true>), grid, dim3(512), 0, st, a);
+    return cvc_launch_status();
+}
+
 extern "C" int cvc_packed_lstm_fwd(const float* wp, const float* xq, int K, const float* b_ih, const float* b_hh,
                                    const float* gate_bias, const float* c_prev_q, int M, int R, float* h_dst1_q,
                                    float* h_dst2_q, float* c_out_q, cvc_stream_t stream) {
@@ -700,6 +785,21 @@ extern "C" int cvc_packed_lstm_embgate_ex_fwd(const float* wp, long long w_blk_s
     a.bias = b_ih; a.bias2 = b_hh; a.gate_bias = gate_bias; a.c_prev_q = c_prev_q; a.c_out_q = c_out_q;
     a.h_dst1_q = h_dst1_q; a.h_dst2_q = h_dst2_q; a.ksplit = 1; a.emb_gate = emb_gate; a.word = word; a.w_cached = w_cached ? 1 : 0;
     return launch_packed<true>(a, R / 8, (hipStream_t)stream);
+}
+
+extern "C" int cvc_packed_lstm_bf16w_fwd(const uint16_t* wp, long long w_blk_stride, const float* xq, int K, const float* b_ih,
+                                         const float* b_hh, const float* gate_bias, const float* emb_gate, const int64_t* word,
+                                         const float* c_prev_q, int M, int R, float* h_dst1_q, float* h_dst2_q, float* c_out_q,
+                                         int w_cached, cvc_stream_t stream) {
+    if (!wp || !xq || !c_prev_q || !c_out_q || (K & 31) || K < 32 || R < 8 || (R & 7) || M < 1 || M > 64) return CVC_E_BADARG;
+    if ((emb_gate != nullptr) != (word != nullptr)) return CVC_E_BADARG;
+    if (w_blk_stride != 0 && (w_blk_stride < (long long)K * 32 || (w_blk_stride & 7))) return CVC_E_BADARG;
+    if (((uintptr_t)wp & 15) || ((uintptr_t)xq & 15)) return CVC_E_BADARG;
+    PackedArgs a{};
+    a.wp = reinterpret_cast<const float*>(wp); a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = 4 * R; a.R = R; a.wstride = w_blk_stride;
+    a.bias = b_ih; a.bias2 = b_hh; a.gate_bias = gate_bias; a.c_prev_q = c_prev_q; a.c_out_q = c_out_q;
+    a.h_dst1_q = h_dst1_q; a.h_dst2_q = h_dst2_q; a.ksplit = 1; a.emb_gate = emb_gate; a.word = word; a.w_cached = w_cached ? 1 : 0;
+    return launch_packed_bf16w<true>(a, R / 8, (hipStream_t)stream);
 }
 
 extern "C" int cvc_packed_lstm_late_fwd(const float* wp, long long w_blk_stride, const float* xq, int K, const float* b_ih,
@@ -979,4 +1079,16 @@ extern "C" int cvc_packed_linear_fwd(const float* wp, const float* xq, int K, co
     a.wp = wp; a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = Nout; a.R = 0;
     a.bias = bias; a.y = y; a.ldy = ldy; a.ksplit = ksplit; a.split_stride = (long long)M * ldy; a.top2_part = top2_part;
     return launch_packed<false>(a, (Nout + 31) / 32, (hipStream_t)stream);
+}
+
+extern "C" int cvc_packed_linear_bf16w_fwd(const uint16_t* wp, const float* xq, int K, const float* bias, int M, int Nout,
+                                           int ksplit, float* y, int ldy, float* top2_part, cvc_stream_t stream) {
+    if (!wp || !xq || (K & 31) || K < 32 || Nout < 1 || ksplit < 1 || (!y && !top2_part) || M < 1 || M > 64) return CVC_E_BADARG;
+    if (ksplit > 1 && top2_part != nullptr) return CVC_E_BADARG;
+    if (y != nullptr && ldy < Nout) return CVC_E_BADARG;
+    if (((uintptr_t)wp & 15) || ((uintptr_t)xq & 15)) return CVC_E_BADARG;
+    PackedArgs a{};
+    a.wp = reinterpret_cast<const float*>(wp); a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = Nout; a.R = 0;
+    a.bias = bias; a.y = y; a.ldy = ldy; a.ksplit = ksplit; a.split_stride = (long long)M * ldy; a.top2_part = top2_part;
+    return launch_packed_bf16w<false>(a, (Nout + 31) / 32, (hipStream_t)stream);
 }

@@ -61,7 +61,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         path without the embedding-gate schedule are refused.
         weights_dtype: "fp32" (default) or "bf16" -- a precision setting, not a speed switch: the six weight matrices
         (BF16_ROUNDED_KEYS) are rounded to bf16 (nearest even) when the engine binds the checkpoint and stored as bf16 packs
-        (csrc/gemm_packed_bf16w.hip: half the weight bytes per step, three MFMAs per product instead of six); the decode computes
+        (the WB16 mode of csrc/gemm_packed.hip: half the weight bytes per step, three MFMAs per product instead of six); the decode computes
         what the fp32 engine computes on a checkpoint that holds the rounded values -- activations, state, accumulation, softmax
         and word selection stay fp32.  Packed path with the embedding-gate schedule only (greedy or sampling with sample_n = 1,
         <= 64 rows); the engine walks its launch list from Python (no C driver) and capture() turns it into a HIP graph.  Every

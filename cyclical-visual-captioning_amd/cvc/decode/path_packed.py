@@ -82,8 +82,6 @@ class PackedPath:
         nblk_v = (V + 31) // 32
         if self.gsk:
             return out + self._build_gsk_steps()
-        if self.bf16w:
-            return out + self._build_bf16w_steps()
         if self.embgate:
             return out + self._build_embgate_steps()
         for t in range(self.T):
@@ -137,7 +135,9 @@ class PackedPath:
         return out
 
     def _build_embgate_steps(self):
-        """The T steps of the embedding-gate schedule (the launch list csrc/decode_driver.hip::run_packed_eg enqueues)."""
+        """The T steps of the embedding-gate schedule (the launch list csrc/decode_driver.hip::run_packed_eg enqueues), with fp32 or
+        bf16-stored weights (weights_dtype="bf16"): same launches and names, the four GEMMs on the WB16 mode of csrc/gemm_packed.hip;
+        attention passes and word selection do not depend on the weights' dtype."""
         L, W = hip.lib(), self.W
         B, N, Fr, R, A, V, rows = self.B, self.N, self.F, W.R, W.A, W.V, self.rows
         fc, conv, pconv, pool, ppool = self.feats
@@ -145,18 +145,23 @@ class PackedPath:
         qoff = lambda buf, k0: buf.data_ptr() + (k0 // 4) * 64 * 4 * 4
         out = []
         nblk_v = (V + 31) // 32
+        if self.bf16w:
+            att_fn, linear_fn = L.cvc_packed_lstm_bf16w_fwd, L.cvc_packed_linear_bf16w_fwd
+            w_att, att_stride, embgate, w_h, w_o = W.pb_att2, 2 * R * 32, W.r_embgate, W.pb_h, W.pb_o
+        else:
+            att_fn, linear_fn = L.cvc_packed_lstm_embgate_ex_fwd, L.cvc_packed_linear_fwd
+            w_att, att_stride, embgate, w_h, w_o = W.p_att2, (2 * R // 4) * 128, W.t_embgate, W.p_h, W.p_o
         for t in range(self.T):
             rd, wr = t & 1, (t + 1) & 1
             XA_r, XA_w, XL_r, XL_w = self.XA[rd], self.XA[wr], self.XL[rd], self.XL[wr]
-            # step 0 multiplies the all-zero initial state: one chunk of the attention cell's K, the language cell without its
-            # h_lang columns (see run_packed_eg)
-            first = t == 0 and hip.gemm_packed_split(-1) == 2
-            out.append(("att_lstm", L.cvc_packed_lstm_embgate_ex_fwd, (ptr(W.p_att2), (2 * R // 4) * 128, ptr(XA_r), 32 if first else 2 * R, None, None,
-                                                                       ptr(self.gate_fc), ptr(W.t_embgate), ptr(self.words[t]), ptr(self.cA[rd]),
-                                                                       rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
-                                                                       1 if self.att_w_cached else 0)))
-            out.append(("h2attn", L.cvc_packed_linear_fwd, (ptr(W.p_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT,
-                                                            ptr(self.q_parts), A, None)))
+            # step 0 multiplies the all-zero initial state (an exact zero times a finite weight adds nothing): one chunk of the
+            # attention cell's K, the language cell without its h_lang columns (see run_packed_eg)
+            first = t == 0 and (self.bf16w or hip.gemm_packed_split(-1) == 2)
+            out.append(("att_lstm", att_fn, (ptr(w_att), att_stride, ptr(XA_r), 32 if first else 2 * R, None, None,
+                                             ptr(self.gate_fc), ptr(embgate), ptr(self.words[t]), ptr(self.cA[rd]),
+                                             rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
+                                             1 if self.att_w_cached else 0)))
+            out.append(("h2attn", linear_fn, (ptr(w_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT, ptr(self.q_parts), A, None)))
             sets = (hip.AttnSet * 2)()
             sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
                                   ptr(self.att_steps[t]), None, N, self.stream_r)
@@ -165,7 +170,12 @@ class PackedPath:
             out.append(("attn_scores", L.cvc_attn_scores_qparts, (W.kind, ptr(self.q_parts), self.QSPLIT, ptr(W.b_h), ptr(W.w_a),
                                                                   ptr(W.b_a), self.inv_temp, sets, 2, B, 1, A)))
             out.append(("attn_wsum", L.cvc_attn_wsum_quad, (sets, 2, B, 1, R, ptr(XL_r))))
-            if first:
+            if self.bf16w:
+                out.append(("lang_lstm", L.cvc_packed_lstm_bf16w_fwd, (ptr(W.pb_lang), 3 * R * 32, ptr(XL_r), 2 * R if first else 3 * R,
+                                                                       ptr(W.b_ih_lang), ptr(W.b_hh_lang), None, None, None, ptr(self.cL[rd]),
+                                                                       rows, R, ptr(XA_w), qoff(XL_w, 2 * R), ptr(self.cL[wr]),
+                                                                       1 if self.lang_w_cached else 0)))
+            elif first:
                 out.append(("lang_lstm", L.cvc_packed_lstm_late_fwd, (ptr(W.p_lang), (3 * R // 4) * 128, ptr(XL_r), 2 * R, ptr(W.b_ih_lang),
                                                                       ptr(W.b_hh_lang), None, ptr(self.cL[rd]), rows, R, ptr(XA_w),
                                                                       qoff(XL_w, 2 * R), ptr(self.cL[wr]), None)))
@@ -179,63 +189,12 @@ class PackedPath:
             # 20.0 + 7.4 us for these two launches: atomics, fence and a serial merge on one CU cost more than a launch boundary)
             if self.sampling:
                 # row-major logits, then the sampling block (the attention cell of step t + 1 reads the word from words[t + 1])
-                out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V,
-                                                                None)))
+                out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V, None)))
                 out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
                                                                        ptr(self.rng), t, ptr(self.words[t + 1]), 1,
                                                                        ptr(self.logprob[t]))))
             else:
-                out.append(("logits", L.cvc_packed_linear_fwd, (ptr(W.p_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
-                                                                ptr(self.top2_part))))
-                out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
-                                                              ptr(self.logprob[t]), None, 0, None, 0)))
-            self._keep.append(sets)
-        return out
-
-    def _build_bf16w_steps(self):
-        """The T steps of the embedding-gate schedule with bf16-stored weights (weights_dtype="bf16"): the launch list of
-        _build_embgate_steps, same names, with the four GEMMs on csrc/gemm_packed_bf16w.hip; attention passes and word selection
-        are the fp32 engine's own launches."""
-        L, W = hip.lib(), self.W
-        B, N, Fr, R, A, V, rows = self.B, self.N, self.F, W.R, W.A, W.V, self.rows
-        fc, conv, pconv, pool, ppool = self.feats
-        ptr = lambda t: None if t is None else t.data_ptr()
-        qoff = lambda buf, k0: buf.data_ptr() + (k0 // 4) * 64 * 4 * 4
-        out = []
-        nblk_v = (V + 31) // 32
-        for t in range(self.T):
-            rd, wr = t & 1, (t + 1) & 1
-            XA_r, XA_w, XL_r, XL_w = self.XA[rd], self.XA[wr], self.XL[rd], self.XL[wr]
-            # step 0 multiplies the all-zero initial state (an exact zero times a finite weight adds nothing): one chunk of the
-            # attention cell's K, the language cell without its h_lang columns
-            first = t == 0
-            out.append(("att_lstm", L.cvc_packed_lstm_bf16w_fwd, (ptr(W.pb_att2), 2 * R * 32, ptr(XA_r), 32 if first else 2 * R, None, None,
-                                                                  ptr(self.gate_fc), ptr(W.r_embgate), ptr(self.words[t]), ptr(self.cA[rd]),
-                                                                  rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
-                                                                  1 if self.att_w_cached else 0)))
-            out.append(("h2attn", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT,
-                                                                  ptr(self.q_parts), A, None)))
-            sets = (hip.AttnSet * 2)()
-            sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
-                                  ptr(self.att_steps[t]), None, N, self.stream_r)
-            sets[1] = hip.AttnSet(ptr(pconv), ptr(conv), None, None, ptr(self.scores_f), None, ptr(self.attn_f), None, Fr,
-                                  self.stream_f)
-            out.append(("attn_scores", L.cvc_attn_scores_qparts, (W.kind, ptr(self.q_parts), self.QSPLIT, ptr(W.b_h), ptr(W.w_a),
-                                                                  ptr(W.b_a), self.inv_temp, sets, 2, B, 1, A)))
-            out.append(("attn_wsum", L.cvc_attn_wsum_quad, (sets, 2, B, 1, R, ptr(XL_r))))
-            out.append(("lang_lstm", L.cvc_packed_lstm_bf16w_fwd, (ptr(W.pb_lang), 3 * R * 32, ptr(XL_r), 2 * R if first else 3 * R,
-                                                                   ptr(W.b_ih_lang), ptr(W.b_hh_lang), None, None, None, ptr(self.cL[rd]),
-                                                                   rows, R, ptr(XA_w), qoff(XL_w, 2 * R), ptr(self.cL[wr]),
-                                                                   1 if self.lang_w_cached else 0)))
-            if self.sampling:
-                out.append(("logits", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits),
-                                                                      V, None)))
-                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
-                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
-                                                                       ptr(self.logprob[t]))))
-            else:
-                out.append(("logits", L.cvc_packed_linear_bf16w_fwd, (ptr(W.pb_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V,
-                                                                      ptr(self.top2_part))))
+                out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V, ptr(self.top2_part))))
                 out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
                                                               ptr(self.logprob[t]), None, 0, None, 0)))
             self._keep.append(sets)

@@ -93,7 +93,7 @@ def lstm_packed_rows(R: int, device) -> torch.Tensor:
     return (((i >> 3) * R + (i & 7)).view(1, 32) + (torch.arange(R // 8, device=device) * 8).view(-1, 1)).reshape(-1)
 
 
-# ------------------------------------------------------------------ bf16-stored weights (csrc/gemm_packed_bf16w.hip)
+# ------------------------------------------------------------------ bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip)
 WEIGHTS_DTYPES = ("fp32", "bf16")
 # the six matrices DecodeEngine(weights_dtype="bf16") rounds when it binds a checkpoint (state_dict names)
 BF16_ROUNDED_KEYS = ("decoder_core.att_lstm.weight_ih", "decoder_core.att_lstm.weight_hh", "decoder_core.lang_lstm.weight_ih",

@@ -234,7 +234,7 @@ SIGNATURES = {
     "cvc_beam_select_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "cvc_sample_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P],
     "cvc_sample_advance": [_P, _P],
-    # packed GEMMs with bf16-stored weights (csrc/gemm_packed_bf16w.hip; building blocks)
+    # packed GEMMs with bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip; building blocks)
     "cvc_packed_lstm_bf16w_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P],
     "cvc_packed_linear_bf16w_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],

@@ -243,7 +243,8 @@ int cvc_lstm_seq_bwd(const float* dy, long long dy_ld_m, long long dy_ld_t, cons
                      const float* c, long long c_ld_m, long long c_ld_t, const float* w_hh, int M, int F, int H, int ndir, float* dg,
                      float* work, cvc_stream_t stream);
 
-/* ---- packed GEMMs with bf16-STORED weights (csrc/gemm_packed_bf16w.hip; DecodeEngine(weights_dtype="bf16")).
+/* ---- packed GEMMs with bf16-STORED weights (the WB16 mode of skinny_gemm_packed_kernel, csrc/gemm_packed.hip;
+ * DecodeEngine(weights_dtype="bf16")).
  * wp: [ceil(Nout/32)][K/8][32 rows][8 k] bf16 (cvc.decode.pack_weights_bf16; row order of the fp32 pack), 16-byte aligned.
  * Activations, biases, state, accumulation and outputs are fp32 as in cvc_packed_lstm_embgate_ex_fwd / cvc_packed_linear_fwd;
  * every product is w * (x.hi + x.mid + x.lo), all three terms.  Bitwise equal (up to the sign of zero) to the fp32 entry points

@@ -1,4 +1,4 @@
-"""bf16-stored decode weights on the GPU (DecodeEngine(weights_dtype="bf16"), csrc/gemm_packed_bf16w.hip): the two kernels against
+"""bf16-stored decode weights on the GPU (DecodeEngine(weights_dtype="bf16"), csrc/gemm_packed.hip): the two kernels against
 fp64 and against the fp32 kernels on the rounded weights, the engine against the CPU oracle on the rounded checkpoint and against the
 fp32 engine on rounded weights, idempotence / determinism / reuse, sampling with one caption per clip, the model plumbing and the
 refusals."""
