@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void gru_pointwise_bwd_kernel(GruStepBwd2 both
 // dy, gates, y: row of (clip m, step t) at base + m * ld_m + t * ld_t, columns [ndir][H] (dy, y) / [ndir][4][H] (gates).
 // w_hh: [ndir][3H, H] row-major (the checkpoint layout).  dgi, dgh: [F * M rows (t * M + m), ndir * 3H] outputs.
 // work: ndir * (2 * M * H + 3H * 64 + ksplit * M * ceil(H / 128) * 128) floats, ksplit = cvc_gru_seq_bwd_ksplit(H).
-// M <= 64, H % 8 == 0.
+// M <= 64, H % 8 == 0, the strides of dy / gates / y multiples of 4 floats (CVC_E_BADARG without launching otherwise).
 extern "C" int cvc_gru_seq_bwd_ksplit(int H) {
     const int slabs = (H + 127) / 128;
     int ks = 256 / slabs;
@@ -85,6 +85,8 @@ extern "C" int cvc_gru_seq_bwd(const float* dy, long long dy_ld_m, long long dy_
                                int F, int H, int ndir, float* dgi, float* dgh, float* work, cvc_stream_t stream) {
     if (!dy || !gates || !y || !w_hh || !dgi || !dgh || !work || M < 1 || M > 64 || F < 1 || H < 8 || (H & 7) || ndir < 1 || ndir > 2)
         return CVC_E_BADARG;
+    // the gate kernel reads dy / gates / y four floats at a time: every row must start on a multiple of 4 floats
+    if (((dy_ld_m | dy_ld_t | g_ld_m | g_ld_t | y_ld_m | y_ld_t) & 3) != 0) return CVC_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const int ks = cvc_gru_seq_bwd_ksplit(H);
     const long long ntot = (long long)((H + 127) / 128) * 128;     // plane row length of the backward-data product

@@ -213,7 +213,9 @@ CVC_API int cvc_gru_seq_persistent_train_fwd(const float* wp, const float* gi, l
  * (clip m, step t) at base + m * ld_m + t * ld_t, columns [ndir][H] / [ndir][4][H]; w_hh [ndir][3H, H] row-major.
  * Outputs dgi, dgh: [F * M rows (t * M + m), ndir * 3H] -- pre-activation gradients of the input / hidden side, from which the
  * caller takes dW_ih, dX, dW_hh and the biases in dense GEMMs over all steps.  work: ndir * (2 M H + 192 H + ksplit * M *
- * ceil(H/128) * 128) floats, ksplit = cvc_gru_seq_bwd_ksplit(H).  M <= 64, H % 8 == 0. */
+ * ceil(H/128) * 128) floats, ksplit = cvc_gru_seq_bwd_ksplit(H).  M <= 64, H % 8 == 0, and the strides of dy / gates / y multiples
+ * of 4 floats (the gate kernel reads four floats at a time; CVC_E_BADARG without launching otherwise).  The persistent form below
+ * reads them one float at a time and takes any stride. */
 /* Persistent form of cvc_gru_seq_bwd (csrc/gru_bwd_persistent.hip): one cooperative launch for the whole sequence, W_hh columns
  * in registers, dgh exchanged through per-step slots.  wt = W_hh^T packed [ndir][H/8][3H/8][8 units][8 k]
  * (cvc.gru.pack_gru_weights_t), slots = F * ndir * 3H * 64 floats, sync = cvc_gru_bwd_persistent_sync_words() words (word 4
