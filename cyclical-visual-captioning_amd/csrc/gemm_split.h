@@ -45,4 +45,14 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const 
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
+// d += W x X on a 32x32x16 tile: the six cross terms, smallest first (mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi)
+__device__ __forceinline__ void split_mma6(const Split3& W, const Split3& X, f32x16& d) {
+    d = mfma_bf16(W.mid, X.mid, d);
+    d = mfma_bf16(W.lo, X.hi, d);
+    d = mfma_bf16(W.hi, X.lo, d);
+    d = mfma_bf16(W.mid, X.hi, d);
+    d = mfma_bf16(W.hi, X.mid, d);
+    d = mfma_bf16(W.hi, X.hi, d);
+}
+
 }  // namespace

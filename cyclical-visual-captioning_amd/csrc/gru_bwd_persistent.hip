@@ -1,6 +1,6 @@
 // Persistent form of the GRU backward recurrence (cvc_gru_seq_bwd launches three kernels per time step; 70 of the 93 ms of a
-// config-2 forward + backward are those 1 440 launches per layer).  One cooperative launch per layer, built like the forward
-// (gru_persistent.hip): a workgroup owns 8 hidden units of one direction for all F steps.
+// config-2 forward + backward are those 1 440 launches per layer).  One launch per layer (recurrence_sync.h), built like the
+// forward (gru_persistent.hip): a workgroup owns 8 hidden units of one direction for all F steps.
 //   per step s (the forward direction walks t = F-1 .. 0, the reverse direction t = 0 .. F-1):
 //     1. wait until every workgroup of the direction has published dgh of step s - 1 (spread arrival counters);
 //     2. dh_mm[m, j] = sum_k dgh_{s-1}[m, k] W_hh[k, j] for its 8 units j: the 3H x 8 weight columns live in registers as split
@@ -10,13 +10,12 @@
 //        memory (the dense dW / dX products of the host side read them), dgh_t of the own units to the step's exchange slot
 //        with write-through stores; arrival.
 #include "cvc_common.h"
-#include <stdlib.h>
 #include "gemm_split.h"
+#include "recurrence_sync.h"
 
 namespace {
 
-constexpr int BCNT = 32, BCNT_STRIDE = 1024, BSYNC_ERR = 4;
-constexpr long long BSYNC_WORDS = BSYNC_ERR + 8 + 2LL * BCNT * BCNT_STRIDE;
+constexpr int SYNC_GROUPS = 2;                    // arrival counter groups (recurrence_sync.h): one per direction
 
 struct GruBArgs {
     const float* wt;                              // W_hh^T packed [ndir][H/8][3H/8][8 units][8 k]
@@ -36,6 +35,16 @@ __device__ __forceinline__ f32x4v mfma16(const u32x4 a, const u32x4 b, const f32
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
+// split_mma6 (gemm_split.h) on a 16x16x32 tile
+__device__ __forceinline__ void split_mma6_16(const Split3& W, const Split3& X, f32x4v& d) {
+    d = mfma16(W.mid, X.mid, d);
+    d = mfma16(W.lo, X.hi, d);
+    d = mfma16(W.hi, X.lo, d);
+    d = mfma16(W.mid, X.hi, d);
+    d = mfma16(W.hi, X.mid, d);
+    d = mfma16(W.hi, X.hi, d);
+}
+
 // NKS = 32-k steps per wave: 3H = 256 * NKS
 template <int NKS>
 __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_kernel(GruBArgs a) {
@@ -46,7 +55,7 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_kernel(GruBArgs a) 
     const int dir = blockIdx.y, blk = blockIdx.x, ndir = gridDim.y, H = a.H, M = a.M, F = a.F;
     const int K = 3 * H, ngrp = K >> 3;
     const unsigned nblk = gridDim.x;
-    unsigned* counter = a.sync + BSYNC_ERR + 8 + (size_t)(dir * BCNT) * BCNT_STRIDE;
+    unsigned* counter = counter_group(a.sync, dir);
 
     // ---- weights: lane (row r = lane & 15, k group = lane >> 4) of k step ks holds 8 consecutive k of unit r (rows 8..15 zero)
     const int wr = lane & 15, wg = lane >> 4;
@@ -88,26 +97,8 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_kernel(GruBArgs a) 
         float dh_mm = 0.f;
         if (s > 0) {
             // ---- wait for dgh of step s - 1
-            if (wave == 0) {
-                const unsigned target = nblk * (unsigned)s;
-                unsigned it = 0;
-                for (;;) {
-                    unsigned v = lane < BCNT ? __hip_atomic_load(counter + (size_t)lane * BCNT_STRIDE, __ATOMIC_RELAXED,
-                                                                 __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-                    for (int o = 1; o < BCNT; o <<= 1) v += __shfl_xor(v, o, 64);
-                    v = __builtin_amdgcn_readfirstlane(v);
-                    if (v >= target) break;
-                    if (++it > a.spin_limit || __hip_atomic_load(a.sync + BSYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                        if (lane == 0) {
-                            __hip_atomic_store(a.sync + BSYNC_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            gave_up = 1;
-                        }
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
+            if (wave == 0 && wait_arrivals(a.sync, counter, nblk * (unsigned)s, a.spin_limit, lane) && lane == 0)
+                gave_up = 1;                              // tell the workgroup
             __syncthreads();
             if (gave_up) return;
             // ---- dh_mm = dgh_{s-1} W_hh[:, own units]: this wave's k steps, 4 tiles of 16 clips
@@ -130,14 +121,7 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_kernel(GruBArgs a) 
                 const int j = ph >> 1;
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2) {
-                    const int ct = (ph & 1) * 2 + c2;
-                    const Split3 Xs = split8(xb[ph & 1][c2][0], xb[ph & 1][c2][1]);
-                    acc[ct] = mfma16(W[j].mid, Xs.mid, acc[ct]);
-                    acc[ct] = mfma16(W[j].lo, Xs.hi, acc[ct]);
-                    acc[ct] = mfma16(W[j].hi, Xs.lo, acc[ct]);
-                    acc[ct] = mfma16(W[j].mid, Xs.hi, acc[ct]);
-                    acc[ct] = mfma16(W[j].hi, Xs.mid, acc[ct]);
-                    acc[ct] = mfma16(W[j].hi, Xs.hi, acc[ct]);
+                    split_mma6_16(W[j], split8(xb[ph & 1][c2][0], xb[ph & 1][c2][1]), acc[(ph & 1) * 2 + c2]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -168,59 +152,22 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_persistent_kernel(GruBArgs a) 
                 // own units of the exchange slot: group (g H + 8 blk) / 8 of gate g, element (clip, unit); straight to memory
                 float* sl = a.slots + ((size_t)s * ndir + dir) * (size_t)ngrp * 512 + ((size_t)blk * 64 + em) * 8 + ejr;
                 const size_t gs = (size_t)(H / 8) * 512;
-                asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 0" ::"v"(sl), "v"(dr) : "memory");
-                asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 0" ::"v"(sl + gs), "v"(dz) : "memory");
-                asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 0" ::"v"(sl + 2 * gs), "v"(dnr) : "memory");
+                store_through1(sl, dr);
+                store_through1(sl + gs, dz);
+                store_through1(sl + 2 * gs, dnr);
             }
         }
         if (s + 1 < F) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            drain_stores();
             __syncthreads();                              // every wave's slot stores are acknowledged; `red` may be rewritten
-            if (tid == 0)
-                __hip_atomic_fetch_add(counter + (size_t)(blk % BCNT) * BCNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) arrive(counter, blk);
         }
     }
-}
-
-__global__ __launch_bounds__(256) void gru_bwd_zero_kernel(unsigned* sync) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < BSYNC_WORDS) sync[t] = 0u;
-}
-
-template <int NKS>
-int launch_bwd(GruBArgs& a, int ndir, hipStream_t st) {
-    void* params[] = {&a};
-    const dim3 grid(a.H / 8, ndir);
-    int per_cu = 0, devid = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)gru_bwd_persistent_kernel<NKS>, 512, 0) != hipSuccess ||
-        hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess) {
-        (void)hipGetLastError();
-        return CVC_E_BADARG;
-    }
-    if ((long long)per_cu * cus < (long long)grid.x * grid.y) return CVC_E_BADARG;
-    // An ORDINARY launch, not hipLaunchCooperativeKernel (round 6).  Co-residency is what the kernel needs, and the occupancy check
-    // above plus the stream's in-order execution give it (the grid is at most one workgroup per CU on an otherwise idle chip);
-    // what the cooperative launch adds is a trip through the runtime's device-wide cooperative queue -- and with it a state of the
-    // runtime's hardware queues in which, once any other stream capture has happened in the process, EVERY later kernel of the
-    // step took 10 - 25 us longer (the captured end-to-end training step 91 -> 122 ms; tools/runs/r06_e2e_after_decode.py,
-    // GPU_MAX_HW_QUEUES <= 2 or per-step GRU forms made it disappear).  A grid that is not resident after all is caught as before:
-    // the barrier's spin is bounded and raises the error word (the caller falls back / the step is voided and re-run).
-    // CVC_GRU_COOPERATIVE=1 restores the cooperative launch (A/B).
-    static const bool coop = [] { const char* e = getenv("CVC_GRU_COOPERATIVE"); return e && e[0] == '1'; }();
-    if (coop) {
-        if (hipLaunchCooperativeKernel((const void*)gru_bwd_persistent_kernel<NKS>, grid, dim3(512), params, 0, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return CVC_E_BADARG;
-        }
-    } else {
-        hipLaunchKernelGGL((gru_bwd_persistent_kernel<NKS>), grid, dim3(512), 0, st, a);
-    }
-    return cvc_launch_status();
 }
 
 }  // namespace
 
-extern "C" int cvc_gru_bwd_persistent_sync_words(void) { return (int)BSYNC_WORDS; }
+extern "C" int cvc_gru_bwd_persistent_sync_words(void) { return (int)sync_words(SYNC_GROUPS); }
 
 // Same inputs and outputs as cvc_gru_seq_bwd except: wt = W_hh^T packed [ndir][H/8][3H/8][8][8] (cvc.gru.pack_gru_weights_t),
 // slots = F * ndir * 3H * 64 floats of exchange memory, sync = cvc_gru_bwd_persistent_sync_words() words (word 4 non-zero
@@ -238,12 +185,14 @@ extern "C" int cvc_gru_seq_bwd_persistent(const float* dy, long long dy_ld_m, lo
     a.wt = wt; a.dy = dy; a.dy_ld_m = dy_ld_m; a.dy_ld_t = dy_ld_t; a.gates = gates; a.g_ld_m = g_ld_m; a.g_ld_t = g_ld_t;
     a.y = y; a.y_ld_m = y_ld_m; a.y_ld_t = y_ld_t; a.dgi = dgi; a.dgh = dgh; a.slots = slots; a.sync = sync;
     a.M = M; a.F = F; a.H = H; a.spin_limit = 1u << 20;
-    hipLaunchKernelGGL(gru_bwd_zero_kernel, dim3((unsigned)((BSYNC_WORDS + 255) / 256)), dim3(256), 0, st, sync);
+#define CVC_GRU_B(NKS_) \
+    return launch_resident(gru_bwd_persistent_kernel<NKS_>, dim3(H / 8, ndir), 512, a, nullptr, 0, sync, SYNC_GROUPS, st)
     switch (3 * H / 256) {
-        case 3: return launch_bwd<3>(a, ndir, st);
-        case 6: return launch_bwd<6>(a, ndir, st);
-        case 9: return launch_bwd<9>(a, ndir, st);
-        case 12: return launch_bwd<12>(a, ndir, st);
+        case 3: CVC_GRU_B(3);
+        case 6: CVC_GRU_B(6);
+        case 9: CVC_GRU_B(9);
+        case 12: CVC_GRU_B(12);
         default: return CVC_E_BADARG;
     }
+#undef CVC_GRU_B
 }

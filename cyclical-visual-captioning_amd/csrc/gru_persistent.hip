@@ -1,7 +1,7 @@
 // Persistent form of the GRU recurrence (the encoder's frame context, reference backbone.py:103-106, 335-338).
 //
 // cvc_gru_seq_fwd (gemm_packed.hip) launches the packed gate GEMM once per time step: at H = 1024 that is 19 us per step, of
-// which ~12 us are launch / drain latency and ~7 us the re-read of W_hh (33 MB per step).  Here ONE cooperative launch runs
+// which ~12 us are launch / drain latency and ~7 us the re-read of W_hh (33 MB per step).  Here ONE launch (recurrence_sync.h) runs
 // the whole sequence:
 //   * a workgroup owns 8 hidden units of one direction (their r, z, n rows of W_hh: a 32-row MFMA tile whose last 8 rows are
 //     zero) for all F steps, and keeps those weights IN REGISTERS, already split into the three bf16 terms of the split-product
@@ -16,14 +16,12 @@
 //     other 31 hit its L2.  The spin is bounded: if a peer never arrives (not all workgroups resident) the kernel raises the
 //     error word instead of hanging the GPU, and the host falls back to the per-step form.
 #include "cvc_common.h"
-#include <stdlib.h>
-#include "gemm_split.h"
+#include "recurrence_sync.h"
+#include "recurrence_tile.h"
 
 namespace {
 
-// sync buffer: word SYNC_ERR = error flag; then 4 groups (direction x batch half) of CNT arrival counters, CNT_STRIDE words apart
-constexpr int CNT = 32, CNT_STRIDE = 1024, SYNC_ERR = 4;
-constexpr long long SYNC_WORDS = SYNC_ERR + 8 + 4LL * CNT * CNT_STRIDE;
+constexpr int SYNC_GROUPS = 4;                    // arrival counter groups (recurrence_sync.h): direction x batch half
 
 struct GruPArgs {
     const float* wp; long long w_stride;          // packed W_hh [ndir][H/8][Kp/4][32][4]
@@ -33,7 +31,7 @@ struct GruPArgs {
     float* hq; long long h_stride;                // state slots, quad layout: [F + 1][ndir][Kp/4][64][4], slot 0 = h0
     float* y; long long y_ld_m, y_ld_t;
     float* gates; long long g_ld_m, g_ld_t;       // training: (r, z, n, W_hn h + b_hn) of every step, columns [ndir][4][H]; nullable
-    unsigned* sync;                               // SYNC_WORDS words: error word + arrival counters (see above)
+    unsigned* sync;                               // sync_words(SYNC_GROUPS) words: error word + arrival counters
     unsigned spin_limit;
 };
 
@@ -55,27 +53,11 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
     const int nquad = a.Kp >> 2;
     const unsigned nblk = gridDim.x;
 
-    // ---- this wave's share of the weights, split once.  Register slot c holds chunk wave + 4 * ((c + rot) % NC).  (Measured:
-    // starting every workgroup at a different chunk, which helps the per-step kernel, is 10 % SLOWER here -- 18.5 vs 16.7 us
-    // per step -- the workgroups of an XCD asking for the same state lines at the same time is what the L2 serves best.)
+    // ---- this wave's share of the weights, split once: register slot c holds chunk wave + NW * c.  (Measured: starting every
+    // workgroup at a different chunk, which helps the per-step kernel, is 10 % SLOWER here -- 18.5 vs 16.7 us per step -- the
+    // workgroups of an XCD asking for the same state lines at the same time is what the L2 serves best.)
     Split3 W[NC][2];
-#ifndef CVC_GRU_ROT
-#define CVC_GRU_ROT 0
-#endif
-    const int rot = CVC_GRU_ROT ? (blk * 5 + dir * 3) % NC : 0;
-    int chunk_of[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) chunk_of[c] = wave + NW * ((c + rot) % NC);
-    {
-        const float* wl = a.wp + (size_t)dir * a.w_stride + ((size_t)blk * nquad * 32 + i) * 4 + kh * 4 * 128;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float* w = wl + (size_t)chunk_of[c] * 8 * 128;
-            const f32x4 q0 = ld4(w), q1 = ld4(w + 128), q2 = ld4(w + 256), q3 = ld4(w + 384);
-            W[c][0] = split8(q0, q1);
-            W[c][1] = split8(q2, q3);
-        }
-    }
+    load_weights<NC, NW>(W, a.wp + (size_t)dir * a.w_stride + ((size_t)blk * nquad * 32 + i) * 4 + kh * 4 * 128, wave);
 
     // ---- epilogue role: thread (em = clip within the group, eqd = which 4 of the 8 hidden units)
     constexpr int ET = MT * 32;
@@ -102,9 +84,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
             const int m = hf * ET + em;                                // clip row of the epilogue role
             const bool ework = eqd < 2 && m < M;
             const size_t eqoff = ((size_t)(ejq / 4) * 64 + (m < 64 ? m : 63)) * 4;
-            // arrivals are spread over CNT counters 4 KB apart (different memory channels): 128 increments of ONE word queue up
-            // behind each other at the memory-side atomic unit, and the last arrival is the one everybody waits for
-            unsigned* counter = a.sync + SYNC_ERR + 8 + (size_t)((dir * 2 + hf) * CNT) * CNT_STRIDE;
+            unsigned* counter = counter_group(a.sync, dir * 2 + hf);
 
             // x-projections of this step: independent of the other workgroups, requested before the wait
             f32x4 egi[3] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
@@ -116,26 +96,8 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
 
             // ---- wait until every workgroup of this direction has published step s - 1 of this group
             if (s > 0) {
-                if (wave == 0) {                                       // lanes 0 .. CNT-1 read one counter each
-                    const unsigned target = nblk * (unsigned)s;
-                    unsigned it = 0;
-                    for (;;) {
-                        unsigned v = lane < CNT ? __hip_atomic_load(counter + (size_t)lane * CNT_STRIDE, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-                        for (int o = 1; o < CNT; o <<= 1) v += __shfl_xor(v, o, 64);
-                        v = __builtin_amdgcn_readfirstlane(v);         // lane 0 holds the sum: one decision for the wave
-                        if (v >= target) break;
-                        if (++it > a.spin_limit || __hip_atomic_load(a.sync + SYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                            if (lane == 0) {
-                                __hip_atomic_store(a.sync + SYNC_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                gave_up = 1;                           // tell the workgroup
-                            }
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                }
+                if (wave == 0 && wait_arrivals(a.sync, counter, nblk * (unsigned)s, a.spin_limit, lane) && lane == 0)
+                    gave_up = 1;                                       // tell the workgroup
                 __syncthreads();                                       // (also: the previous group's readers of `red` are done)
                 if (gave_up) return;                                   // no invalidate: slot s has never been read before
             } else if (hf > 0) {
@@ -144,71 +106,12 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
 
             // ---- partial tiles: this wave's K slice (chunks wave, wave + 4, ...) of this group's clip tiles
             f32x16 acc[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-            // The activations are requested in phases of (half of the wave's chunks) x (one 32-clip tile), two phases in
-            // flight (128 registers next to the 192 of the weights); the schedule is pinned, otherwise the compiler requests
-            // the later phases one load at a time with a full wait behind each
-            constexpr int HC = (NC + 1) / 2;                          // chunks per phase
-            const float* xl = hprev + (size_t)i * 4 + kh * 4 * 256 + hf * ET * 4;
-            f32x4 xb[2][HC][4];
-            auto load_phase = [&](f32x4 (&buf)[HC][4], const int half, const int mt) __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < HC; ++j) {
-                    const int c = half * HC + j;
-                    if (c < NC) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) buf[j][q] = ld4(xl + (size_t)chunk_of[c] * 8 * 256 + q * 256 + mt * 128);
-                    }
-                }
-            };
-            auto mma_phase = [&](const f32x4 (&buf)[HC][4], const int half, f32x16& d) __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < HC; ++j) {
-                    const int c = half * HC + j;
-                    if (c < NC) {
-#pragma unroll
-                        for (int s2 = 0; s2 < 2; ++s2) {
-                            const Split3 X = split8(buf[j][2 * s2], buf[j][2 * s2 + 1]);
-                            const Split3& Wc = W[c][s2];
-                            d = mfma_bf16(Wc.mid, X.mid, d);
-                            d = mfma_bf16(Wc.lo, X.hi, d);
-                            d = mfma_bf16(Wc.hi, X.lo, d);
-                            d = mfma_bf16(Wc.mid, X.hi, d);
-                            d = mfma_bf16(Wc.hi, X.mid, d);
-                            d = mfma_bf16(Wc.hi, X.hi, d);
-                        }
-                    }
-                }
-            };
-            load_phase(xb[0], 0, 0);
-            load_phase(xb[1], 1, 0);
-            const f32x4 ehp = ld4(hprev + eqoff);                     // (every thread: an unconditional load keeps the waits counted)
-            __builtin_amdgcn_sched_barrier(0);
-            mma_phase(xb[0], 0, acc[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MT == 2) load_phase(xb[0], 0, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_phase(xb[1], 1, acc[0]);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MT == 2) {
-                load_phase(xb[1], 1, 1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_phase(xb[0], 0, acc[1]);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_phase(xb[1], 1, acc[1]);
-            }
+            f32x4 ehp;                                  // (every thread: an unconditional load keeps the waits counted)
+            tile_product<MT, NC, NW>(acc, W, hprev + (size_t)i * 4 + kh * 4 * 256 + hf * ET * 4, wave,
+                                     [&]() __attribute__((always_inline)) { ehp = ld4(hprev + eqoff); });
 
             // ---- ordered cross-wave sum, gate arithmetic
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    red[(wave * 32 + row) * LDM + mt * 32 + i] = acc[mt][r];
-                }
+            spill_tiles<MT>((lds_float*)red, acc, wave, lane);
             __syncthreads();
             if (ework) {
                 f32x4 hv, gsave[4];
@@ -217,14 +120,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
                     const int jj = eqd * 4 + e;
                     float pre[3];
 #pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        const int row = g * 8 + jj;
-                        pre[g] = (red[(0 * 32 + row) * LDM + em] + red[(1 * 32 + row) * LDM + em]) +
-                                 (red[(2 * 32 + row) * LDM + em] + red[(3 * 32 + row) * LDM + em]);
-                        if constexpr (NW == 8)
-                            pre[g] += (red[(4 * 32 + row) * LDM + em] + red[(5 * 32 + row) * LDM + em]) +
-                                      (red[(6 * 32 + row) * LDM + em] + red[(7 * 32 + row) * LDM + em]);
-                    }
+                    for (int g = 0; g < 3; ++g) pre[g] = sum_waves<MT, NW>((const lds_float*)red, g * 8 + jj, em);
                     const float rg = fast_sigmoid(pre[0] + egi[0][e] + ebias[0][e]);
                     const float zg = fast_sigmoid(pre[1] + egi[1][e] + ebias[1][e]);
                     const float ng = fast_tanh(egi[2][e] + ebias[2][e] + rg * (pre[2] + ebias[3][e]));
@@ -236,64 +132,20 @@ __global__ __launch_bounds__(NW * 64, 1) void gru_persistent_kernel(GruPArgs a) 
 #pragma unroll
                     for (int g = 0; g < 4; ++g) st4(gp + g * H, gsave[g]);
                 }
-                // the state goes straight through this XCD's L2 to memory (sc0 sc1): a release fence would instead walk the
-                // whole L2 for dirty lines (buffer_wbl2) once per workgroup and step.  (Inline assembly is invisible to the
-                // compiler's hazard recognizer: the s_nop covers "wide store followed by a write to its data registers".)
-                float* hp = hnext + eqoff;
-                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(hp), "v"(hv) : "memory");
+                store_through4(hnext + eqoff, hv);
                 st4(a.y + (size_t)m * a.y_ld_m + t * a.y_ld_t + (size_t)dir * H + ejq, hv);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                drain_stores();
             }
             // ---- publish: one arrival per workgroup, after all of its state stores have been acknowledged
             __syncthreads();
-            if (tid == 0)
-                __hip_atomic_fetch_add(counter + (size_t)(blk % CNT) * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) arrive(counter, blk);
         }
     }
-}
-
-__global__ __launch_bounds__(256) void gru_zero_kernel(float* p, long long n, unsigned* sync) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) p[t] = 0.f;
-    if (t < SYNC_WORDS) sync[t] = 0u;
-}
-
-template <int NH, int MT, int NC, int NW>
-int launch_persistent(GruPArgs& a, int ndir, hipStream_t st) {
-    void* params[] = {&a};
-    const dim3 grid(a.H / 8, ndir);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)gru_persistent_kernel<NH, MT, NC, NW>, NW * 64, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return CVC_E_BADARG;
-    }
-    int devid = 0, cus = 0;
-    if (hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess)
-        return CVC_E_BADARG;
-    if ((long long)per_cu * cus < (long long)grid.x * grid.y) return CVC_E_BADARG;     // would not be co-resident
-    // An ORDINARY launch, not hipLaunchCooperativeKernel (round 6).  Co-residency is what the kernel needs, and the occupancy check
-    // above plus the stream's in-order execution give it (the grid is at most one workgroup per CU on an otherwise idle chip);
-    // what the cooperative launch adds is a trip through the runtime's device-wide cooperative queue -- and with it a state of the
-    // runtime's hardware queues in which, once any other stream capture has happened in the process, EVERY later kernel of the
-    // step took 10 - 25 us longer (the captured end-to-end training step 91 -> 122 ms; tools/runs/r06_e2e_after_decode.py,
-    // GPU_MAX_HW_QUEUES <= 2 or per-step GRU forms made it disappear).  A grid that is not resident after all is caught as before:
-    // the barrier's spin is bounded and raises the error word (the caller falls back / the step is voided and re-run).
-    // CVC_GRU_COOPERATIVE=1 restores the cooperative launch (A/B).
-    static const bool coop = [] { const char* e = getenv("CVC_GRU_COOPERATIVE"); return e && e[0] == '1'; }();
-    if (coop) {
-        if (hipLaunchCooperativeKernel((const void*)gru_persistent_kernel<NH, MT, NC, NW>, grid, dim3(NW * 64), params, 0, st) != hipSuccess) {
-            (void)hipGetLastError();
-            return CVC_E_BADARG;
-        }
-    } else {
-        hipLaunchKernelGGL((gru_persistent_kernel<NH, MT, NC, NW>), grid, dim3(NW * 64), 0, st, a);
-    }
-    return cvc_launch_status();
 }
 
 }  // namespace
 
-extern "C" int cvc_gru_persistent_sync_words(void) { return (int)SYNC_WORDS; }
+extern "C" int cvc_gru_persistent_sync_words(void) { return (int)sync_words(SYNC_GROUPS); }
 
 static int cvc_gru_waves8 = 1;
 // A/B + test hook: 1 (default) = 8 waves per workgroup where K is a multiple of 256, 0 = always 4.  Returns the previous setting.
@@ -356,13 +208,13 @@ static int gru_persistent_impl(const float* wp, const float* gi, long long gi_ld
     a.M = M; a.F = F; a.H = H; a.Kp = H; a.hq = hq; a.h_stride = (long long)H * 64;
     a.y = y; a.y_ld_m = y_ld_m; a.y_ld_t = y_ld_t; a.sync = sync; a.spin_limit = 1u << 20;
     a.gates = gates; a.g_ld_m = g_ld_m; a.g_ld_t = g_ld_t;
-    const long long n = a.h_stride * ndir;                          // slot 0 = h0 = 0
-    const long long nz = n > SYNC_WORDS ? n : SYNC_WORDS;
-    hipLaunchKernelGGL(gru_zero_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, hq, n, sync);
     // 8 waves (K / 8 per wave) when K is a multiple of 256, else 4 waves (K / 4 per wave)
     const bool w8 = cvc_gru_waves8 && (H % 256) == 0;
     const int NC = w8 ? H / 256 : H / 128;
-#define CVC_GRU_P(NH_, MT_, NC_, NW_) return launch_persistent<NH_, MT_, NC_, NW_>(a, ndir, st)
+    // (slot 0 = h0 = 0 and the sync words are cleared by the launcher, once the launch is certain)
+#define CVC_GRU_P(NH_, MT_, NC_, NW_)                                                                                     \
+    return launch_resident(gru_persistent_kernel<NH_, MT_, NC_, NW_>, dim3(H / 8, ndir), NW_ * 64, a, hq, a.h_stride * ndir, sync, \
+                           SYNC_GROUPS, st)
 #define CVC_GRU_NC(NH_, MT_)                                                                                              \
     if (w8) {                                                                                                             \
         switch (NC) { case 1: CVC_GRU_P(NH_, MT_, 1, 8); case 2: CVC_GRU_P(NH_, MT_, 2, 8); case 3: CVC_GRU_P(NH_, MT_, 3, 8); \

@@ -24,13 +24,12 @@
 //     dh = dY_t + carried dh, dc carried through f) and dgates_t W_hh on the backward-data kernel (cvc_linear_nn_planes_fwd), as
 //     cvc_gru_seq_bwd does.  b_ih and b_hh enter the same sum, so ONE dG serves the input-side and the hidden-side products.
 #include "cvc_common.h"
-#include "gemm_split.h"
+#include "recurrence_sync.h"
+#include "recurrence_tile.h"
 
 namespace {
 
-// sync buffer: word SYNC_ERR = error flag; then one group of CNT arrival counters per direction, CNT_STRIDE words apart
-constexpr int CNT = 32, CNT_STRIDE = 1024, SYNC_ERR = 4;
-constexpr long long SYNC_WORDS = SYNC_ERR + 8 + 2LL * CNT * CNT_STRIDE;
+constexpr int SYNC_GROUPS = 2;                    // arrival counter groups (recurrence_sync.h): one per direction
 
 struct LstmArgs {
     const float* wp; long long w_stride;          // packed W_hh [ndir][H/8][Kp/4][32][4]
@@ -41,7 +40,7 @@ struct LstmArgs {
     float* y; long long y_ld_m, y_ld_t;
     float* gates; long long g_ld_m, g_ld_t;       // training: activated (i, f, g, o) of every step, columns [ndir][4][H]; nullable
     float* c; long long c_ld_m, c_ld_t;           // training: c_t of every step, columns [ndir][H]; nullable
-    unsigned* sync;                               // SYNC_WORDS words: error word + arrival counters
+    unsigned* sync;                               // sync_words(SYNC_GROUPS) words: error word + arrival counters
     unsigned spin_limit;
     // per-step form: this step's operands
     const float* h_in; float* h_out; float* c_q;  // quad layout [ndir][Kp/4][64][4] each
@@ -78,16 +77,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_persistent_kernel(LstmArgs a)
 
     // ---- this wave's share of the weights (chunks wave, wave + NW, ...), split once
     Split3 W[NC][2];
-    {
-        const float* wl = a.wp + (size_t)dir * a.w_stride + ((size_t)blk * nquad * 32 + i) * 4 + kh * 4 * 128;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float* w = wl + (size_t)(wave + NW * c) * 8 * 128;
-            const f32x4 q0 = ld4(w), q1 = ld4(w + 128), q2 = ld4(w + 256), q3 = ld4(w + 384);
-            W[c][0] = split8(q0, q1);
-            W[c][1] = split8(q2, q3);
-        }
-    }
+    load_weights<NC, NW>(W, a.wp + (size_t)dir * a.w_stride + ((size_t)blk * nquad * 32 + i) * 4 + kh * 4 * 128, wave);
 
     // ---- epilogue role: thread (em = clip, eqd = which 4 of the 8 hidden units); its cell state lives in `ecell` for all steps
     constexpr int ET = MT * 32, NT = NW * 64, NGI = (ET * 8 + NT - 1) / NT;
@@ -101,8 +91,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_persistent_kernel(LstmArgs a)
         const size_t col = (size_t)dir * 4 * H + (size_t)(tid >> 3) * H + blk * 8 + (tid & 7);
         sbias[tid] = a.b_ih[col] + a.b_hh[col];
     }
-    // arrivals are spread over CNT counters 4 KB apart (different memory channels)
-    unsigned* counter = a.sync + SYNC_ERR + 8 + (size_t)(dir * CNT) * CNT_STRIDE;
+    unsigned* counter = counter_group(a.sync, dir);
 
     if (tid == 0) gave_up = 0;
     __syncthreads();
@@ -126,94 +115,18 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_persistent_kernel(LstmArgs a)
 
         // ---- wait until every workgroup of this direction has published step s - 1
         if (s > 0) {
-            if (wave == 0) {                                           // lanes 0 .. CNT-1 read one counter each
-                const unsigned target = nblk * (unsigned)s;
-                unsigned it = 0;
-                for (;;) {
-                    unsigned v = lane < CNT ? __hip_atomic_load(counter + (size_t)lane * CNT_STRIDE, __ATOMIC_RELAXED,
-                                                                __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-                    for (int o = 1; o < CNT; o <<= 1) v += __shfl_xor(v, o, 64);
-                    v = __builtin_amdgcn_readfirstlane(v);             // one decision for the wave
-                    if (v >= target) break;
-                    if (++it > a.spin_limit || __hip_atomic_load(a.sync + SYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                        if (lane == 0) {
-                            __hip_atomic_store(a.sync + SYNC_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            gave_up = 1;                               // tell the workgroup
-                        }
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
+            if (wave == 0 && wait_arrivals(a.sync, counter, nblk * (unsigned)s, a.spin_limit, lane) && lane == 0)
+                gave_up = 1;                                           // tell the workgroup
             __syncthreads();                                           // (also: the previous step's readers of `red` are done)
             if (gave_up) return;                                       // no invalidate: slot s has never been read before
         }
 
-        // ---- partial tiles: this wave's K slice of the clip tiles.  The activations are requested in phases of (half of the
-        // wave's chunks) x (one 32-clip tile), two phases in flight; the schedule is pinned (see gru_persistent.hip)
+        // ---- partial tiles: this wave's K slice of the clip tiles
         f32x16 acc[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-        constexpr int HC = (NC + 1) / 2;                              // chunks per phase
-        const float* xl = hprev + (size_t)i * 4 + kh * 4 * 256;
-        f32x4 xb[2][HC][4];
-        auto load_phase = [&](f32x4 (&buf)[HC][4], const int half, const int mt) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < HC; ++j) {
-                const int c = half * HC + j;
-                if (c < NC) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) buf[j][q] = ld4(xl + (size_t)(wave + NW * c) * 8 * 256 + q * 256 + mt * 128);
-                }
-            }
-        };
-        auto mma_phase = [&](const f32x4 (&buf)[HC][4], const int half, f32x16& d) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < HC; ++j) {
-                const int c = half * HC + j;
-                if (c < NC) {
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const Split3 X = split8(buf[j][2 * s2], buf[j][2 * s2 + 1]);
-                        const Split3& Wc = W[c][s2];
-                        d = mfma_bf16(Wc.mid, X.mid, d);
-                        d = mfma_bf16(Wc.lo, X.hi, d);
-                        d = mfma_bf16(Wc.hi, X.lo, d);
-                        d = mfma_bf16(Wc.mid, X.hi, d);
-                        d = mfma_bf16(Wc.hi, X.mid, d);
-                        d = mfma_bf16(Wc.hi, X.hi, d);
-                    }
-                }
-            }
-        };
-        load_phase(xb[0], 0, 0);
-        load_phase(xb[1], 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_phase(xb[0], 0, acc[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MT == 2) load_phase(xb[0], 0, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma_phase(xb[1], 1, acc[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MT == 2) {
-            load_phase(xb[1], 1, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_phase(xb[0], 0, acc[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_phase(xb[1], 1, acc[1]);
-        }
+        tile_product<MT, NC, NW>(acc, W, hprev + (size_t)i * 4 + kh * 4 * 256, wave, [] {});
 
         // ---- ordered cross-wave sum, cell arithmetic
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-                red[(wave * 32 + row) * LDM + mt * 32 + i] = acc[mt][r];
-            }
+        spill_tiles<MT>((lds_float*)red, acc, wave, lane);
 #pragma unroll
         for (int k = 0; k < NGI; ++k) {
             const int it = tid + k * NT, gm = it % ET, gq = it / ET;
@@ -230,12 +143,7 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_persistent_kernel(LstmArgs a)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int row = g * 8 + eqd * 4 + e;
-                    float p = (red[(0 * 32 + row) * LDM + em] + red[(1 * 32 + row) * LDM + em]) +
-                              (red[(2 * 32 + row) * LDM + em] + red[(3 * 32 + row) * LDM + em]);
-                    if constexpr (NW == 8)
-                        p += (red[(4 * 32 + row) * LDM + em] + red[(5 * 32 + row) * LDM + em]) +
-                             (red[(6 * 32 + row) * LDM + em] + red[(7 * 32 + row) * LDM + em]);
-                    pre[g][e] = p + sgi[row * LDM + em];
+                    pre[g][e] = sum_waves<MT, NW>((const lds_float*)red, row, em) + sgi[row * LDM + em];
                 }
             lstm_cell4(pre, ecell, hv, act);
             if (a.gates != nullptr) {
@@ -244,46 +152,14 @@ __global__ __launch_bounds__(NW * 64, 1) void lstm_persistent_kernel(LstmArgs a)
                 for (int g = 0; g < 4; ++g) st4(gp + g * H, act[g]);
                 st4(a.c + (size_t)em * a.c_ld_m + t * a.c_ld_t + (size_t)dir * H + ejq, ecell);
             }
-            // the state goes straight through this XCD's L2 to memory (sc0 sc1) and is acknowledged before the arrival
-            // (inline assembly is invisible to the hazard recognizer: the s_nop covers "wide store, then a write to its data registers")
-            float* hp = hnext + eqoff;
-            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(hp), "v"(hv) : "memory");
+            store_through4(hnext + eqoff, hv);
             st4(a.y + (size_t)em * a.y_ld_m + t * a.y_ld_t + (size_t)dir * H + ejq, hv);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            drain_stores();
         }
         // ---- publish: one arrival per workgroup, after all of its state stores have been acknowledged
         __syncthreads();
-        if (tid == 0)
-            __hip_atomic_fetch_add(counter + (size_t)(blk % CNT) * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) arrive(counter, blk);
     }
-}
-
-// zeroes the first n floats of p (slot 0 = h0; the per-step form's whole workspace) and, when given, the sync words
-__global__ __launch_bounds__(256) void lstm_zero_kernel(float* p, long long n, unsigned* sync) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) p[t] = 0.f;
-    if (sync != nullptr && t < SYNC_WORDS) sync[t] = 0u;
-}
-
-template <int MT, int NC, int NW>
-int launch_persistent(LstmArgs& a, int ndir, hipStream_t st) {
-    const dim3 grid(a.H / 8, ndir);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)lstm_persistent_kernel<MT, NC, NW>, NW * 64, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return CVC_E_BADARG;
-    }
-    int devid = 0, cus = 0;
-    if (hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess)
-        return CVC_E_BADARG;
-    if ((long long)per_cu * cus < (long long)grid.x * grid.y) return CVC_E_BADARG;     // would not be co-resident
-    // slot 0 = h0 = 0, counters and error word cleared: only once the launch is certain (a refused call launches nothing)
-    const long long n = a.h_stride * ndir, nz = n > SYNC_WORDS ? n : SYNC_WORDS;
-    hipLaunchKernelGGL(lstm_zero_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, a.hq, n, a.sync);
-    // an ordinary launch (gru_persistent.hip explains why not a cooperative one): co-residency comes from the occupancy check and
-    // the stream's in-order execution; a grid that is not resident after all runs into the bounded spin and raises the error word
-    hipLaunchKernelGGL((lstm_persistent_kernel<MT, NC, NW>), grid, dim3(NW * 64), 0, st, a);
-    return cvc_launch_status();
 }
 
 // ---- per-step form: one launch per time step, grid (H / 8, ndir), 4 waves splitting K chunk by chunk (wave, wave + 4, ...)
@@ -332,35 +208,17 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmArgs a) {
             const f32x4 x0 = ld4(x), x1 = ld4(x + 256), x2 = ld4(x + 512), x3 = ld4(x + 768);
             const Split3 Xs[2] = {split8(x0, x1), split8(x2, x3)};
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                f32x16& d = acc[mt];
-                d = mfma_bf16(Ws[s2].mid, Xs[s2].mid, d);
-                d = mfma_bf16(Ws[s2].lo, Xs[s2].hi, d);
-                d = mfma_bf16(Ws[s2].hi, Xs[s2].lo, d);
-                d = mfma_bf16(Ws[s2].mid, Xs[s2].hi, d);
-                d = mfma_bf16(Ws[s2].hi, Xs[s2].mid, d);
-                d = mfma_bf16(Ws[s2].hi, Xs[s2].hi, d);
-            }
+            for (int s2 = 0; s2 < 2; ++s2) split_mma6(Ws[s2], Xs[s2], acc[mt]);
         }
     }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-            red[(wave * 32 + row) * LDM + mt * 32 + i] = acc[mt][r];
-        }
+    spill_tiles<MT>((lds_float*)red, acc, wave, lane);
     __syncthreads();
     if (ework) {
         f32x4 hv, act[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int row = g * 8 + eqd * 4 + e;
-                pre[g][e] += (red[(0 * 32 + row) * LDM + em] + red[(1 * 32 + row) * LDM + em]) +
-                             (red[(2 * 32 + row) * LDM + em] + red[(3 * 32 + row) * LDM + em]);
-            }
+            for (int e = 0; e < 4; ++e) pre[g][e] += sum_waves<MT, NW>((const lds_float*)red, g * 8 + eqd * 4 + e, em);
         lstm_cell4(pre, ecell, hv, act);
         st4(cq, ecell);
         st4(a.h_out + (size_t)dir * a.h_stride + eqoff, hv);
@@ -468,7 +326,10 @@ int persistent_impl(LstmArgs& a, int ndir, unsigned* sync, cvc_stream_t stream) 
     // 8 waves (K / 8 per wave) when K is a multiple of 256, else 4 waves (K / 4 per wave)
     const bool w8 = (H % 256) == 0;
     const int NC = w8 ? H / 256 : H / 128;
-#define CVC_LSTM_P(MT_, NC_, NW_) return launch_persistent<MT_, NC_, NW_>(a, ndir, st)
+    // (slot 0 = h0 = 0 and the sync words are cleared by the launcher, once the launch is certain)
+#define CVC_LSTM_P(MT_, NC_, NW_)                                                                                           \
+    return launch_resident(lstm_persistent_kernel<MT_, NC_, NW_>, dim3(H / 8, ndir), NW_ * 64, a, a.hq, a.h_stride * ndir, sync, \
+                           SYNC_GROUPS, st)
 #define CVC_LSTM_NC(MT_)                                                                                       \
     if (w8) {                                                                                                  \
         switch (NC) { case 1: CVC_LSTM_P(MT_, 1, 8); case 2: CVC_LSTM_P(MT_, 2, 8); case 3: CVC_LSTM_P(MT_, 3, 8); \
@@ -486,7 +347,7 @@ int steps_impl(LstmArgs& a, int ndir, cvc_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     // workspace hq: [2 h states + c][ndir][Kp/4][64][4], all zero at the start (h0 = c0 = 0; rows beyond M and the k padding stay 0)
     const long long one = a.h_stride * ndir, n = 3 * one;
-    hipLaunchKernelGGL(lstm_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.hq, n, (unsigned*)nullptr);
+    launch_clear(a.hq, n, nullptr, 0, st);
     a.c_q = a.hq + 2 * one;
     const dim3 grid(a.H / 8, ndir);
     for (int s = 0; s < a.F; ++s) {
@@ -501,7 +362,7 @@ int steps_impl(LstmArgs& a, int ndir, cvc_stream_t stream) {
 
 }  // namespace
 
-extern "C" int cvc_lstm_persistent_sync_words(void) { return (int)SYNC_WORDS; }
+extern "C" int cvc_lstm_persistent_sync_words(void) { return (int)sync_words(SYNC_GROUPS); }
 
 extern "C" int cvc_lstm_seq_persistent_fwd(const float* wp, const float* gi, long long gi_ld_m, long long gi_ld_t, const float* b_ih,
                                            const float* b_hh, int M, int F, int H, int ndir, float* hq, float* y, long long y_ld_m,

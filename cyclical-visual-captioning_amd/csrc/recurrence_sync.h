@@ -1,0 +1,103 @@
+// The cross-workgroup step protocol of the persistent recurrences (gru_persistent.hip, lstm_seq.hip, gru_bwd_persistent.hip).
+//
+// One launch runs a whole sequence; a workgroup owns 8 hidden units of one direction for all steps, and a step needs what
+// EVERY workgroup of its direction wrote in the step before.  The pieces, each defined here once:
+//   * every step's exchanged state has its OWN slot in memory: an address is written once, before the arrival, and first read
+//     after the wait, so no cache can hold a stale copy and no reader invalidates (the 8 XCDs' L2s are not coherent with each
+//     other, and invalidating them at every step costs more than the step);
+//   * the writers store straight through their L2 (store_through*), drain the stores (drain_stores), meet at a workgroup
+//     barrier and publish ONE arrival per workgroup (arrive);
+//   * wave 0 of a reader waits for the arrivals of all workgroups (wait_arrivals).  The spin is bounded: if a peer never
+//     arrives (not all workgroups resident) it raises the error word instead of hanging the GPU, and the host falls back to
+//     the per-step form;
+//   * the host launches the grid only when all of it can be resident (launch_resident).
+#pragma once
+#include "cvc_common.h"
+
+namespace {
+
+// sync buffer: word SYNC_ERR = error flag; then groups of CNT arrival counters, CNT_STRIDE words apart.  Arrivals are spread
+// over CNT counters 4 KB apart (different memory channels): 128 increments of ONE word queue up behind each other at the
+// memory-side atomic unit, and the last arrival is the one everybody waits for.
+constexpr int CNT = 32, CNT_STRIDE = 1024, SYNC_ERR = 4;
+constexpr long long sync_words(int groups) { return SYNC_ERR + 8 + (long long)groups * CNT * CNT_STRIDE; }
+
+__device__ __forceinline__ unsigned* counter_group(unsigned* sync, int group) {
+    return sync + SYNC_ERR + 8 + (size_t)(group * CNT) * CNT_STRIDE;
+}
+
+// Called by wave 0 (all 64 lanes): waits until the group's counters sum to `target`.  Returns true when the wait was given
+// up -- the spin limit ran out or a peer had already raised the error word -- with the error word raised; the caller hands
+// that to its workgroup through LDS.
+__device__ __forceinline__ bool wait_arrivals(unsigned* sync, const unsigned* counter, unsigned target, unsigned spin_limit, int lane) {
+    unsigned it = 0;
+    for (;;) {
+        unsigned v = lane < CNT ? __hip_atomic_load(counter + (size_t)lane * CNT_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                : 0u;                                  // lanes 0 .. CNT-1 read one counter each
+#pragma unroll
+        for (int o = 1; o < CNT; o <<= 1) v += __shfl_xor(v, o, 64);
+        v = __builtin_amdgcn_readfirstlane(v);                         // lane 0 holds the sum: one decision for the wave
+        if (v >= target) return false;
+        if (++it > spin_limit || __hip_atomic_load(sync + SYNC_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+            if (lane == 0) __hip_atomic_store(sync + SYNC_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return true;
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+}
+
+// One arrival per workgroup (one thread calls this), after all of its state stores have been acknowledged.
+__device__ __forceinline__ void arrive(unsigned* counter, int blk) {
+    __hip_atomic_fetch_add(counter + (size_t)(blk % CNT) * CNT_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The exchanged state goes straight through this XCD's L2 to memory (sc0 sc1): a release fence would instead walk the whole
+// L2 for dirty lines (buffer_wbl2) once per workgroup and step.  drain_stores waits for the acknowledgements; the workgroup
+// barrier and the arrival follow it.  (Inline assembly is invisible to the compiler's hazard recognizer: the s_nop covers
+// "store followed by a write to its data registers".)
+__device__ __forceinline__ void store_through4(float* p, const f32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void store_through1(float* p, const float v) {
+    asm volatile("global_store_dword %0, %1, off sc0 sc1\n\ts_nop 0" ::"v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// zeroes the first n floats of p and, when given, the first `words` words of sync
+__global__ __launch_bounds__(256) void recurrence_clear_kernel(float* p, long long n, unsigned* sync, long long words) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) p[t] = 0.f;
+    if (sync != nullptr && t < words) sync[t] = 0u;
+}
+inline void launch_clear(float* p, long long n, unsigned* sync, long long words, hipStream_t st) {
+    const long long nz = n > words ? n : words;
+    hipLaunchKernelGGL(recurrence_clear_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, p, n, sync, words);
+}
+
+// Launches a persistent recurrence kernel when its whole grid can be resident, after zeroing the first `nzero` floats of
+// `zero` (the initial state; nullable) and the `groups` counter groups and error word of `sync`.  CVC_E_BADARG, with nothing
+// launched and nothing written, when the grid would not be co-resident.
+//
+// An ORDINARY launch, not hipLaunchCooperativeKernel (round 6).  Co-residency is what the kernel needs, and the occupancy check
+// plus the stream's in-order execution give it (the grid is at most one workgroup per CU on an otherwise idle chip); what the
+// cooperative launch adds is a trip through the runtime's device-wide cooperative queue -- and with it a state of the runtime's
+// hardware queues in which, once any other stream capture has happened in the process, EVERY later kernel of the step took
+// 10 - 25 us longer (the captured end-to-end training step 91 -> 122 ms; tools/runs/r06_e2e_after_decode.py, GPU_MAX_HW_QUEUES
+// <= 2 or per-step GRU forms made it disappear).  A grid that is not resident after all is caught as before: the barrier's spin
+// is bounded and raises the error word (the caller falls back / the step is voided and re-run).
+template <typename Args>
+int launch_resident(void (*kernel)(Args), dim3 grid, int block, const Args& a, float* zero, long long nzero, unsigned* sync,
+                    int groups, hipStream_t st) {
+    int per_cu = 0, devid = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, block, 0) != hipSuccess ||
+        hipGetDevice(&devid) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess) {
+        (void)hipGetLastError();
+        return CVC_E_BADARG;
+    }
+    if ((long long)per_cu * cus < (long long)grid.x * grid.y) return CVC_E_BADARG;     // would not be co-resident
+    launch_clear(zero, nzero, sync, sync_words(groups), st);
+    hipLaunchKernelGGL(kernel, grid, dim3(block), 0, st, a);
+    return cvc_launch_status();
+}
+
+}  // namespace

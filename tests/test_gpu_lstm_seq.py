@@ -38,9 +38,14 @@ def want_form(H):
 
 
 # ---- 5, 6: inference, both forms
+# every instantiation of lstm_persistent_kernel<MT, NC, NW>: NC 1..4 at 8 waves (H % 256 == 0), NC 1, 3, 5, 7 at 4 waves, each at
+# MT 1 (32 clips) and MT 2 (33 clips)
+EVERY_INSTANTIATION = [(B, 3, 16, H, 1, True) for H in range(128, 1025, 128) for B in (32, 33)]
+
+
 @pytest.mark.parametrize("B,F,inp,H,layers,bidir", [(3, 5, 32, 16, 2, True), (64, 20, 256, 128, 2, True), (70, 7, 48, 128, 2, True),
                                                     (9, 11, 24, 40, 1, False), (33, 11, 100, 72, 2, True), (20, 33, 64, 384, 2, True),
-                                                    (64, 17, 96, 256, 1, False), (40, 9, 64, 512, 3, True)])
+                                                    (64, 17, 96, 256, 1, False), (40, 9, 64, 512, 3, True)] + EVERY_INSTANTIATION)
 def test_lstm_hip_vs_fp64(B, F, inp, H, layers, bidir):
     """lstm_forward in the form the shape selects and in the per-step form against the fp64 reference and against each other; more
     than 64 clips run in chunks; a second run of each form gives the same bits (fixed reduction order)."""
