@@ -41,6 +41,7 @@ const Entry table[] = {
     CVC_B(cvc_lstm_pointwise_bwd4_pair),
     CVC_B(cvc_beam_select_parts),
     CVC_B(cvc_sample_select_parts),
+    CVC_B(cvc_sample_select_trunc_parts),
     CVC_B(cvc_sample_advance),
     CVC_B(cvc_tile_lstm_finish),
     CVC_B(cvc_tile_lstm_finish_embgate),

@@ -39,7 +39,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def __init__(self, weights: DecodeWeights, feats: Dict[str, torch.Tensor], T: int, unk_idx: int, beam: int = 1,
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
-                 sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32"):
+                 sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
+                 top_k: int = 0, top_p: float = 1.0):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -59,6 +60,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         noise from the engine's own generator state {seed_lo, seed_hi, call, 0} (seed(); every decode first advances `call`).
         A sampling engine walks its launch list from Python (no C driver); beam > 1, gsk, gate_ksplit, lang_ksx and the packed
         path without the embedding-gate schedule are refused.
+        top_k, top_p: truncation of the sampled distribution (both need a temperature): top_k = k > 0 keeps the k
+        most likely words (and every word tied with the k-th), top_p = p < 1 then the smallest set of most likely words whose mass
+        under softmax(z / tau) over the kept words reaches p (nucleus sampling).  The word is the one the untruncated sampler draws
+        from the same state whenever that lies in the kept set; logprob stays the model's log-prob (full vocabulary -- not the
+        truncated distribution's).  A truncating engine owns self.cutoff [T, rows] (the smallest kept logit) and self.kept
+        [T, rows] (int32, the size of the kept set); 0 / 1.0 = off: the launch list of a temperature-only engine.
         weights_dtype: "fp32" (default) or "bf16" -- a precision setting, not a speed switch: the six weight matrices
         (BF16_ROUNDED_KEYS) are rounded to bf16 (nearest even) when the engine binds the checkpoint and stored as bf16 packs
         (the WB16 mode of csrc/gemm_packed.hip: half the weight bytes per step, three MFMAs per product instead of six); the decode computes
@@ -89,6 +96,14 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                                    f"(beam = 1, one caption per clip, <= 64 rows); refused: {why}")
             gsk, gate_ksplit, lang_ksx = False, False, False
         self.sampling = temperature is not None
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
+            raise RuntimeError(f"DecodeEngine: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+        if not (0.0 < float(top_p) <= 1.0):
+            raise RuntimeError(f"DecodeEngine: top_p must lie in (0, 1] (1 = off), got {top_p!r}")
+        self.top_k, self.top_p = int(top_k), float(top_p)
+        self.trunc = self.top_k > 0 or self.top_p < 1.0
+        if self.trunc and not self.sampling:
+            raise RuntimeError("DecodeEngine: top_k / top_p truncate the sampled distribution: they need a sampling temperature")
         if self.sampling:
             tau = float(temperature)
             if not (0.0 < tau < float("inf")):
@@ -151,6 +166,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.sampling:
             self.rng = torch.zeros(4, device=dev, dtype=torch.int32)          # {seed_lo, seed_hi, call, 0} (uint32 bit patterns)
             self.seed(0 if seed is None else seed)
+        if self.trunc:
+            self.cutoff = z(self.T, rows)                                     # min over the kept set of z, per step and row
+            self.kept = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)
         if self.beam > 1:
             self.score = z(2, rows)
             self.done = torch.zeros(2, rows, dtype=torch.uint8, device=dev)
@@ -373,6 +391,17 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             out.insert(0, ("sample_advance", hip.lib().cvc_sample_advance, (self.rng.data_ptr(),)))
         return out
 
+    def _word_select_sampled(self, t, parts, nparts, part_stride, bias):
+        """The sampling paths' word_select launch of step t over logits parts[0] + ... (+ bias): the plain block, or the
+        truncating one (top_k / top_p are launch constants: they live in the captured graph)."""
+        L, rows, V = hip.lib(), self.rows, self.W.V
+        head = (parts, nparts, part_stride, bias, rows, V, self.unk, self.inv_tau)
+        tail = (self.rng.data_ptr(), t, self.words[t + 1].data_ptr(), 1, self.logprob[t].data_ptr())
+        if not self.trunc:
+            return ("word_select", L.cvc_sample_select_parts, head + tail)
+        return ("word_select", L.cvc_sample_select_trunc_parts, head + (self.top_k, self.top_p) + tail +
+                (self.cutoff[t].data_ptr(), self.kept[t].data_ptr()))
+
     def _python_launches(self):
         if self._launches is None:
             self._keep = []
@@ -409,7 +438,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode

@@ -190,9 +190,7 @@ class PackedPath:
             if self.sampling:
                 # row-major logits, then the sampling block (the attention cell of step t + 1 reads the word from words[t + 1])
                 out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V, None)))
-                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
-                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
-                                                                       ptr(self.logprob[t]))))
+                out.append(self._word_select_sampled(t, ptr(self.logits), 1, 0, None))
             else:
                 out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V, ptr(self.top2_part))))
                 out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,

@@ -69,9 +69,7 @@ class RingPath:
             if sampling:
                 # finished logits, the sampling block, then next step's embedded word relu(Emb[word])
                 out.append(("logits", L.cvc_linear_fwd, (seg_o, 1, ptr(W.b_o), None, rows, V, ptr(self.logits), V)))
-                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.logits), 1, 0, None, rows, V, self.unk, self.inv_tau,
-                                                                       ptr(self.rng), t, ptr(self.words[t + 1]), 1,
-                                                                       ptr(self.logprob[t]))))
+                out.append(self._word_select_sampled(t, ptr(self.logits), 1, 0, None))
                 if t + 1 < self.T:
                     out.append(("embed", L.cvc_embed_relu_fwd, (ptr(W.embed), ptr(self.words[t + 1]), None, rows, E, ptr(self.emb))))
             elif fused_head:

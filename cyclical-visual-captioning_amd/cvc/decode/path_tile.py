@@ -125,9 +125,7 @@ class TilePath:
                                                                         ptr(self.logits), V)))
             if self.sampling:
                 # the sampling block sums the K-slice slabs itself, in the finishing pass's order
-                out.append(("word_select", L.cvc_sample_select_parts, (ptr(self.parts_o), self.ks_o, rows * V, ptr(W.b_o), rows, V,
-                                                                       self.unk, self.inv_tau, ptr(self.rng), t,
-                                                                       ptr(self.words[t + 1]), 1, ptr(self.logprob[t]))))
+                out.append(self._word_select_sampled(t, ptr(self.parts_o), self.ks_o, rows * V, ptr(W.b_o)))
                 parent = None
             elif beam == 1:
                 out.append(("word_select", L.cvc_top2_unk, (ptr(self.logits), rows, V, self.unk, ptr(self.words[t + 1]), 1,

@@ -31,7 +31,7 @@ LAST_TRAINER = None
 
 
 def main(argv=None, sample=None):
-    """sample: (n, temperature, seed) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    """sample: (n, temperature, seed) or (n, temperature, seed, top_k, top_p) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample)."""
     parser = cvc_opts.build_parser()
     parser.add_argument("--synthetic_clips", type=int, default=128)
@@ -128,7 +128,7 @@ def main(argv=None, sample=None):
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
-        path = trainer.sample(*sample)
+        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
         if comm is not None:

@@ -96,6 +96,9 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.sample_temperature = float(getattr(opts, "temperature", 1.0))
         self.sample_n = int(getattr(opts, "sample_n", 1))
         self.sample_seed = int(getattr(opts, "sample_seed", 0))
+        # truncation of the sampled distribution (DecodeEngine top_k / top_p; 0 / 1.0 = off)
+        self.sample_top_k = int(getattr(opts, "top_k", 0))
+        self.sample_top_p = float(getattr(opts, "top_p", 1.0))
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
         self.decode_weights_dtype = getattr(opts, "decode_weights", "fp32")
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
@@ -457,12 +460,15 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
     @torch.no_grad()
     def _sample(self, segs_feat, seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats, frm_mask, sample_idx,
                 pnt_mask, beam_size: Optional[int] = None, sample_max: Optional[int] = None, temperature: Optional[float] = None,
-                sample_n: Optional[int] = None, seed: Optional[int] = None, decode_weights: Optional[str] = None):
+                sample_n: Optional[int] = None, seed: Optional[int] = None, decode_weights: Optional[str] = None,
+                top_k: Optional[int] = None, top_p: Optional[float] = None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
         UNK, sample_n captions per clip -> (seq [B*n, T], att2_weights [B*n, T, N], logprob [B*n, T]), row b * n + j = sample j of
         clip b.  The sampling engine is seeded once, when it is created (seed); later batches draw fresh noise.
+        top_k / top_p (arguments, else the model's sample_top_k / sample_top_p): top-k / nucleus truncation of the sampled
+        distribution (DecodeEngine); logprob stays the model's log-prob over the full vocabulary.
         decode_weights: "fp32" / "bf16" (argument, else the model's opts.decode_weights): DecodeEngine's weights_dtype; what the
         bf16 mode does not cover (beam search, sample_n > 1, more than 64 rows) raises, it never decodes in fp32 instead."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
@@ -475,12 +481,14 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         tau = (self.sample_temperature if temperature is None else float(temperature)) if sampling else None
         n = (self.sample_n if sample_n is None else int(sample_n)) if sampling else 1
         s_seed = (self.sample_seed if seed is None else int(seed)) if sampling else None
+        k = (self.sample_top_k if top_k is None else int(top_k)) if sampling else 0
+        p = (self.sample_top_p if top_p is None else float(top_p)) if sampling else 1.0
         wdtype = self.decode_weights_dtype if decode_weights is None else decode_weights
         weights = self.decode_weights()
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype)
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p)
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -493,7 +501,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 engine.load_features(feats)
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
-                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype)
+                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)

@@ -3,8 +3,9 @@
 temperature) without UNK, written to <results_dir>/densecap-<val_split>-<id>_samples.json (Trainer.sample).
 
   python -m cvc.sample --temperature 0.7 --sample_n 5 --sample_seed 1 --path_opt cfgs/cyclical.yml --resume True --id my_run
+  python -m cvc.sample --temperature 1.0 --top_k 40 --top_p 0.9 ...      (top-k, then nucleus truncation of the distribution)
 
---temperature / --sample_n / --sample_seed are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
+--temperature / --sample_n / --sample_seed / --top_k / --top_p are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
 --resume with --load_best_score: the same checkpoint loading as an --inference_only evaluation).
 """
 from __future__ import annotations
@@ -15,19 +16,31 @@ import sys
 from . import main as cvc_main
 
 
-def main(argv=None):
+def parse(argv=None):
+    """-> (this module's own flags, the rest for cvc.main)"""
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, add_help=False)
     p.add_argument("--temperature", type=float, default=1.0, help="sampling temperature tau > 0 (not --softmax_temp, the attention's)")
     p.add_argument("--sample_n", type=int, default=5, help="captions per segment")
     p.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling noise")
+    p.add_argument("--top_k", type=int, default=0, help="keep the k most likely words (and ties with the k-th); 0 = off")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus: keep the most likely words up to mass p in (0, 1]; 1 = off")
     own, rest = p.parse_known_args(argv)
     if not own.temperature > 0:
         raise SystemExit("--temperature must be > 0")
     if own.sample_n < 1:
         raise SystemExit("--sample_n must be >= 1")
+    if own.top_k < 0:
+        raise SystemExit("--top_k must be >= 0")
+    if not 0 < own.top_p <= 1:
+        raise SystemExit("--top_p must lie in (0, 1]")
+    return own, rest
+
+
+def main(argv=None):
+    own, rest = parse(argv)
     if "--inference_only" not in rest:
         rest = rest + ["--inference_only"]
-    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed))
+    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p))
 
 
 if __name__ == "__main__":

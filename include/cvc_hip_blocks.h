@@ -139,6 +139,23 @@ int cvc_sample_select_parts(const float* parts, int nparts, long long part_strid
                             float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
                             cvc_stream_t stream);
 int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream);
+/* The same with top-k / nucleus (top-p) truncation: z, s, the noise, the hash counters and logprob are those of
+ * cvc_sample_select_parts; the arg-max runs over a candidate set C2 only.
+ *   C0 = { v < V, v != unk_idx }
+ *   C1 = { v in C0 : z[v] >= theta_k }, theta_k = the top_k-th largest z over C0, with multiplicity (top_k = 0 or >= |C0|: C1 = C0);
+ *        words tied with the top_k-th value are all kept: |C1| may exceed top_k, the set depends on the values only
+ *   C2 = { v in C1 : z[v] >= theta_p }, theta_p = the largest z occurring in C1 with mass(theta_p) >= top_p * mass(-inf), where
+ *        mass(theta) = sum over v in C1 with z[v] >= theta of expf((z[v] - max_C1 z) * inv_tau), fp32, fixed order (top_p = 1: C2 = C1)
+ *   word[r * word_stride] = argmax over v in C2 of s: the word cvc_sample_select_parts draws from the same state, if that lies in C2
+ *   logprob[r] = the model's log-prob of the word (full V, independent of tau, top_k, top_p; NOT the truncated distribution's)
+ *   cutoff[r] = min over C2 of z, kept[r] = |C2| (both nullable)
+ * top_k < 0, top_p outside (0, 1] or not finite: CVC_E_BADARG.  Truncation off (top_k == 0 or >= V - 1, and top_p == 1): the
+ * plain kernel is launched (same bits as cvc_sample_select_parts), cutoff / kept are filled from C0 if given.  Bitwise
+ * deterministic. */
+int cvc_sample_select_trunc_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
+                                  int unk_idx, float inv_tau, int top_k, float top_p, const uint32_t* rng_state, int t,
+                                  int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
+                                  cvc_stream_t stream);
 int cvc_tile_lstm_finish(const float* parts, int nparts, long long part_stride, const float* b_ih, const float* b_hh,
                          const float* gate_bias, int gb_div, const float* c_prev, int M, int R, float* c_out,
                          float* h_out, void* frag1, long long frag1_stride, void* frag2, long long frag2_stride,
