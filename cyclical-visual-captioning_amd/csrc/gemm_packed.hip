@@ -1075,6 +1075,7 @@ extern "C" int cvc_packed_linear_fwd(const float* wp, const float* xq, int K, co
                                      int ksplit, float* y, int ldy, float* top2_part, cvc_stream_t stream) {
     if (!wp || !xq || (K & 31) || Nout < 1 || ksplit < 1 || (!y && !top2_part)) return CVC_E_BADARG;
     if (ksplit > 1 && top2_part != nullptr) return CVC_E_BADARG;
+    if (y != nullptr && ldy < Nout) return CVC_E_BADARG;          // (rows would overlap, the last one end past M * ldy)
     PackedArgs a{};
     a.wp = wp; a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = Nout; a.R = 0;
     a.bias = bias; a.y = y; a.ldy = ldy; a.ksplit = ksplit; a.split_stride = (long long)M * ldy; a.top2_part = top2_part;

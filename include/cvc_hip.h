@@ -139,7 +139,7 @@ CVC_API int cvc_linear_fwd(const cvc_gemm_seg* segs, int nsegs, const float* bia
  *        cvc_attn_wsum_quad, cvc_top2_final with emb_ld == 0).
  * K % 32 == 0, M <= 64.  LSTM: cell state c in quad layout [R/4][64][4]; h' goes to up to two quad
  * destinations (the next consumers' K ranges).  Linear: y row-major (split-K slices at stride
- * M*ldy, bias in slice 0) and/or the fused word-selection partials (see cvc_linear_top2_fwd). */
+ * M*ldy, bias in slice 0; ldy >= Nout) and/or the fused word-selection partials (see cvc_linear_top2_fwd). */
 /* Embedding-gate table form of the att-LSTM (decoder_core.py:45-50 with xt = relu(Emb[word]), captioner.py:53-68 in eval mode):
  * the embedded word's share of the gates, W_ih[:, emb columns] x relu(Emb[v]), depends on the word alone, so it is tabulated once
  * per checkpoint -- emb_gate [V][4R] fp32, gates in checkpoint order (gate * R + unit; cvc.decode.embgate_table) -- and the
