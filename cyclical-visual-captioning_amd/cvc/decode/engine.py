@@ -40,7 +40,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
-                 top_k: int = 0, top_p: float = 1.0):
+                 top_k: int = 0, top_p: float = 1.0, forced_n: int = 0):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -72,19 +72,39 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         what the fp32 engine computes on a checkpoint that holds the rounded values -- activations, state, accumulation, softmax
         and word selection stay fp32.  Packed path with the embedding-gate schedule only (greedy or sampling with sample_n = 1,
         <= 64 rows); the engine walks its launch list from Python (no C driver) and capture() turns it into a HIP graph.  Every
-        other configuration is refused with a RuntimeError -- the mode never runs in fp32 instead."""
+        other configuration is refused with a RuntimeError -- the mode never runs in fp32 instead.
+        forced_n: 0 = off.  n >= 1: the teacher-forced mode -- the engine chooses no word, it follows n given
+        captions per clip (load_captions(); row b * n + j is caption j of clip b) and the selection block cvc_forced_select_parts
+        writes the given word's log-prob (self.logprob [T, rows]) and its rank among the logits (self.rank [T, rows] int32).  The
+        launch lists are the sampling paths' with that block as word_select, on the same choice of paths with the same refusals
+        (beam > 1, a temperature, gsk, gate_ksplit, lang_ksx, the packed path without the embedding-gate schedule); no C driver.
+        With a frame mask bound (load_captions) the region attention also writes its frame-masked pre-softmax scores per step
+        (self.fm_steps [T, rows, N]): the att2_weights of the training pass, what grounding on given sentences reads."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
             raise RuntimeError(f"DecodeEngine: weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
         self.weights_dtype = weights_dtype
         self.bf16w = weights_dtype == "bf16"
+        if isinstance(forced_n, bool) or not isinstance(forced_n, (int, np.integer)) or forced_n < 0:
+            raise RuntimeError(f"DecodeEngine: forced_n must be an integer >= 0 (0 = off), got {forced_n!r}")
+        self.forced = int(forced_n) >= 1
+        if self.forced:
+            if self.beam != 1:
+                raise RuntimeError("DecodeEngine: the forced mode (forced_n) and beam search (beam > 1) exclude each other")
+            if temperature is not None:
+                raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no sampling temperature")
+            if gsk or gate_ksplit or lang_ksx:
+                raise RuntimeError("DecodeEngine: the forced mode runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
+            gate_ksplit, lang_ksx = False, False
         if self.bf16w:
             why = None
             if self.beam != 1:
                 why = f"beam search (beam = {self.beam}) runs on the tile path"
             elif int(sample_n) != 1:
                 why = f"sample_n = {sample_n} > 1 runs on the tile path"
+            elif int(forced_n) > 1:
+                why = f"forced_n = {forced_n} > 1 runs on the tile path"
             elif path in ("tile", "ring"):
                 why = f'path="{path}" was asked for'
             elif gsk or gate_ksplit or lang_ksx:
@@ -96,6 +116,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                                    f"(beam = 1, one caption per clip, <= 64 rows); refused: {why}")
             gsk, gate_ksplit, lang_ksx = False, False, False
         self.sampling = temperature is not None
+        # the next step's word is read from words[t + 1] (sampled there by the selection block, or given): the sampling launch lists
+        self.given = self.sampling or self.forced
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
             raise RuntimeError(f"DecodeEngine: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
         if not (0.0 < float(top_p) <= 1.0):
@@ -119,13 +141,18 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         elif int(sample_n) != 1:
             raise RuntimeError("DecodeEngine: sample_n > 1 needs a sampling temperature")
         # queries per clip: the beams of beam search, the samples of sampled decoding (attention passes, gate_fc rows)
-        self.nq = int(sample_n) if self.sampling else self.beam
+        self.nq = int(sample_n) if self.sampling else (int(forced_n) if self.forced else self.beam)
         fc, conv, pconv = feats["fc_feats"], feats["conv_feats"], feats["p_conv_feats"]
         pool, ppool = feats["pool_feats"], feats["p_pool_feats"]
         mask = feats["pnt_mask"][:, 1:] if feats["pnt_mask"].shape[1] == pool.shape[1] + 1 else feats["pnt_mask"]
         self.B, self.N, self.F = pool.shape[0], pool.shape[1], conv.shape[1]
         B, N, Fr, R, A, V = self.B, self.N, self.F, W.R, W.A, W.V
         dev = pool.device
+        # the packed path: one query per clip, at most 64 rows, widths the fragment layouts take
+        packed = self.nq == 1 and B * self.nq <= 64 and path != "tile" and R % 32 == 0 and W.E % 32 == 0 and A % 32 == 0
+        if self.forced and packed and embgate is not None and not embgate:              # (before anything is copied or allocated)
+            raise RuntimeError("DecodeEngine: the forced mode on the packed path needs the embedding-gate schedule (the attention "
+                               "cell reads the word from words[t])")
         if self.bf16w and (B * self.nq > 64 or R % 32 or W.E % 32 or A % 32):          # (before anything is copied or allocated)
             raise RuntimeError(f'DecodeEngine: weights_dtype="bf16" covers the packed path only: at most 64 rows and R, E, A '
                                f"multiples of 32 (got {B * self.nq} rows, R = {R}, E = {W.E}, A = {A})")
@@ -166,6 +193,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.sampling:
             self.rng = torch.zeros(4, device=dev, dtype=torch.int32)          # {seed_lo, seed_hi, call, 0} (uint32 bit patterns)
             self.seed(0 if seed is None else seed)
+        if self.forced:
+            self.rank = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)      # rank of the given word among the row's logits
+            self.fmask = self.fm_steps = None                                          # bound by load_captions(frame_mask=...)
         if self.trunc:
             self.cutoff = z(self.T, rows)                                     # min over the kept set of z, per step and row
             self.kept = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)
@@ -180,7 +210,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
-        self.packed = self.nq == 1 and rows <= 64 and path != "tile" and R % 32 == 0 and W.E % 32 == 0 and A % 32 == 0
+        self.packed = packed
         # packed path: K-split gate GEMMs (activations shared through LDS, csrc/gemm_packed_ks.hip) where the shape allows
         # (True: partial tiles + a finishing launch; "fused": the last-arriving K slice of a tile finishes it in the same launch)
         self.gate_ksplit = GATE_KSPLIT_DEFAULT if gate_ksplit is None else gate_ksplit
@@ -196,9 +226,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if embgate and not eg_ok:
             raise RuntimeError("DecodeEngine: the embedding-gate schedule needs the packed path (without gsk / gate_ksplit) or the tile path")
         self.embgate = (eg_ok and 4 * V * 4 * R <= EMBGATE_MAX_BYTES) if embgate is None else bool(embgate)
-        if self.sampling and self.packed and not self.embgate:
-            raise RuntimeError("DecodeEngine: sampling on the packed path needs the embedding-gate schedule (the attention cell reads "
-                               "the sampled word from words[t])")
+        if self.given and self.packed and not self.embgate:
+            raise RuntimeError(f"DecodeEngine: {'sampling' if self.sampling else 'the forced mode'} on the packed path needs the "
+                               "embedding-gate schedule (the attention cell reads the word from words[t])")
         # what stays in the Infinity Cache between steps: small linear weights, then (embedding-gate schedule on the packed path) the
         # attention cell's gate matrix over K = 2R if it fits, then the largest subset of the feature tensors
         if self.bf16w and not (self.packed and self.embgate):
@@ -234,7 +264,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         elif self.tile:
             self._alloc_tile()
         self._launches = self._build_launches()
-        if driver and not self.sampling and not self.bf16w and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
+        if driver and not self.given and not self.bf16w and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
 
     # ------------------------------------------------------------------ C-ABI decode driver (csrc/decode_driver.hip)
@@ -364,6 +394,47 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.mask.copy_(hip._mask(mask))
         return self
 
+    def load_captions(self, words: torch.Tensor, frame_mask: Optional[torch.Tensor] = None):
+        """Forced mode: the captions to follow, words [B * n, T] int64 (row b * n + j = caption j of clip b), copied into the
+        engine-owned words[1:] (words[0] stays BOS) -- a stream-ordered copy, so a captured graph is reused across batches as
+        load_features() does it.  frame_mask [T, B * n, N] (uint8 / bool, non-zero = the proposal lies outside the word's frames):
+        copied into the engine-owned mask; from the first such call on the region attention of step t also writes fm_steps[t], its
+        pre-softmax scores with the fill value at the masked proposals.  The mask changes the launch list, so it has to be bound
+        before capture(); None on an engine that has one clears it (fm_steps = the unmasked scores)."""
+        if not self.forced:
+            raise RuntimeError("DecodeEngine.load_captions: this engine is not in the forced mode (forced_n = 0)")
+        if tuple(words.shape) != (self.rows, self.T) or words.dtype != torch.int64:
+            raise RuntimeError(f"DecodeEngine.load_captions: words must be int64 [{self.rows}, {self.T}], got {words.dtype} "
+                               f"{tuple(words.shape)}")
+        if frame_mask is not None:
+            if tuple(frame_mask.shape) != (self.T, self.rows, self.N):
+                raise RuntimeError(f"DecodeEngine.load_captions: frame_mask has shape {tuple(frame_mask.shape)}, expected "
+                                   f"{(self.T, self.rows, self.N)}")
+            if self.fmask is None:
+                if self.graph is not None:
+                    raise RuntimeError("DecodeEngine.load_captions: the captured graph has no frame-masked output; bind the first "
+                                       "frame mask before capture()")
+                dev = self.words.device
+                self.fmask = torch.zeros(self.T, self.rows, self.N, dtype=torch.uint8, device=dev)
+                self.fm_steps = torch.zeros(self.T, self.rows, self.N, dtype=torch.float32, device=dev)
+                self._launches = None                   # rebuilt on demand with the mask in the region set
+            self.fmask.copy_(hip._mask(frame_mask))
+        elif self.fmask is not None:
+            self.fmask.zero_()
+        self.words[1:].copy_(words.t())
+        return self
+
+    def _region_set(self, t):
+        """The region feature set of step t's attention passes; the forced mode with a frame mask bound adds the mask and the
+        frame-masked output of that step."""
+        fc, conv, pconv, pool, ppool = self.feats
+        ptr = lambda x: None if x is None else x.data_ptr()
+        fm_in = fm_out = None
+        if self.forced and self.fmask is not None:
+            fm_in, fm_out = ptr(self.fmask[t]), ptr(self.fm_steps[t])
+        return hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), fm_in, ptr(self.scores_r), fm_out, ptr(self.att_steps[t]), None,
+                           self.N, self.stream_r)
+
     def bind_features(self, feats: Dict[str, torch.Tensor]):
         """Next batch of the same shape WITHOUT copying it: the C-ABI plan (and this engine) is pointed at the caller's
         feature tensors.  Only for engines that run through the driver without a captured graph (a graph keeps the pointers it
@@ -393,8 +464,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
 
     def _word_select_sampled(self, t, parts, nparts, part_stride, bias):
         """The sampling paths' word_select launch of step t over logits parts[0] + ... (+ bias): the plain block, or the
-        truncating one (top_k / top_p are launch constants: they live in the captured graph)."""
+        truncating one (top_k / top_p are launch constants: they live in the captured graph); the forced mode: the block that
+        scores the given word words[t + 1] and writes none."""
         L, rows, V = hip.lib(), self.rows, self.W.V
+        if self.forced:
+            return ("word_select", L.cvc_forced_select_parts, (parts, nparts, part_stride, bias, rows, V, self.words[t + 1].data_ptr(), 1,
+                                                               self.logprob[t].data_ptr(), self.rank[t].data_ptr()))
         head = (parts, nparts, part_stride, bias, rows, V, self.unk, self.inv_tau)
         tail = (self.rng.data_ptr(), t, self.words[t + 1].data_ptr(), 1, self.logprob[t].data_ptr())
         if not self.trunc:
@@ -438,7 +513,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
@@ -468,13 +543,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def run(self):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
         engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],
-        logprob [B*n, T]), row b * n + j = sample j of clip b."""
+        logprob [B*n, T]), row b * n + j = sample j of clip b.  Forced mode: (seq = the given words, att2_weights, logprob,
+        rank [B*n, T] int32), row b * n + j = caption j of clip b."""
         if self.graph is not None:
             self.graph.replay()
         else:
             self._run_once()
             if self.lang_ksx and not self._ksx_checked and self.check_ksx():
                 self._run_once()                           # the fallback's results
+        if self.forced:
+            return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t(), self.rank.t()
         if self.sampling:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t()
         if self.beam == 1:

@@ -163,8 +163,7 @@ class PackedPath:
                                              1 if self.att_w_cached else 0)))
             out.append(("h2attn", linear_fn, (ptr(w_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT, ptr(self.q_parts), A, None)))
             sets = (hip.AttnSet * 2)()
-            sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
-                                  ptr(self.att_steps[t]), None, N, self.stream_r)
+            sets[0] = self._region_set(t)
             sets[1] = hip.AttnSet(ptr(pconv), ptr(conv), None, None, ptr(self.scores_f), None, ptr(self.attn_f), None, Fr,
                                   self.stream_f)
             out.append(("attn_scores", L.cvc_attn_scores_qparts, (W.kind, ptr(self.q_parts), self.QSPLIT, ptr(W.b_h), ptr(W.w_a),
@@ -187,8 +186,8 @@ class PackedPath:
                                                                  ptr(self.cL[wr]))))
             # (cvc_packed_linear_select_fwd, the one-launch form whose last workgroup merges the records, measured 34.9 us against
             # 20.0 + 7.4 us for these two launches: atomics, fence and a serial merge on one CU cost more than a launch boundary)
-            if self.sampling:
-                # row-major logits, then the sampling block (the attention cell of step t + 1 reads the word from words[t + 1])
+            if self.given:
+                # row-major logits, then the sampling / forced block (the attention cell of step t + 1 reads the word from words[t + 1])
                 out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V, None)))
                 out.append(self._word_select_sampled(t, ptr(self.logits), 1, 0, None))
             else:

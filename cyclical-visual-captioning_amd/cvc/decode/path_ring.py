@@ -17,7 +17,7 @@ class RingPath:
     def _build(self):
         L, W = hip.lib(), self.W
         B, N, Fr, R, A, E, V, rows, beam = self.B, self.N, self.F, W.R, W.A, W.E, W.V, self.rows, self.beam
-        nq, sampling = self.nq, self.sampling          # queries per clip (beams or samples)
+        nq, sampling = self.nq, self.given             # queries per clip (beams, samples or given captions); words read from words[t]
         fc, conv, pconv, pool, ppool = self.feats
         ptr = lambda t: None if t is None else t.data_ptr()
         out = []
@@ -48,8 +48,7 @@ class RingPath:
             else:
                 out.append(("h2attn", L.cvc_linear_fwd, (seg_q, 1, ptr(W.b_h), None, rows, A, ptr(self.q), A)))
             sets = (hip.AttnSet * 2)()
-            sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
-                                  ptr(self.att_steps[t]), None, N, self.stream_r)
+            sets[0] = self._region_set(t)
             sets[1] = hip.AttnSet(ptr(pconv), ptr(conv), None, None, ptr(self.scores_f), None, ptr(self.attn_f), None, Fr,
                                   self.stream_f)
             if split_q:

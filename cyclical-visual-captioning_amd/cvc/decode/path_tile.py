@@ -100,8 +100,7 @@ class TilePath:
                                                                    ptr(self.t_c_att), ptr(self.t_h_att), xl_hatt, xl_s, None, 0)))
             out.append(("h2attn", L.cvc_tile_gemm, (ptr(W.t_h), xl_hatt, xl_s, R, rows, A, self.ks_q, ptr(self.parts_q), A, rows * A)))
             sets = (hip.AttnSet * 2)()
-            sets[0] = hip.AttnSet(ptr(ppool), ptr(pool), ptr(self.mask), None, ptr(self.scores_r), None,
-                                  ptr(self.att_steps[t]), None, N, self.stream_r)
+            sets[0] = self._region_set(t)
             sets[1] = hip.AttnSet(ptr(pconv), ptr(conv), None, None, ptr(self.scores_f), None, ptr(self.attn_f), None, Fr,
                                   self.stream_f)
             # the query slabs are summed ONCE here: every one of a clip's ~19 score workgroups would otherwise re-sum
@@ -120,11 +119,11 @@ class TilePath:
             # beams: the selection sums the K-slice slabs itself (in the finishing pass's order: same logits bit for bit), the
             # finished [rows, V] matrix is neither written nor read back; CVC_BEAM_FINISH=1 keeps the separate pass (A/B)
             fused_sel = beam > 1 and self.ks_o in (2, 4, 6, 8) and V % 4 == 0 and os.environ.get("CVC_BEAM_FINISH") != "1"
-            if not fused_sel and not self.sampling:
+            if not fused_sel and not self.given:
                 out.append(("logits_finish", L.cvc_tile_linear_finish, (ptr(self.parts_o), self.ks_o, rows * V, V, ptr(W.b_o), None, rows, V,
                                                                         ptr(self.logits), V)))
-            if self.sampling:
-                # the sampling block sums the K-slice slabs itself, in the finishing pass's order
+            if self.given:
+                # the sampling / forced block sums the K-slice slabs itself, in the finishing pass's order
                 out.append(self._word_select_sampled(t, ptr(self.parts_o), self.ks_o, rows * V, ptr(W.b_o)))
                 parent = None
             elif beam == 1:

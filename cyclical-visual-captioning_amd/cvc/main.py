@@ -8,6 +8,7 @@ gradient all-reduce instead of nn.DataParallel; the dataset is the synthetic sta
 """
 from __future__ import annotations
 
+import json
 import os
 import pickle
 import random
@@ -30,9 +31,11 @@ from .trainer import Trainer, build_optimizer
 LAST_TRAINER = None
 
 
-def main(argv=None, sample=None):
+def main(argv=None, sample=None, score=None):
     """sample: (n, temperature, seed) or (n, temperature, seed, top_k, top_p) -- set up as for evaluation (checkpoint loading included), then write the validation split's
-    sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample)."""
+    sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
+    score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
+    (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
     parser = cvc_opts.build_parser()
     parser.add_argument("--synthetic_clips", type=int, default=128)
     parser.add_argument("--decode_weights", choices=("fp32", "bf16"), default="fp32",
@@ -131,6 +134,15 @@ def main(argv=None, sample=None):
         path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
+        if comm is not None:
+            destroy_exchange_comm()
+        return 0
+    if score is not None:
+        stats = trainer.score()
+        if score.get("ground_gt"):
+            stats.update(trainer.ground_gt())
+        if rank == 0:
+            print("scores written to %s: %s" % (trainer.scores_file, json.dumps(stats)))
         if comm is not None:
             destroy_exchange_comm()
         return 0

@@ -455,6 +455,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         a HIP-graph replay of the training step, or a fused optimizer kernel (Trainer calls this after every step)."""
         self._decode_cache = None
         self._engine_cache = None
+        self._score_cache = None
         hip.bump_weights_generation()            # the encoder's packed GRU / dense operands are keyed on it (cvc/gru.py, cvc/dense.py)
 
     @torch.no_grad()
@@ -509,3 +510,90 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if sampling:
             return res[0].clone(), res[1].clone(), res[2].clone()
         return res[0].clone(), res[1].clone(), None
+
+    # ------------------------------------------------------------------ teacher-forced decode (scoring, grounding on GT sentences)
+    @torch.no_grad()
+    def score(self, segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask, sample_idx,
+              pnt_mask, captions: Optional[torch.Tensor] = None, grounding: bool = False, decode_weights: Optional[str] = None):
+        """The decoder run over GIVEN words on the decode engine's forced mode (DecodeEngine forced_n; no autograd pass, eval()
+        semantics): forward's 11 tensors, plus
+        captions: [B, n, T] or [B * n, T] int64, n captions per clip (row b * n + j = caption j of clip b); None = the batch's
+        ground-truth captions gt_caption[:, :seq_per_img].
+        -> dict of clones: logprob [B * n, T] (the model's log-prob of every given word, full vocabulary), rank [B * n, T] int32
+        (its rank among the logits, 0 = arg-max), mask [B * n, T] bool (the steps up to and including the first 0, as LMCriterion
+        masks them), seq_logprob [B * n] (the masked sum), att [B * n, T, N] (post-softmax region attention).
+        grounding=True (ground-truth captions only, n = seq_per_img = 1): the frame mask of every word's boxes is bound to the
+        engine, and the dict also holds att2_weights [B, T, N] (frame-masked pre-softmax attention), ground_weights [B, T, N],
+        roi_labels [B, T, N] and frm_mask_output [B, T, N + 1] -- the tensors debug_collect shows for the eval-mode training pass.
+        decode_weights: "fp32" / "bf16" (argument, else opts.decode_weights), DecodeEngine's weights_dtype."""
+        was_training = self.training
+        self.eval()
+        try:
+            return self._score(segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask,
+                               sample_idx, pnt_mask, captions, grounding, decode_weights)
+        finally:
+            self.train(was_training)
+
+    def _score(self, segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask, sample_idx,
+               pnt_mask, captions, grounding, decode_weights):
+        T = self.seq_length
+        B = proposals.size(0)
+        if grounding and (captions is not None or self.seq_per_img != 1):
+            raise RuntimeError("score(grounding=True) grounds the batch's ground-truth captions, one per clip: captions must be None "
+                               f"and seq_per_img 1 (got seq_per_img = {self.seq_per_img})")
+        if captions is None:
+            captions = gt_caption[:, :self.seq_per_img, :]
+        if captions.dim() == 3:
+            if captions.size(0) != B:
+                raise RuntimeError(f"score: captions [B, n, T] has {captions.size(0)} clips, the batch {B}")
+            captions = captions.reshape(-1, captions.size(2))
+        if captions.dim() != 2 or captions.size(1) != T or captions.size(0) % B or captions.dtype != torch.int64:
+            raise RuntimeError(f"score: captions must be int64 [B, n, T] or [B * n, T] with B = {B}, T = {T}; got {captions.dtype} "
+                               f"{tuple(captions.shape)}")
+        n = captions.size(0) // B
+        F_.new_step()
+        overlaps, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, g_pool_feats, pnt_mask, _o, _c, _l) = self._encode(
+            segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
+        feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
+                     pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
+        step_fmask = None
+        if grounding:
+            # label glue exactly as _forward_3_loops does it: per-word proposal labels and the frame mask on proposals
+            roi_labels, frm_mask_output, step_fmask = hip.label_glue(overlaps, mask_boxes[:, 0, :, 1:T + 1], frm_mask, pnt_mask)
+        temp = float(getattr(self.opts, "softmax_temp", 1.0))
+        wdtype = self.decode_weights_dtype if decode_weights is None else decode_weights
+        weights = self.decode_weights()
+        # one forced engine per batch shape, in a slot of its own: a score call between two _sample calls evicts nothing there
+        key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), temp, T, self.use_hip_graph, n,
+               wdtype, bool(grounding))
+        cached = getattr(self, "_score_cache", None)
+        captions = captions.contiguous()
+        if cached is not None and cached[0] == key:
+            engine = cached[1]
+            engine.load_features(feats)
+            engine.load_captions(captions, step_fmask)
+        else:
+            engine = DecodeEngine(weights, feats, T, self.unk_idx, inv_temp=1.0 / temp, own_features=True, forced_n=n,
+                                  weights_dtype=wdtype)
+            engine.load_captions(captions, step_fmask)         # (the frame mask is part of the launch list: before capture)
+            if self.use_hip_graph:
+                engine.capture()
+            self._score_cache = (key, engine)
+        _seq, att, logprob, rank = engine.run()
+        first0 = (captions == 0).long().cumsum(1)
+        mask = (first0 == 0) | ((first0 == 1) & (captions == 0))           # steps up to and including the first 0 (LMCriterion)
+        logprob = logprob.clone()
+        out = dict(logprob=logprob, rank=rank.clone(), mask=mask, seq_logprob=logprob.masked_fill(~mask, 0.0).sum(1), att=att.clone())
+        if grounding:
+            att2_weights = engine.fm_steps.transpose(0, 1).clone()                    # [B, T, N] pre-softmax, frame-masked
+            xt_clamp = torch.clamp(input_seq.view(-1, input_seq.size(2), input_seq.size(3))[:, 1:T + 1, 0].clone() - self.vocab_size, min=0)
+            xt_all = self._vis_embed(xt_clamp)
+            if hasattr(self.roi_feat_extractor, 'vis_classifiers_bias'):
+                bias = self.roi_feat_extractor.vis_classifiers_bias[xt_clamp].type(xt_all.type()).unsqueeze(2).expand(
+                    B, T, pool_feats.size(1))
+            else:
+                bias = 0
+            ground_weights = self._grounder(xt_all, g_pool_feats, frm_mask_output[:, :, 1:], bias + att2_weights)
+            out.update(att2_weights=att2_weights, ground_weights=ground_weights.clone(), roi_labels=roi_labels.clone(),
+                       frm_mask_output=frm_mask_output.clone())
+        return out

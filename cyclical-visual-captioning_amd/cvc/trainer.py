@@ -14,6 +14,7 @@ import os
 import time
 from collections import defaultdict
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -536,6 +537,8 @@ class Trainer:
         # every rank decoded its shard of the clips; merge host-side, rank 0 writes the files and scores
         predictions, grd_output = gather_eval_outputs(predictions, grd_output)
         lang_stats = {}
+        if getattr(o, "eval_obj_grounding_gt", False):        # (every rank: its shards are merged like the predictions)
+            self._eval_ground_gt(epoch, tb_logger)
         self.submission_file = self.attn_file = None
         self.predictions = predictions
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
@@ -551,6 +554,115 @@ class Trainer:
                     tb_logger.add_scalar('eval/' + k, v, epoch)
         self.predictions = predictions
         return lang_stats
+
+    def _eval_ground_gt(self, epoch, tb_logger):
+        """eval's --eval_obj_grounding_gt part: grounding on the GT sentences, kept as self.grounding_gt_stats and logged under
+        grounding_gt/ -- never merged into eval's lang_stats (the LR schedule and the best-score logic read those)."""
+        self.grounding_gt_stats = self.ground_gt()
+        if tb_logger and self.grounding_gt_stats:
+            for k, v in self.grounding_gt_stats.items():
+                tb_logger.add_scalar('grounding_gt/' + k, v, epoch)
+
+    def _val_batches(self):
+        """the validation split's batches as eval prepares them, with the proposal axis of the frame mask trimmed like the proposals
+        (what the label glue of a teacher-forced pass reads; _prepare trims it for training batches only)"""
+        for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
+            n_prop = b["ppls"].size(1)
+            if b["mask_frms"].size(1) != n_prop:
+                b["mask_frms"] = b["mask_frms"][:, :n_prop].contiguous()
+            yield b
+
+    def _full_proposal_axis(self, ppls, weights):
+        """an evaluation batch is trimmed to its largest proposal count (_prepare); the per-frame box gather wants all
+        num_sampled_frm x num_prop_per_frm slots: the missing ones are zero boxes that no word attends to"""
+        full = self.opts.num_sampled_frm * self.opts.num_prop_per_frm
+        pad = full - ppls.size(1)
+        if pad <= 0:
+            return ppls, weights
+        return (torch.nn.functional.pad(ppls, (0, 0, 0, pad)), torch.nn.functional.pad(weights, (0, pad), value=float("-inf")))
+
+    def _score_call(self, model, b, **kw):
+        return model.score(b["segs_feat"], b["input_seqs"], b["gt_seqs"], b["num"], b["ppls"], b["gt_bboxs"], b["mask_bboxs"],
+                           b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"], **kw)
+
+    def score(self, stem: str = None):
+        """Teacher-forced scoring of the validation split's GT captions (model.score: the decode engine's forced mode).
+        Writes <results_dir>/<stem>_scores.json (rank 0, after the merge of the ranks' shards, as sample does; stem defaults to
+        densecap-<val_split>-<id>):  {video: [{"segment", "timestamp", "logprob": sum of the caption's log-probs over its masked
+        steps, "words": the number of those steps, "top1": how many of them have the given word as the model's arg-max}]}
+        Returns {"ppl": exp(-sum logprob / sum words), "top1": sum top1 / sum words} over the first caption of every segment."""
+        model = getattr(self.model, "module", self.model)
+        o = self.opts
+        timestamps = self._segment_timestamps()
+        scores = defaultdict(list)
+        for b in self._val_batches():
+            out = self._score_call(model, b)
+            n = out["logprob"].size(0) // len(b["seg_id"])
+            mask = out["mask"]
+            lp, nw = out["seq_logprob"].tolist(), mask.sum(1).tolist()
+            top1 = ((out["rank"] == 0) & mask).sum(1).tolist()
+            for k, seg_id in enumerate(b["seg_id"]):
+                vid_idx, entry = densecap_entry("", seg_id, timestamps)
+                scores[vid_idx].append({"segment": entry["segment"], "timestamp": entry["timestamp"], "logprob": lp[k * n],
+                                        "words": nw[k * n], "top1": top1[k * n]})
+        scores, _ = gather_eval_outputs(scores, {})
+        self.scores = scores
+        tot = [sum(e[key] for segs in scores.values() for e in segs) for key in ("logprob", "words", "top1")]
+        stats = {"ppl": float(np.exp(-tot[0] / max(tot[1], 1))), "top1": tot[2] / max(tot[1], 1)}
+        if not (torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0):
+            d = getattr(o, "results_dir", "results")
+            os.makedirs(d, exist_ok=True)
+            self.scores_file = os.path.join(d, (stem or "densecap-%s-%s" % (o.val_split, o.id)) + "_scores.json")
+            with open(self.scores_file, "w") as f:
+                json.dump(scores, f)
+        return stats
+
+    def ground_gt(self, stem: str = None):
+        """Grounding on the GT sentences (--eval_obj_grounding_gt; the reference parses the flag and raises NotImplementedError,
+        trainer.py:352-353): model.score(grounding=True) over the validation split, then per annotated object word the proposal
+        with the largest weight among those that are not frame-masked -- once by the decoder's frame-masked region attention
+        (att2_weights -> box_accu_att), once by the grounder (ground_weights -> box_accu_grd); a hit is a proposal that overlaps one
+        of the word's boxes (roi_labels).  Writes attn-gt-sent-results-<split>-<id>.json and grd-gt-sent-results-<split>-<id>.json
+        (write_grounding_json's layout, 'eval_mode': 'GT'; a stem replaces the first part of both names) and returns the two
+        accuracies, their per-class means and the number of annotated object words."""
+        model = getattr(self.model, "module", self.model)
+        o = self.opts
+        records = defaultdict(list)
+        grd_att, grd_grd = defaultdict(dict), defaultdict(dict)
+        for b in self._val_batches():
+            out = self._score_call(model, b, grounding=True)
+            T = out["att2_weights"].size(1)
+            cls = (b["input_seqs"][:, 0, 1:T + 1, 0] - o.vocab_size)
+            annotated = (~b["mask_bboxs"][:, 0, :, 1:T + 1].bool()).any(1)                       # [B, T]
+            counted = (cls >= 1) & annotated
+            hits = [ground_picks(out[k], out["frm_mask_output"], out["roi_labels"])[1] for k in ("att2_weights", "ground_weights")]
+            sel = counted.nonzero().tolist()
+            cls_l, ha, hg = cls.tolist(), hits[0].tolist(), hits[1].tolist()
+            records["words"].extend((cls_l[i][t], ha[i][t], hg[i][t]) for i, t in sel)
+            gt_words = b["gt_seqs"][:, 0].tolist()
+            obj = (cls >= 1).tolist()
+            for key, dst in (("att2_weights", grd_att), ("ground_weights", grd_grd)):
+                boxes_l = self._frame_boxes(*self._full_proposal_axis(b["ppls"], out[key]))[..., :4].tolist()
+                for i, seg_id in enumerate(b["seg_id"]):
+                    vid_id, seg_idx = seg_id.split('_segment_')
+                    res = {'clss': [], 'idx_in_sent': [], 'bbox_for_all_frames': []}
+                    for j, w in enumerate(gt_words[i][:T]):
+                        if w == 0:
+                            break
+                        if obj[i][j]:
+                            res['bbox_for_all_frames'].append(boxes_l[i][j])
+                            res['clss'].append(o.itod[cls_l[i][j]])
+                            res['idx_in_sent'].append(j)
+                    dst[vid_id][str(int(seg_idx))] = res
+        records, grd_att = gather_eval_outputs(records, grd_att)
+        _, grd_grd = gather_eval_outputs({}, grd_grd)
+        stats = ground_accuracy(records.get("words", []))
+        self.grounding_gt = (grd_att, grd_grd)
+        self.grounding_gt_files = None
+        if not (torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0):
+            self.grounding_gt_files = (write_grounding_json(grd_att, o, stem=(stem or 'attn') + '-gt-sent-results', eval_mode='GT'),
+                                       write_grounding_json(grd_grd, o, stem=(stem or 'grd') + '-gt-sent-results', eval_mode='GT'))
+        return stats
 
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
@@ -592,14 +704,20 @@ class Trainer:
             json.dump(samples, f)
         return path
 
+    def _frame_boxes(self, ppls, weights):
+        """weights [B, T, N] over the proposals (N = num_sampled_frm x num_prop_per_frm, frame-major) -> per word the proposal
+        with the largest weight in every sampled frame: boxes [B, T, num_sampled_frm, 7] (trainer.py:217-225)"""
+        o = self.opts
+        B = weights.size(0)
+        ind = torch.max(weights.view(B, weights.size(1), o.num_sampled_frm, o.num_prop_per_frm), dim=-1)[1]
+        return torch.gather(ppls.view(-1, o.num_sampled_frm, o.num_prop_per_frm, 7).permute(0, 2, 1, 3).contiguous(), 1,
+                            ind.unsqueeze(-1).expand(B, ind.size(1), o.num_sampled_frm, ppls.size(-1)))
+
     def _collect_grounding(self, b, seq, att2_weights, grd_output):
         """Per generated word, the most attended proposal of every sampled frame (trainer.py:217-248)."""
         o = self.opts
         B = seq.size(0)
-        ppls = b["ppls"]
-        att2_ind = torch.max(att2_weights.view(B, att2_weights.size(1), o.num_sampled_frm, o.num_prop_per_frm), dim=-1)[1]
-        boxes = torch.gather(ppls.view(-1, o.num_sampled_frm, o.num_prop_per_frm, 7).permute(0, 2, 1, 3).contiguous(), 1,
-                             att2_ind.unsqueeze(-1).expand(B, att2_ind.size(1), o.num_sampled_frm, ppls.size(-1)))
+        boxes = self._frame_boxes(b["ppls"], att2_weights)
         lemma_det = {o.wtol[k]: i for k, i in o.wtod.items() if k in o.wtol}
         words = seq.tolist()                                   # one device -> host copy each, not one per word
         boxes_l = boxes[..., :4].tolist()
@@ -615,6 +733,31 @@ class Trainer:
                     res['clss'].append(o.itod[lemma_det[lemma]])
                     res['idx_in_sent'].append(j)
             grd_output[vid_id][str(int(seg_idx))] = res
+
+
+def ground_picks(weights, frm_mask_output, roi_labels):
+    """weights [B, T, N] (attention or grounder scores of every word over the proposals), frm_mask_output [B, T, N + 1] bool (column 0:
+    the sentinel), roi_labels [B, T, N] bool -> pick [B, T] int64: the arg-max over the proposals that are not frame-masked, lowest
+    index on ties, -1 for a word without such a proposal; hit [B, T] bool: roi_labels at the pick (a word without one: a miss)."""
+    free = ~frm_mask_output[:, :, 1:].bool()
+    some = free.any(2)
+    pick = weights.masked_fill(~free, float("-inf")).argmax(2)           # (the first of equal maxima)
+    hit = roi_labels.bool().gather(2, pick.unsqueeze(2)).squeeze(2) & some
+    return torch.where(some, pick, torch.full_like(pick, -1)), hit
+
+
+def ground_accuracy(words):
+    """words: (class index, hit by the attention, hit by the grounder) per annotated object word -> box_accu_att / box_accu_grd
+    (hits over all such words), their per-class means box_accu_*_per_cls, and the number of words"""
+    per = defaultdict(list)
+    for cls, ha, hg in words:
+        per[int(cls)].append((bool(ha), bool(hg)))
+    n = sum(len(v) for v in per.values())
+    stats = {"obj_words": n}
+    for i, name in enumerate(("att", "grd")):
+        stats["box_accu_" + name] = sum(h[i] for v in per.values() for h in v) / n if n else 0.0
+        stats["box_accu_%s_per_cls" % name] = float(np.mean([np.mean([h[i] for h in v]) for v in per.values()])) if n else 0.0
+    return stats
 
 
 def densecap_entry(sentence, seg_id, timestamps):
@@ -642,11 +785,12 @@ def write_densecap_json(predictions, o):
     return path
 
 
-def write_grounding_json(grd_output, o):
-    """Per-word grounding boxes of the generated sentences for the ANet-Entities scorer (trainer.py:318-329)."""
-    path = _results_path(o, 'attn-gen-sent-results')
+def write_grounding_json(grd_output, o, stem='attn-gen-sent-results', eval_mode='gen'):
+    """Per-word grounding boxes of the generated sentences for the ANet-Entities scorer (trainer.py:318-329); with another stem and
+    eval_mode 'GT': of the GT sentences (Trainer.ground_gt)."""
+    path = _results_path(o, stem)
     with open(path, 'w') as f:
-        json.dump({'results': grd_output, 'eval_mode': 'gen',
+        json.dump({'results': grd_output, 'eval_mode': eval_mode,
                    'external_data': {'used': True,
                                      'details': 'Object detector pre-trained on Visual Genome on object detection task.'}}, f)
     return path

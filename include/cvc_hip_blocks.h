@@ -156,6 +156,17 @@ int cvc_sample_select_trunc_parts(const float* parts, int nparts, long long part
                                   int unk_idx, float inv_tau, int top_k, float top_p, const uint32_t* rng_state, int t,
                                   int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                   cvc_stream_t stream);
+/* Teacher-forced decoding (csrc/forced.hip): the log-prob and the rank of a GIVEN word per row, one workgroup per row.
+ *   z[r, :]    = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish -- the bits the other
+ *                selection blocks see (nparts = 1, bias = NULL: a finished [M, V] logit matrix)
+ *   w          = word[r * word_stride], read only (the block writes no word); w outside [0, V): logprob[r] = NaN, rank[r] = -1,
+ *                and nothing is read at w
+ *   logprob[r] = z[r, w] - logsumexp_v z[r, v]   (nullable; full V, UNK included: the definition of cvc_sample_select_parts)
+ *   rank[r]    = #{v : z[r, v] > z[r, w]} + #{v < w : z[r, v] == z[r, w]}   (nullable; 0 <=> w is the arg-max under the lower-index
+ *                tie rule; NaN logits compare false)
+ * V <= 8192, M * V < 2^32 (CVC_E_TOOBIG otherwise); the argument checks of cvc_sample_select_parts.  Bitwise deterministic. */
+int cvc_forced_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
+                            const int64_t* word, int word_stride, float* logprob, int32_t* rank, cvc_stream_t stream);
 int cvc_tile_lstm_finish(const float* parts, int nparts, long long part_stride, const float* b_ih, const float* b_hh,
                          const float* gate_bias, int gb_div, const float* c_prev, int M, int R, float* c_out,
                          float* h_out, void* frag1, long long frag1_stride, void* frag2, long long frag2_stride,
