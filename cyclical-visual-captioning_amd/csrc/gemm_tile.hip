@@ -859,7 +859,9 @@ __global__ __launch_bounds__(256) void tile_pack_rows_kernel(const float* x, int
 }
 
 
-// fp32 row-major [M, K], ANY K (scalar, bounds-checked loads; the k tail of the last 16-step is zero) -> activation fragments
+// fp32 row-major [M, K], ANY K (scalar, bounds-checked loads) -> activation fragments.  Writes the ceil(K / 4) quads of the rows
+// below M, zeros from K to the end of the last quad; the rest of the last 16-step and rows >= M are the caller's to clear
+// (include/cvc_hip.h; cvc.hip._FragPool clears them once per buffer)
 __global__ __launch_bounds__(256) void tile_pack_rows_any_kernel(const float* x, long long ldx, int M, int K, uint16_t* xb,
                                                                  long long mblk_stride) {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -648,81 +648,18 @@ __global__ __launch_bounds__(WG) void lstm_pointwise_bwd4v_pair_kernel(PwOne a, 
 constexpr int BEAM_MAX = 8;
 constexpr int ROW_CACHE = 32;        // values per thread kept in registers: V <= 256 * 32
 
-// logits: [rows, V], or -- nparts > 1 / bias given -- the K-slice slabs of the vocabulary GEMM [nparts][rows, V] (+ bias [V]),
-// summed in slab order while the row is loaded (the tile path's logits never exist as one matrix)
-__global__ __launch_bounds__(WG) void beam_rowtop_kernel(const float* logits, int nparts, long long part_stride, const float* bias,
-                                                         int beam, int V, int unk, float* cand_v, int* cand_i, float* lse_out) {
-    __shared__ float red[4];
-    __shared__ float bestv[4];
-    __shared__ int besti[4];
-    __shared__ int winner;
-    const int row = blockIdx.x;
-    const float* x = logits + (size_t)row * V;
-    float vals[ROW_CACHE];
-    float m = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < ROW_CACHE; ++u) {
-        const int v = threadIdx.x + u * WG;
-        float xv = -INFINITY;
-        if (v < V) {
-            xv = x[v];
-            for (int p = 1; p < nparts; ++p) xv += x[(size_t)p * part_stride + v];
-            if (bias != nullptr) xv += bias[v];
-        }
-        vals[u] = xv;
-        m = fmaxf(m, vals[u]);
-    }
-    m = block_max(m, red);
-    float s = 0.f;
-#pragma unroll
-    for (int u = 0; u < ROW_CACHE; ++u) s += expf(vals[u] - m);       // exp(-inf) = 0 for padding
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) lse_out[row] = m + logf(s);
-#pragma unroll
-    for (int u = 0; u < ROW_CACHE; ++u)
-        if (threadIdx.x + u * WG == unk) vals[u] = -INFINITY;
-    for (int sel = 0; sel < beam; ++sel) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < ROW_CACHE; ++u) {
-            const int v = threadIdx.x + u * WG;
-            if (v < V && better(vals[u], v, bv, bi)) { bv = vals[u]; bi = v; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        __syncthreads();
-        if (lane == 0) { bestv[wave] = bv; besti[wave] = bi; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w)
-                if (better(bestv[w], besti[w], bv, bi)) { bv = bestv[w]; bi = besti[w]; }
-            cand_v[row * BEAM_MAX + sel] = bv;
-            cand_i[row * BEAM_MAX + sel] = bi;
-            winner = bi;
-        }
-        __syncthreads();
-        const int wv = winner;
-#pragma unroll
-        for (int u = 0; u < ROW_CACHE; ++u)
-            if (threadIdx.x + u * WG == wv) vals[u] = -INFINITY;   // taken
-    }
-}
-
-// Fast form for one finished logit matrix with V % 4 == 0: float4 loads all requested up front (the general kernel's inner slab
-// loop and bias branch serialised its 20 loads per thread), log-sum-exp from per-wave (max, sum) pairs, and the `beam` best
-// found per WAVE without a barrier (shuffles only), then merged by wave 0 -- the row's top `beam` are among the 4 x beam wave
-// winners, so the result is the general kernel's (ties broken towards the lower index in both).  3 barriers instead of 19.
-// NP > 0: the logits are still the NP K-slice slabs of the vocabulary GEMM (+ bias): summed on load in the finishing pass's order
-// (slab 0 + slab 1 + ... + bias, cvc_tile_linear_finish), so the finished matrix is never written or read back.
-template <int NG, int NP = 0>      // float4 groups per thread: V <= NG * 1024
-__global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, long long part_stride, const float* bias, int beam, int V,
-                                                          int unk, float* cand_v, int* cand_i, float* lse_out) {
+// Row scan, one workgroup per hypothesis row: thread tid holds elements (tid + 256 g) * 4 .. + 3 of group g in registers, the
+// log-sum-exp comes from per-wave (max, sum) pairs, and the `beam` best are found per WAVE without a barrier (shuffles only), then
+// merged by wave 0 -- the row's top `beam` are among the 4 x beam wave winners; ties go to the lower index.
+// VEC (the fast form, V % 4 == 0 and aligned operands): float4 loads, all requested up front.  NP > 0: the logits are still the NP
+// K-slice slabs of the vocabulary GEMM (+ bias), summed on load in the finishing pass's order (slab 0 + slab 1 + ... + bias,
+// cvc_tile_linear_finish), so the finished matrix is never written or read back.
+// VEC == false (the general form: any V, any alignment, any number of slabs): scalar, bounds-checked loads and a run-time slab loop
+// in the same order, then the SAME code -- its log-sum-exp, candidates and scores are the fast form's bit for bit on the same
+// values (tests/test_gpu_tile_path.py; history and figures: profiles/tile_path_pins.md).
+template <int NG, int NP = 0, bool VEC = true>      // float4 groups per thread: V <= NG * 1024
+__global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, int nparts, long long part_stride, const float* bias, int beam,
+                                                          int V, int unk, float* cand_v, int* cand_i, float* lse_out) {
     __shared__ float wm[4], ws[4];
     __shared__ float wv[4 * BEAM_MAX];
     __shared__ int wi[4 * BEAM_MAX];
@@ -732,7 +669,19 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, l
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const int e = (tid + g * WG) * 4;
-        if (e < V) {
+        if constexpr (!VEC) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = e + j;
+                float xv = -INFINITY;
+                if (v < V) {
+                    xv = x[v];
+                    for (int p = 1; p < nparts; ++p) xv += x[(size_t)p * part_stride + v];
+                    if (bias != nullptr) xv += bias[v];
+                }
+                v4[g][j] = xv;
+            }
+        } else if (e < V) {
             v4[g] = ld4(x + e);
             if constexpr (NP > 0) {
                 f32x4 pv[NP];
@@ -1246,7 +1195,7 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
     // over the chip)
     if ((aligned && nparts == 1 && bias == nullptr) || slabs) {
 #define CVC_RT4P(NG_, NP_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, NP_>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
-                                              part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse)
+                                              nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse)
 #define CVC_RT4(NG_) do { switch (slabs ? nparts : 0) { case 2: CVC_RT4P(NG_, 2); break; case 4: CVC_RT4P(NG_, 4); break; \
                                                          case 6: CVC_RT4P(NG_, 6); break; case 8: CVC_RT4P(NG_, 8); break; \
                                                          default: CVC_RT4P(NG_, 0); break; } } while (0)
@@ -1262,9 +1211,21 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
         }
 #undef CVC_RT4
 #undef CVC_RT4P
-    } else
-        hipLaunchKernelGGL(beam_rowtop_kernel, dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, nparts, part_stride, bias, beam,
-                           V, unk_idx, cand_v, cand_i, lse);
+    } else {
+#define CVC_RT4G(NG_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, 0, false>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
+                                         nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse)
+        switch ((V + 4 * WG - 1) / (4 * WG)) {
+            case 1: CVC_RT4G(1); break;
+            case 2: CVC_RT4G(2); break;
+            case 3: CVC_RT4G(3); break;
+            case 4: CVC_RT4G(4); break;
+            case 5: CVC_RT4G(5); break;
+            case 6: CVC_RT4G(6); break;
+            case 7: CVC_RT4G(7); break;
+            default: CVC_RT4G(8); break;
+        }
+#undef CVC_RT4G
+    }
     hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
                        beam, V, first_step, parent, word, score_out, done_out);
     return cvc_launch_status();

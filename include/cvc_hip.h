@@ -468,7 +468,8 @@ CVC_API int cvc_beam_select(const float* logits, const float* score_in, const ui
  * plus bias[V] (nullable): summed in slab order while a row is loaded, so the tile path never writes the logits matrix */
 /* Best hypothesis of every clip after a beam decode: words [T, B*beam] (the word chosen for row r at step t), parent
  * [T, B*beam] (its parent beam slot), att [T, B*beam, N] (region attention of the step, computed for the parent row) ->
- * seq [B, T], att_out [B, T, N] of the rank-0 hypothesis (build-defined beam rule).  T <= 256. */
+ * seq [B, T], att_out [B, T, N] of the rank-0 hypothesis (build-defined beam rule).  T <= 256.
+ * A parent outside [0, beam) is clamped to the nearest slot (0 or beam - 1), so that no read leaves the clip's rows. */
 CVC_API int cvc_beam_backtrack(const int64_t* words, const int64_t* parent, const float* att, int B, int beam, int T, int N,
                        int64_t* seq, float* att_out, cvc_stream_t stream);
 
@@ -511,9 +512,16 @@ CVC_API int cvc_tile_linear_finish(const float* parts, int nparts, long long par
 CVC_API int cvc_tile_pack_rows(const float* x, int ldx, const int64_t* idx, int relu, int M, int K, void* xb,
                        long long x_mblk_stride, cvc_stream_t stream);
 /* Operand packers for the dense backward products (autograd of nn.Linear / nn.LSTMCell: dW = dY^T X batched over all T steps,
- * dX = dY W of the vocabulary head; reference decoder_core.py:50,61, captioner.py:266,361): any sizes, zero fill.
- * cvc_tile_pack_rows_any: x [M, K] row-major -> fragments with rows m, contraction k (k padded to a multiple of 16).
- * cvc_tile_pack_cols:     x [S, C] row-major read as its transpose -> fragments with rows c, contraction s. */
+ * dX = dY W of the vocabulary head; reference decoder_core.py:50,61, captioner.py:266,361): any sizes.
+ * cvc_tile_pack_rows_any: x [M, K] row-major -> fragments with rows m, contraction k (the GEMM's K is K padded to a multiple of 16).
+ *   What it writes depends on the form it takes (pinned in tests/test_gpu_tile_path.py):
+ *   - K % 16 == 0, ldx % 4 == 0 and x 16-byte aligned: whole fragments of the ceil(M/32) row blocks, rows [M, 32 ceil(M/32)) as zeros;
+ *   - otherwise (scalar loads): ONLY the ceil(K/4) quads of the rows below M, zeros from K to the end of the last quad.  The rest of
+ *     the last k step and the rows from M on are NOT written: the caller clears them once (cvc.hip._FragPool does, when it creates
+ *     a buffer, and keys its buffers by (rows, K) so that the padding stays zero across uses).
+ *   Row blocks from ceil(M/32) up to cvc_tile_rows_alloc(M) / 32 are the caller's to clear in both forms.
+ * cvc_tile_pack_cols:     x [S, C] row-major read as its transpose -> fragments with rows c, contraction s: whole fragments of the
+ *   ceil(C/32) row blocks x ceil(S/16) k steps, zeros beyond C and S; further row blocks are the caller's to clear. */
 CVC_API int cvc_tile_pack_rows_any(const float* x, long long ldx, int M, int K, void* xb, long long x_mblk_stride, cvc_stream_t stream);
 CVC_API int cvc_tile_pack_cols(const float* x, long long ldx, int S, int C, void* xb, long long x_mblk_stride, cvc_stream_t stream);
 /* Beam-state reorder fused with next step's operand packing: row r continues hypothesis (r / beam) * beam + parent[r]
