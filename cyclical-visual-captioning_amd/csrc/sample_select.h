@@ -1,0 +1,345 @@
+// The selection kernel of sampled decoding and its dispatch, shared by csrc/sample.hip (cvc_sample_select_parts /
+// cvc_sample_select_trunc_parts: contract in that file's header comment) and csrc/constrain.hip (cvc_constrained_select_parts:
+// the CONS flag of the same kernel, contract in that file).  One definition of the logit sum, the hash counters, the noise, the
+// truncation search and the log-prob: every form rounds alike.
+#pragma once
+#include "cvc_common.h"
+#include "dropout_rng.h"
+#include <math.h>
+
+namespace {
+
+constexpr int WG = 256;
+constexpr int SAMPLE_NC_MAX = 32;              // logits per thread: V <= 8192, the bound of cvc_beam_select_parts
+constexpr uint32_t KEY_NEG_INF = 0x007fffffu;  // key of -inf: no float compares below it
+
+// what the truncating form of the kernel takes on top of the plain one's arguments (the plain one: nothing)
+struct NoTrunc {};
+struct TruncArgs { int top_k; float top_p; float* cutoff; int32_t* kept; };
+template <bool TRUNC> struct trunc_args { using type = NoTrunc; };
+template <> struct trunc_args<true> { using type = TruncArgs; };
+
+// what the constrained form takes on top (csrc/constrain.hip): the row's history hist[s * hist_stride + row], s < t, and the rules
+constexpr int CONS_T_MAX = 64;                 // history steps: one lane per step
+constexpr int CONS_LIST_MAX = 256;             // entries of a list: one thread per entry
+struct NoCons {};
+struct ConsArgs {
+    const int64_t* hist; long long hist_stride; int t;
+    int ngram, immediate, min_len;
+    const int32_t* ban; int nban;
+    const int32_t* bad_end; int nbad;
+    int32_t* nbanned;
+};
+template <bool CONS> struct cons_args { using type = NoCons; };
+template <> struct cons_args<true> { using type = ConsArgs; };
+
+// the float of an order-preserving key: key(a) < key(b) <=> a < b over the non-NaN floats (-0 below +0; keys above key(+inf) and
+// below KEY_NEG_INF are NaNs)
+__device__ __forceinline__ float unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) { return (va > vb) | ((va == vb) & (ia < ib)); }
+
+// the Gumbel perturbation of hash value h (its 23 high bits)
+__device__ __forceinline__ float gumbel(uint32_t h) {
+    const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;
+    return -logf(-logf(u));
+}
+
+// NC logits per thread; NP > 0: that many slabs summed with an unrolled loop, NP == 0: nparts at run time.  VEC (V % 4 == 0,
+// 16-byte aligned operands): NC / 4 float4 groups, element u at column (tid + (u / 4) * WG) * 4 + u % 4; otherwise column tid + u * WG.
+// Both sum a column's slabs in the same order (same bits); only the loads differ.
+// TRUNC: the cutoff search of the header comment in front of the Gumbel-max; the noise is then drawn for the kept words only.
+// CONS: the candidates are the words outside the row's ban set (a V-bit map in LDS, built from the history and the lists, then one
+// bit per register slot) instead of the words other than UNK; inv_tau == 0 is then the arg-max mode (s = z, no noise, state unread).
+template <int NC, int NP, bool VEC, bool TRUNC, bool CONS>
+__global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, int nparts, long long part_stride, const float* bias,
+                                                           int V, int unk, float inv_tau, const uint32_t* state, uint32_t site,
+                                                           int64_t* word, int wstride, float* logprob,
+                                                           typename trunc_args<TRUNC>::type ta,
+                                                           typename cons_args<CONS>::type ca) {
+#pragma clang fp contract(off)
+    __shared__ float red_m[4], red_s[4], red_v[4], red_z[4];
+    __shared__ int red_i[4];
+    [[maybe_unused]] __shared__ int red_b[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool noisy = !CONS || inv_tau != 0.f;
+    uint32_t seed_lo = 0, seed_hi = 0, call = 0;
+    if (noisy) { seed_lo = state[0]; seed_hi = state[1]; call = state[2]; }
+    const float* x = parts + (size_t)row * V;
+    float z[NC];
+    auto col = [&](int u) { return VEC ? (tid + (u >> 2) * WG) * 4 + (u & 3) : tid + u * WG; };
+    if constexpr (VEC) {
+#pragma unroll
+        for (int g = 0; g < NC / 4; ++g) {
+            const int e = (tid + g * WG) * 4;
+            f32x4 s = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (e < V) {                                  // V % 4 == 0: the whole group is inside the row
+                if constexpr (NP > 0) {
+                    f32x4 p[NP];
+#pragma unroll
+                    for (int k = 0; k < NP; ++k) p[k] = ld4(x + (size_t)k * part_stride + e);
+                    s = p[0];
+#pragma unroll
+                    for (int k = 1; k < NP; ++k) s += p[k];
+                } else {
+                    s = ld4(x + e);
+                    for (int k = 1; k < nparts; ++k) s += ld4(x + (size_t)k * part_stride + e);
+                }
+                if (bias != nullptr) s += ld4(bias + e);
+            }
+            z[4 * g] = s.x; z[4 * g + 1] = s.y; z[4 * g + 2] = s.z; z[4 * g + 3] = s.w;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            const int v = col(u);
+            float s = -INFINITY;
+            if (v < V) {
+                s = x[v];
+                for (int k = 1; k < nparts; ++k) s += x[(size_t)k * part_stride + v];
+                if (bias != nullptr) s += bias[v];
+            }
+            z[u] = s;
+        }
+    }
+    // CONS: bit u of `banned` = the word of register slot u is in the row's ban set
+    [[maybe_unused]] uint32_t banned = 0;
+    [[maybe_unused]] float se_full = 0.f;
+    if constexpr (CONS) {
+        static_assert(NC <= 32, "one ban bit per register slot");
+        __shared__ uint32_t bits[WG];                       // V <= 32 * WG
+        __shared__ long long hist[CONS_T_MAX];
+        const int t = ca.t;
+        bits[tid] = 0u;
+        if (tid < t) hist[tid] = ca.hist[(size_t)tid * ca.hist_stride + row];
+        __syncthreads();
+        auto ban = [&](long long v) { if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31)); };
+        if (tid == 0) {
+            ban(unk);
+            if (t < ca.min_len) ban(0);
+            if (ca.immediate && t >= 1) ban(hist[t - 1]);
+        }
+        if (tid < ca.nban) ban(ca.ban[tid]);
+        if (t >= 1 && tid < ca.nbad && (long long)ca.bad_end[tid] == hist[t - 1]) ban(0);
+        if (ca.ngram >= 1 && tid < t && tid >= ca.ngram - 1) {          // lane j: y_j is banned if the n - 1 words before it are the last n - 1
+            bool same = true;
+            for (int i = 1; i < ca.ngram; ++i) same = same && hist[tid - i] == hist[t - i];
+            if (same) ban(hist[tid]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            const int v = col(u);
+            if (v < V && ((bits[v >> 5] >> (v & 31)) & 1u)) banned |= 1u << u;
+        }
+        int nb = __popc(bits[tid]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
+        if (lane == 0) red_b[wave] = nb;                    // read by thread 0 after the barriers below
+    }
+    // perturbed scores: the best (s, v) and its logit; the row's maximum logit
+    float bs = -INFINITY, bz = -INFINITY, m = -INFINITY;
+    int bi = 0x7fffffff;
+    const uint32_t base = (uint32_t)row * (uint32_t)V;
+    [[maybe_unused]] float theta = -INFINITY, z_unk = -INFINITY, nkept = 0.f, zmin = INFINITY;
+    if constexpr (TRUNC) {
+        __shared__ float red_c[4], red_p[2][4];
+        // the row's maximum (UNK included: the log-prob's), then UNK leaves the candidates: its slot holds -inf like the padding
+        // (neither is ever counted: no probe runs at a cutoff of -inf, the last pass tests v) and the thread that owns it keeps z_unk
+        float mc = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            m = fmaxf(m, z[u]);
+            if constexpr (CONS) {
+                if (!((banned >> u) & 1u)) mc = fmaxf(mc, z[u]);
+            } else {
+                if (col(u) == unk) { z_unk = z[u]; z[u] = -INFINITY; }
+                mc = fmaxf(mc, z[u]);
+            }
+        }
+        m = wave_max(m);
+        mc = wave_max(mc);
+        if (lane == 0) { red_m[wave] = m; red_c[wave] = mc; }
+        __syncthreads();
+        m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+        mc = fmaxf(fmaxf(red_c[0], red_c[1]), fmaxf(red_c[2], red_c[3]));
+        if constexpr (CONS) {
+            // many slots may leave the candidates: the thread's share of the log-sum-exp (the last pass's terms in its order) is taken
+            // now, then every banned slot holds -inf like the padding
+            if (m != -INFINITY) {
+#pragma unroll
+                for (int u = 0; u < NC; ++u) se_full += expf(z[u] - m);
+            }
+#pragma unroll
+            for (int u = 0; u < NC; ++u)
+                if ((banned >> u) & 1u) z[u] = -INFINITY;
+        }
+        // workgroup sum in a fixed order; alternating slots: one barrier per probe
+        int slot = 0;
+        auto wg_sum = [&](float x) {
+            x = wave_sum(x);
+            float* r = red_p[slot];
+            slot ^= 1;
+            if (lane == 0) r[wave] = x;
+            __syncthreads();
+            return (r[0] + r[1]) + (r[2] + r[3]);
+        };
+        if (mc > -INFINITY) {                              // a candidate with a finite logit exists (NaN logits compare false: never kept)
+            if (ta.top_k > 0) {
+                const float fk = (float)ta.top_k;          // counts are <= 8192: exact in fp32
+                uint32_t T = 0;
+                for (int b = 31; b >= 0; --b) {
+                    const uint32_t c = T | (1u << b);
+                    if (c <= KEY_NEG_INF) { T = c; continue; }      // every candidate is >= -inf
+                    const float th = unkey(c);
+                    float n = 0.f;
+#pragma unroll
+                    for (int u = 0; u < NC; ++u) n += (z[u] >= th) ? 1.f : 0.f;
+                    n = wg_sum(n);
+                    if (n >= fk) {
+                        T = c;
+                        if (n == fk) break;                // exactly k at or above th: that set is C1 (ties compare equal)
+                    }
+                }
+                theta = unkey(T);
+            }
+            if (ta.top_p < 1.f) {
+                float e[NC], tot = 0.f;
+#pragma unroll
+                for (int u = 0; u < NC; ++u) {
+                    e[u] = (z[u] >= theta) ? expf((z[u] - mc) * inv_tau) : 0.f;
+                    tot += e[u];
+                }
+                tot = wg_sum(tot);
+                const float need = ta.top_p * tot;         // <= tot: the predicate holds at the lowest cutoff (same sum, same order)
+                uint32_t T = 0;
+                for (int b = 31; b >= 0; --b) {
+                    const uint32_t c = T | (1u << b);
+                    if (c <= KEY_NEG_INF) { T = c; continue; }
+                    const float th = unkey(c);
+                    float s = 0.f;
+#pragma unroll
+                    for (int u = 0; u < NC; ++u) s += (z[u] >= th) ? e[u] : 0.f;
+                    s = wg_sum(s);
+                    if (s >= need) T = c;
+                }
+                theta = fmaxf(theta, unkey(T));
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NC; ++u) {
+        const int v = col(u);
+        if (v < V) {
+            if constexpr (!TRUNC) m = fmaxf(m, z[u]);
+            bool cand = CONS ? !((banned >> u) & 1u) : v != unk;
+            if constexpr (TRUNC) cand = cand && z[u] >= theta;
+            if (cand) {
+                float s;
+                if (noisy) s = z[u] * inv_tau + gumbel(cvc_drop_hash(seed_lo, seed_hi, call, site, base + (uint32_t)v));
+                else s = z[u];
+                if (better(s, v, bs, bi)) { bs = s; bi = v; bz = z[u]; }
+                if constexpr (TRUNC) { nkept += 1.f; zmin = fminf(zmin, z[u]); }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float os = __shfl_xor(bs, o, 64), oz = __shfl_xor(bz, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (better(os, oi, bs, bi)) { bs = os; bi = oi; bz = oz; }
+    }
+    if constexpr (TRUNC) {
+        __shared__ float red_k[4], red_n[4];
+        nkept = wave_sum(nkept);
+        zmin = -wave_max(-zmin);
+        if (lane == 0) { red_k[wave] = nkept; red_n[wave] = zmin; red_v[wave] = bs; red_i[wave] = bi; red_z[wave] = bz; }
+        __syncthreads();
+        nkept = (red_k[0] + red_k[1]) + (red_k[2] + red_k[3]);
+        zmin = fminf(fminf(red_n[0], red_n[1]), fminf(red_n[2], red_n[3]));
+        if constexpr (!CONS) {
+#pragma unroll
+            for (int u = 0; u < NC; ++u)
+                if (col(u) == unk) z[u] = z_unk;           // the log-sum-exp runs over the full row
+        }
+    } else {
+        m = wave_max(m);
+        if (lane == 0) { red_m[wave] = m; red_v[wave] = bs; red_i[wave] = bi; red_z[wave] = bz; }
+        __syncthreads();
+        m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    }
+    float se = 0.f;
+    if constexpr (TRUNC && CONS) {
+        se = se_full;
+    } else if (m != -INFINITY) {
+#pragma unroll
+        for (int u = 0; u < NC; ++u) se += expf(z[u] - m);          // padding: exp(-inf) = 0
+    }
+    se = wave_sum(se);
+    if (lane == 0) red_s[wave] = se;
+    __syncthreads();
+    if (tid == 0) {
+        bs = red_v[0]; bi = red_i[0]; bz = red_z[0];
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[w], red_i[w], bs, bi)) { bs = red_v[w]; bi = red_i[w]; bz = red_z[w]; }
+        const float S = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
+        int w = bi;
+        if (w < 0 || w >= V) w = 0;        // every score NaN: nothing compared better; the word is a gather index next step
+        word[(size_t)row * wstride] = w;
+        if (logprob != nullptr) logprob[row] = bz - (m + logf(S));
+        if constexpr (CONS) {
+            if (ca.nbanned != nullptr) ca.nbanned[row] = (red_b[0] + red_b[1]) + (red_b[2] + red_b[3]);
+        }
+        if constexpr (TRUNC) {
+            if (ta.cutoff != nullptr) ta.cutoff[row] = zmin;
+            if (ta.kept != nullptr) ta.kept[row] = (int32_t)nkept;
+        }
+    }
+}
+
+}  // namespace
+
+// argument checks shared by the entry points (argmax: the constrained block's mode without noise, inv_tau == 0 and no state)
+static int select_check(const float* parts, int nparts, long long part_stride, int M, int V, float inv_tau, const uint32_t* rng_state,
+                        int t, const int64_t* word, int word_stride, bool argmax = false) {
+    if (!parts || (!rng_state && !argmax) || !word || nparts < 1 || M < 1 || V < 2 || word_stride < 1 || t < 0) return CVC_E_BADARG;
+    if (!argmax && (!(inv_tau > 0.f) || !isfinite(inv_tau))) return CVC_E_BADARG;
+    if (nparts > 1 && part_stride < (long long)M * V) return CVC_E_BADARG;
+    if ((long long)M * V > 0xffffffffLL) return CVC_E_TOOBIG;          // the hash counter r * V + v is one 32-bit word
+    if ((V + WG - 1) / WG > SAMPLE_NC_MAX) return CVC_E_TOOBIG;
+    return 0;
+}
+
+// one dispatch for both forms: the same NC / NP / VEC choice, the TRUNC flag and its arguments on top
+template <bool TRUNC, bool CONS = false>
+static void select_launch(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V, int unk_idx,
+                          float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
+                          typename trunc_args<TRUNC>::type ta, cvc_stream_t stream, typename cons_args<CONS>::type ca = {}) {
+    const int nc = (V + WG - 1) / WG;
+    const uint32_t site = CVC_SAMPLE_SITE + (uint32_t)t;
+    const bool vec = (V & 3) == 0 && ((uintptr_t)parts & 15) == 0 && (nparts == 1 || (part_stride & 3) == 0) &&
+                     ((uintptr_t)bias & 15) == 0;
+#define CVC_SS(NC_, NP_, VEC_) hipLaunchKernelGGL((sample_select_kernel<NC_, NP_, VEC_, TRUNC, CONS>), dim3(M), dim3(WG), 0, \
+                                                  (hipStream_t)stream, parts, nparts, part_stride, bias, V, unk_idx, inv_tau, rng_state, \
+                                                  site, word, word_stride, logprob, ta, ca)
+#define CVC_SS_NP(NG_) do { switch (nparts) { case 1: CVC_SS(4 * NG_, 1, true); break; case 2: CVC_SS(4 * NG_, 2, true); break; \
+                                              case 4: CVC_SS(4 * NG_, 4, true); break; case 6: CVC_SS(4 * NG_, 6, true); break; \
+                                              case 8: CVC_SS(4 * NG_, 8, true); break; default: CVC_SS(4 * NG_, 0, true); break; } \
+                           } while (0)
+    if (vec) {                                             // float4 groups: V <= NG * 1024
+        const int ng = (V + 4 * WG - 1) / (4 * WG);
+        if (ng <= 1) CVC_SS_NP(1);
+        else if (ng <= 2) CVC_SS_NP(2);
+        else if (ng <= 4) CVC_SS_NP(4);
+        else if (ng <= 5) CVC_SS_NP(5);
+        else CVC_SS_NP(8);
+    } else if (nc <= 1) CVC_SS(1, 0, false);
+    else if (nc <= 2) CVC_SS(2, 0, false);
+    else if (nc <= 4) CVC_SS(4, 0, false);
+    else if (nc <= 8) CVC_SS(8, 0, false);
+    else if (nc <= 16) CVC_SS(16, 0, false);
+    else if (nc <= 20) CVC_SS(20, 0, false);
+    else CVC_SS(32, 0, false);
+#undef CVC_SS_NP
+#undef CVC_SS
+}

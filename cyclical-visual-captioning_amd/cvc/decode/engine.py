@@ -19,6 +19,31 @@ from .path_tile import TilePath
 from .path_ring import RingPath
 from .path_experimental import ExperimentalPaths
 
+CONSTRAINT_T_MAX = 64            # history steps of cvc_constrained_select_parts (one lane per step)
+CONSTRAINT_LIST_MAX = 256        # entries of its ban_words / bad_endings lists (one thread per entry)
+
+
+def _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings):
+    """The five constraint arguments checked and normalised: (n, immediate, min_len, ban ids, bad-ending ids), the lists sorted and
+    without duplicates.  Malformed values raise the engine's RuntimeError (ids are checked against V by the caller)."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    for name, v, hi in (("no_repeat_ngram", no_repeat_ngram, CONSTRAINT_T_MAX), ("min_len", min_len, None)):
+        if not is_int(v) or v < 0 or (hi is not None and v > hi):
+            raise RuntimeError(f"DecodeEngine: {name} must be an integer >= 0 (0 = off)" + (f" and <= {hi}" if hi else "") + f", got {v!r}")
+    if not isinstance(no_immediate_repeat, (bool, np.bool_)) and no_immediate_repeat not in (0, 1):
+        raise RuntimeError(f"DecodeEngine: no_immediate_repeat must be a bool, got {no_immediate_repeat!r}")
+    lists = []
+    for name, ids in (("ban_words", ban_words), ("bad_endings", bad_endings)):
+        ids = [] if ids is None else list(ids) if isinstance(ids, (list, tuple, set, frozenset, np.ndarray)) else None
+        if ids is None or not all(is_int(v) and v >= 0 for v in ids):
+            raise RuntimeError(f"DecodeEngine: {name} must be a list of word ids (integers >= 0), got {ban_words if name == 'ban_words' else bad_endings!r}")
+        ids = tuple(sorted({int(v) for v in ids}))
+        if len(ids) > CONSTRAINT_LIST_MAX:
+            raise RuntimeError(f"DecodeEngine: {name} takes at most {CONSTRAINT_LIST_MAX} ids, got {len(ids)}")
+        lists.append(ids)
+    return int(no_repeat_ngram), bool(no_immediate_repeat), int(min_len), lists[0], lists[1]
+
+
 def _capture_mode() -> str:
     """"global" (torch's default) unless a c10d "nccl" process group is up in this process: its watchdog thread polls the events of
     earlier collectives with hipEventQuery, which fails with hipErrorStreamCaptureUnsupported while ANOTHER thread captures in
@@ -40,7 +65,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
-                 top_k: int = 0, top_p: float = 1.0, forced_n: int = 0):
+                 top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
+                 min_len: int = 0, ban_words=None, bad_endings=None):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -79,7 +105,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         launch lists are the sampling paths' with that block as word_select, on the same choice of paths with the same refusals
         (beam > 1, a temperature, gsk, gate_ksplit, lang_ksx, the packed path without the embedding-gate schedule); no C driver.
         With a frame mask bound (load_captions) the region attention also writes its frame-masked pre-softmax scores per step
-        (self.fm_steps [T, rows, N]): the att2_weights of the training pass, what grounding on given sentences reads."""
+        (self.fm_steps [T, rows, N]): the att2_weights of the training pass, what grounding on given sentences reads.
+        no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings: constrained decoding (the rule is
+        the comment of cvc_constrained_select_parts in include/cvc_hip_blocks.h).  Step t never chooses UNK, a word of ban_words, a
+        word that would complete an n-gram the row already holds (no_repeat_ngram = n), the previous word (no_immediate_repeat),
+        word 0 before step min_len or right after a word of bad_endings.  All five off (the default): nothing changes.  Any of
+        them on: the sampling paths' launch lists with that block as word_select, with or without a temperature (without: the
+        arg-max over the allowed words), with sample_n and top_k / top_p; no C driver; capture() works (t and the rules are launch
+        constants, the lists live in engine-owned device buffers).  The engine owns self.nbanned [T, rows] int32 (the size of the
+        ban set) and run() returns the sampling engine's tuple in both modes.  Refused: beam > 1, forced_n, gsk / gate_ksplit /
+        lang_ksx, the packed path without the embedding-gate schedule, T > 64, malformed values and ids outside [0, V)."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -96,6 +131,22 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no sampling temperature")
             if gsk or gate_ksplit or lang_ksx:
                 raise RuntimeError("DecodeEngine: the forced mode runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
+            gate_ksplit, lang_ksx = False, False
+        self.cons = _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings)
+        self.constrained = bool(self.cons[0] or self.cons[1] or self.cons[2] or self.cons[3] or self.cons[4])
+        if self.constrained:
+            if self.beam != 1:
+                raise RuntimeError("DecodeEngine: constrained decoding and beam search (beam > 1) exclude each other (beam histories "
+                                   "follow their parents)")
+            if self.forced:
+                raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no constraints")
+            if gsk or gate_ksplit or lang_ksx:
+                raise RuntimeError("DecodeEngine: constrained decoding runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
+            if self.T > CONSTRAINT_T_MAX:
+                raise RuntimeError(f"DecodeEngine: constrained decoding covers T <= {CONSTRAINT_T_MAX} steps, got T = {self.T}")
+            bad = [v for v in self.cons[3] + self.cons[4] if v >= W.V]
+            if bad:
+                raise RuntimeError(f"DecodeEngine: ban_words / bad_endings ids outside [0, V = {W.V}): {bad}")
             gate_ksplit, lang_ksx = False, False
         if self.bf16w:
             why = None
@@ -117,7 +168,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             gsk, gate_ksplit, lang_ksx = False, False, False
         self.sampling = temperature is not None
         # the next step's word is read from words[t + 1] (sampled there by the selection block, or given): the sampling launch lists
-        self.given = self.sampling or self.forced
+        self.given = self.sampling or self.forced or self.constrained
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
             raise RuntimeError(f"DecodeEngine: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
         if not (0.0 < float(top_p) <= 1.0):
@@ -138,7 +189,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 raise RuntimeError(f"DecodeEngine: sample_n must be >= 1, got {sample_n}")
             self.inv_tau = 1.0 / tau
             gate_ksplit, lang_ksx = False, False
-        elif int(sample_n) != 1:
+        elif self.constrained:
+            self.inv_tau = 0.0                   # the constrained block's arg-max mode
+        if not self.sampling and int(sample_n) != 1:
             raise RuntimeError("DecodeEngine: sample_n > 1 needs a sampling temperature")
         # queries per clip: the beams of beam search, the samples of sampled decoding (attention passes, gate_fc rows)
         self.nq = int(sample_n) if self.sampling else (int(forced_n) if self.forced else self.beam)
@@ -150,9 +203,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         dev = pool.device
         # the packed path: one query per clip, at most 64 rows, widths the fragment layouts take
         packed = self.nq == 1 and B * self.nq <= 64 and path != "tile" and R % 32 == 0 and W.E % 32 == 0 and A % 32 == 0
-        if self.forced and packed and embgate is not None and not embgate:              # (before anything is copied or allocated)
-            raise RuntimeError("DecodeEngine: the forced mode on the packed path needs the embedding-gate schedule (the attention "
-                               "cell reads the word from words[t])")
+        if (self.forced or self.constrained) and packed and embgate is not None and not embgate:   # (before anything is copied or allocated)
+            raise RuntimeError(f"DecodeEngine: {'the forced mode' if self.forced else 'constrained decoding'} on the packed path needs "
+                               "the embedding-gate schedule (the attention cell reads the word from words[t])")
         if self.bf16w and (B * self.nq > 64 or R % 32 or W.E % 32 or A % 32):          # (before anything is copied or allocated)
             raise RuntimeError(f'DecodeEngine: weights_dtype="bf16" covers the packed path only: at most 64 rows and R, E, A '
                                f"multiples of 32 (got {B * self.nq} rows, R = {R}, E = {W.E}, A = {A})")
@@ -199,6 +252,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.trunc:
             self.cutoff = z(self.T, rows)                                     # min over the kept set of z, per step and row
             self.kept = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)
+        if self.constrained:
+            n_, imm_, len_, ban_, bad_ = self.cons
+            i32 = lambda ids: torch.tensor(list(ids) or [0], dtype=torch.int32, device=dev)
+            self.nbanned = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)   # |Ban| per step and row, UNK included
+            self.ban_ids, self.bad_ids = i32(ban_), i32(bad_)
+            self._cons_desc = hip.Constraint(n_, int(imm_), len_, len(ban_), self.ban_ids.data_ptr(), self.bad_ids.data_ptr(), len(bad_))
         if self.beam > 1:
             self.score = z(2, rows)
             self.done = torch.zeros(2, rows, dtype=torch.uint8, device=dev)
@@ -227,7 +286,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             raise RuntimeError("DecodeEngine: the embedding-gate schedule needs the packed path (without gsk / gate_ksplit) or the tile path")
         self.embgate = (eg_ok and 4 * V * 4 * R <= EMBGATE_MAX_BYTES) if embgate is None else bool(embgate)
         if self.given and self.packed and not self.embgate:
-            raise RuntimeError(f"DecodeEngine: {'sampling' if self.sampling else 'the forced mode'} on the packed path needs the "
+            raise RuntimeError(f"DecodeEngine: {'sampling' if self.sampling else 'the forced mode' if self.forced else 'constrained decoding'} on the packed path needs the "
                                "embedding-gate schedule (the attention cell reads the word from words[t])")
         # what stays in the Infinity Cache between steps: small linear weights, then (embedding-gate schedule on the packed path) the
         # attention cell's gate matrix over K = 2R if it fits, then the largest subset of the feature tensors
@@ -471,6 +530,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             return ("word_select", L.cvc_forced_select_parts, (parts, nparts, part_stride, bias, rows, V, self.words[t + 1].data_ptr(), 1,
                                                                self.logprob[t].data_ptr(), self.rank[t].data_ptr()))
         head = (parts, nparts, part_stride, bias, rows, V, self.unk, self.inv_tau)
+        if self.constrained:           # the history is words[1 .. t]: row r of step s at words[1] + s * rows + r
+            opt = lambda buf: buf[t].data_ptr() if self.trunc else None
+            return ("word_select", L.cvc_constrained_select_parts, head + (
+                self.top_k, self.top_p, self.rng.data_ptr() if self.sampling else None, t, self.words[t + 1].data_ptr(), 1,
+                self.logprob[t].data_ptr(), opt(getattr(self, "cutoff", None)), opt(getattr(self, "kept", None)),
+                self.words[1].data_ptr(), rows, self._cons_desc, self.nbanned[t].data_ptr()))
         tail = (self.rng.data_ptr(), t, self.words[t + 1].data_ptr(), 1, self.logprob[t].data_ptr())
         if not self.trunc:
             return ("word_select", L.cvc_sample_select_parts, head + tail)
@@ -513,7 +578,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
@@ -543,7 +608,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def run(self):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
         engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],
-        logprob [B*n, T]), row b * n + j = sample j of clip b.  Forced mode: (seq = the given words, att2_weights, logprob,
+        logprob [B*n, T]), row b * n + j = sample j of clip b; a constrained engine returns that tuple with or without a temperature.  Forced mode: (seq = the given words, att2_weights, logprob,
         rank [B*n, T] int32), row b * n + j = caption j of clip b."""
         if self.graph is not None:
             self.graph.replay()
@@ -553,7 +618,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()                           # the fallback's results
         if self.forced:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t(), self.rank.t()
-        if self.sampling:
+        if self.sampling or self.constrained:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t()
         if self.beam == 1:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2)

@@ -101,6 +101,12 @@ class LstmStep(C.Structure):
                 [("site", C.c_uint), ("p", C.c_float), ("h_dst1_q", C.c_void_p), ("h_dst2_q", C.c_void_p), ("w_cached", C.c_int)])
 
 
+class Constraint(C.Structure):
+    """cvc_constraint of include/cvc_hip_blocks.h: the rules of cvc_constrained_select_parts (the two lists are device memory)."""
+    _fields_ = [("no_repeat_ngram", C.c_int), ("no_immediate_repeat", C.c_int), ("min_len", C.c_int), ("nban", C.c_int),
+                ("ban", C.c_void_p), ("bad_end", C.c_void_p), ("nbad", C.c_int)]
+
+
 class TrainLoop(C.Structure):
     """cvc_train_loop of include/cvc_hip.h, field for field (tests/test_cabi.py compares the size with the C compiler's)."""
     _fields_ = (
@@ -236,6 +242,8 @@ SIGNATURES = {
     "cvc_sample_select_trunc_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P],
     "cvc_sample_advance": [_P, _P],
     "cvc_forced_select_parts": [_P, _I, _LL, _P, _I, _I, _P, _I, _P, _P, _P],
+    "cvc_constrained_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P, _LL, C.POINTER(Constraint),
+                                     _P, _P],
     # packed GEMMs with bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip; building blocks)
     "cvc_packed_lstm_bf16w_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P],
     "cvc_packed_linear_bf16w_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P],
@@ -276,7 +284,7 @@ BLOCKS = {
     "cvc_attn_bwd_pair", "cvc_ctxfeat_bwd_steps", "cvc_dproj_bwd_steps", "cvc_tile_gemm_big", "cvc_tile_gemm_plan", "cvc_linear_splitk_fwd", "cvc_linear_top2_fwd", "cvc_top2_final", "cvc_packed_lstm_fwd", "cvc_packed_linear_fwd",
     "cvc_packed_lstm_embgate_fwd", "cvc_packed_lstm_embgate_ex_fwd", "cvc_packed_lstm_late_fwd", "cvc_packed_lstm_train_fwd",
     "cvc_packed_lstm_train_pre_fwd", "cvc_packed_lstm_train_drop_fwd", "cvc_lstm_pointwise_bwd", "cvc_lstm_pointwise_bwd3",
-    "cvc_lstm_pointwise_bwd3_drop", "cvc_pack_lstm_weights", "cvc_linear_nn_planes_fwd", "cvc_linear_nn_planes2_fwd", "cvc_gru_seq_train_fwd", "cvc_lstm_pointwise_bwd4_pair", "cvc_beam_select_parts", "cvc_sample_select_parts", "cvc_sample_select_trunc_parts", "cvc_sample_advance", "cvc_forced_select_parts", "cvc_tile_lstm_finish",
+    "cvc_lstm_pointwise_bwd3_drop", "cvc_pack_lstm_weights", "cvc_linear_nn_planes_fwd", "cvc_linear_nn_planes2_fwd", "cvc_gru_seq_train_fwd", "cvc_lstm_pointwise_bwd4_pair", "cvc_beam_select_parts", "cvc_sample_select_parts", "cvc_sample_select_trunc_parts", "cvc_sample_advance", "cvc_forced_select_parts", "cvc_constrained_select_parts", "cvc_tile_lstm_finish",
     "cvc_tile_lstm_finish_embgate", "cvc_tile_reorder_pack", "cvc_decode_num_launches", "cvc_gemm_force_generic",
     "cvc_tile_gemm_loaders", "cvc_gru_persistent_waves8", "cvc_relu_dropout_fwd", "cvc_relu_dropout_bwd", "cvc_bn_workspace",
     "cvc_bn_relu_train_fwd", "cvc_bn_relu_train_bwd", "cvc_class_softmax_bwd", "cvc_layernorm_cat_bwd", "cvc_stable_order", "cvc_col_sum", "cvc_col_sum_ws", "cvc_attn_weighted_rows",

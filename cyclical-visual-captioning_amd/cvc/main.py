@@ -41,6 +41,12 @@ def main(argv=None, sample=None, score=None):
     parser.add_argument("--decode_weights", choices=("fp32", "bf16"), default="fp32",
                         help="precision of the caption decode's weight matrices: bf16 stores the six GEMM matrices rounded to bf16 "
                              "(greedy / one sample per clip, <= 64 rows; other decodes are refused, never run in fp32 instead)")
+    # constrained decoding (DecodeEngine; eval, cvc.sample): flags of this entry point, not of the reference's option surface
+    parser.add_argument("--no_repeat_ngram", type=int, default=0, help="never complete an n-gram the caption already holds; 0 = off")
+    parser.add_argument("--no_immediate_repeat", action="store_true", help="never choose the previous word again")
+    parser.add_argument("--min_caption_len", type=int, default=0, help="no end of sentence before this many words; 0 = off")
+    parser.add_argument("--ban_words", type=str, default="", help="comma-separated words (or word ids) that are never chosen")
+    parser.add_argument("--bad_endings", type=str, default="", help="comma-separated words (or word ids) a caption may not end on")
     parser.add_argument("--no_cfg", action="store_true", help="skip the YAML overlay (pure CLI)")
     parser.add_argument("--synthetic_raw", action="store_true",
                         help="feed raw frame / region features through the once-per-clip encoder (model/backbone.py) "
@@ -93,6 +99,10 @@ def main(argv=None, sample=None, score=None):
             opt.glove_clss, opt.glove_vg_cls = torch.from_numpy(full.glove_clss), torch.from_numpy(full.glove_vg_cls)
             opt.vg_cls, opt.detectron_tables = full.vg_cls, full.tables
 
+    if opt.no_repeat_ngram < 0 or opt.min_caption_len < 0:
+        raise SystemExit("--no_repeat_ngram and --min_caption_len must be >= 0")
+    opt.ban_word_ids = word_ids(opt.ban_words, opt.wtoi, "--ban_words")
+    opt.bad_ending_ids = word_ids(opt.bad_endings, opt.wtoi, "--bad_endings")
     model = build_model(opt, device)
     save_dir = os.path.join(opt.checkpoint_path, opt.exp_name)
 
@@ -188,6 +198,22 @@ def main(argv=None, sample=None, score=None):
         trainer._graphs.clear()                               # captured steps hold work on the communicator
         destroy_exchange_comm()
     return 0
+
+
+def word_ids(spec: str, wtoi, flag: str):
+    """"a,the,17" -> word ids: an entry is an integer id or a word of the dataset's vocabulary (wtoi); an unknown word is a
+    SystemExit that names it."""
+    out = []
+    for w in (x.strip() for x in (spec or "").split(",")):
+        if not w:
+            continue
+        if w.lstrip("-").isdigit():
+            out.append(int(w))
+        elif w in wtoi:
+            out.append(int(wtoi[w]))
+        else:
+            raise SystemExit("%s: unknown word %r (not in the dataset's vocabulary)" % (flag, w))
+    return out
 
 
 def _picklable(v):

@@ -99,6 +99,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # truncation of the sampled distribution (DecodeEngine top_k / top_p; 0 / 1.0 = off)
         self.sample_top_k = int(getattr(opts, "top_k", 0))
         self.sample_top_p = float(getattr(opts, "top_p", 1.0))
+        # constrained decoding (DecodeEngine no_repeat_ngram / no_immediate_repeat / min_len / ban_words / bad_endings; all off =
+        # the unconstrained engines); the two lists are word ids
+        self.no_repeat_ngram = int(getattr(opts, "no_repeat_ngram", 0))
+        self.no_immediate_repeat = bool(getattr(opts, "no_immediate_repeat", False))
+        self.min_caption_len = int(getattr(opts, "min_caption_len", 0))
+        self.ban_words = tuple(getattr(opts, "ban_word_ids", None) or ())
+        self.bad_endings = tuple(getattr(opts, "bad_ending_ids", None) or ())
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
         self.decode_weights_dtype = getattr(opts, "decode_weights", "fp32")
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
@@ -462,7 +469,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
     def _sample(self, segs_feat, seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats, frm_mask, sample_idx,
                 pnt_mask, beam_size: Optional[int] = None, sample_max: Optional[int] = None, temperature: Optional[float] = None,
                 sample_n: Optional[int] = None, seed: Optional[int] = None, decode_weights: Optional[str] = None,
-                top_k: Optional[int] = None, top_p: Optional[float] = None):
+                top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
+                no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -471,7 +479,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         top_k / top_p (arguments, else the model's sample_top_k / sample_top_p): top-k / nucleus truncation of the sampled
         distribution (DecodeEngine); logprob stays the model's log-prob over the full vocabulary.
         decode_weights: "fp32" / "bf16" (argument, else the model's opts.decode_weights): DecodeEngine's weights_dtype; what the
-        bf16 mode does not cover (beam search, sample_n > 1, more than 64 rows) raises, it never decodes in fp32 instead."""
+        bf16 mode does not cover (beam search, sample_n > 1, more than 64 rows) raises, it never decodes in fp32 instead.
+        no_repeat_ngram / no_immediate_repeat / min_len / ban_words / bad_endings (arguments, else the model's attributes, read from
+        opts): DecodeEngine's constrained decoding.  With any of them on the third result is the log-prob [B*n, T] in the arg-max
+        mode too; what the constrained engine does not cover (beam search) raises."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
             segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
@@ -485,11 +496,16 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         k = (self.sample_top_k if top_k is None else int(top_k)) if sampling else 0
         p = (self.sample_top_p if top_p is None else float(top_p)) if sampling else 1.0
         wdtype = self.decode_weights_dtype if decode_weights is None else decode_weights
+        cons = dict(no_repeat_ngram=self.no_repeat_ngram if no_repeat_ngram is None else no_repeat_ngram,
+                    no_immediate_repeat=self.no_immediate_repeat if no_immediate_repeat is None else no_immediate_repeat,
+                    min_len=self.min_caption_len if min_len is None else min_len,
+                    ban_words=tuple(self.ban_words if ban_words is None else ban_words),
+                    bad_endings=tuple(self.bad_endings if bad_endings is None else bad_endings))
         weights = self.decode_weights()
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p)
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, tuple(cons.values()))
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -502,12 +518,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 engine.load_features(feats)
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
-                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p)
+                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p, **cons)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)
         res = engine.run()
-        if sampling:
+        if sampling or engine.constrained:
             return res[0].clone(), res[1].clone(), res[2].clone()
         return res[0].clone(), res[1].clone(), None
 

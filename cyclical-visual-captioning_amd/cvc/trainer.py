@@ -664,10 +664,13 @@ class Trainer:
                                        write_grounding_json(grd_grd, o, stem=(stem or 'grd') + '-gt-sent-results', eval_mode='GT'))
         return stats
 
-    def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0):
+    def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
+               constraints: dict = None):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
         without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise);
         top_k / top_p truncate that distribution (0 / 1.0 = off; the log-probs stay the model's, over the full vocabulary).
+        constraints: keyword arguments of model._sample's constrained decoding (no_repeat_ngram, no_immediate_repeat, min_len,
+        ban_words, bad_endings); what is not given is the model's attribute, i.e. the run's options -- as in eval().
         Writes <results_dir>/<stem>_samples.json (rank 0, as eval does; stem defaults to densecap-<val_split>-<id>):
             {video: [{"segment": seg_idx, "timestamp": [start, end], "sentences": [n], "logprobs": [n]}]}
         logprobs[j]: the sum of the log-probs of sample j's words up to and including its first EOS (all T steps without one).
@@ -683,7 +686,7 @@ class Trainer:
                 seq, _, logprob = model._sample(b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"],
                                                 b["gt_bboxs"], b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"],
                                                 sample_max=0, temperature=temperature, sample_n=n, seed=seed, top_k=top_k,
-                                                top_p=top_p)
+                                                top_p=top_p, **(constraints or {}))
                 sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 # sequence log-prob: the steps up to and including the first EOS (word 0)

@@ -156,6 +156,39 @@ int cvc_sample_select_trunc_parts(const float* parts, int nparts, long long part
                                   int unk_idx, float inv_tau, int top_k, float top_p, const uint32_t* rng_state, int t,
                                   int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                   cvc_stream_t stream);
+/* Constrained decoding (csrc/constrain.hip): cvc_sample_select_trunc_parts over a candidate set that depends on the row's history.
+ * Step t chooses y_t for a row with history y_0 .. y_{t-1}: element (s, r) at hist[s * hist_stride + r], s < t (the engine's
+ * words[1 .. t]; BOS is not history).  Ban(t, r) is the union of
+ *   {unk_idx};   ban[0 .. nban): a fixed list of word ids;
+ *   no_repeat_ngram = n >= 1: every v for which some j, n-1 <= j <= t-1, has y_j = v and y_{j-n+1 .. j-1} = y_{t-n+1 .. t-1}
+ *       (n = 1: every earlier word; nothing is banned while t < n-1);
+ *   no_immediate_repeat: y_{t-1}, t >= 1;
+ *   min_len = L: word 0 while t < L;
+ *   bad_end[0 .. nbad): word 0 when t >= 1 and y_{t-1} is in the list
+ * and C0 = { v < V } \ Ban.  Both lists are device memory; ids outside [0, V) are ignored (nothing is read or written at them).
+ *   inv_tau == 0: arg-max mode -- word = argmax over C0 of z, ties -> lower index; rng_state may be NULL, top_k / top_p must be off
+ *   inv_tau > 0 : s, the hash counters and the noise of cvc_sample_select_parts with the arg-max over C0: the unconstrained
+ *                 sampler's word whenever that is allowed, else an exact draw from the renormalised distribution; top_k / top_p:
+ *                 the C1 / C2 of cvc_sample_select_trunc_parts with this C0 (top_k counts allowed words only)
+ *   logprob[r]  = the model's log-prob of the word (full V, banned words included in the log-sum-exp)
+ *   nbanned[r]  = |Ban|, distinct ids, UNK included (nullable); cutoff / kept (nullable) as in cvc_sample_select_trunc_parts
+ *   a row without a candidate: word 0, logprob -inf.  Steps after a row's first 0 are computed like any other step.
+ * t > 64, V > 8192 or M * V >= 2^32: CVC_E_TOOBIG.  n < 0, n > 64, min_len < 0, nban / nbad outside [0, 256], a NULL list with a
+ * non-zero count, truncation together with inv_tau == 0: CVC_E_BADARG.  Bitwise deterministic. */
+typedef struct cvc_constraint {
+    int no_repeat_ngram;            /* n; 0 = off */
+    int no_immediate_repeat;        /* 0 / 1 */
+    int min_len;                    /* L; 0 = off */
+    int nban;
+    const int32_t* ban;             /* device, nban ids */
+    const int32_t* bad_end;         /* device, nbad ids */
+    int nbad;
+} cvc_constraint;
+int cvc_constrained_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
+                                 int unk_idx, float inv_tau, int top_k, float top_p, const uint32_t* rng_state, int t,
+                                 int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
+                                 const int64_t* hist, long long hist_stride, const cvc_constraint* c, int32_t* nbanned,
+                                 cvc_stream_t stream);
 /* Teacher-forced decoding (csrc/forced.hip): the log-prob and the rank of a GIVEN word per row, one workgroup per row.
  *   z[r, :]    = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish -- the bits the other
  *                selection blocks see (nparts = 1, bias = NULL: a finished [M, V] logit matrix)
