@@ -1,6 +1,7 @@
 // Constrained decoding: the selection block that knows the row's history (DecodeEngine(no_repeat_ngram / no_immediate_repeat /
-// min_len / ban_words / bad_endings)).  The CONS flag of the sampling kernel (csrc/sample_select.h): the logit sum,
-// the hash counters, the noise, the truncation search and the log-prob are that kernel's, the candidates differ.
+// min_len / ban_words / bad_endings)).  The CONS flag of the sampling kernel (csrc/sample_select.h): the row loader
+// (csrc/select_row.h), the hash counters, the noise, the candidate mask, the truncation search and the log-prob are that kernel's;
+// the mask holds the row's ban set instead of UNK alone.  The top_k / top_p rules and the choice of form are select_run's, there too.
 //
 // Step t (0 .. T-1) chooses y_t for a row with history y_0 .. y_{t-1} = hist[0 .. t-1] (the engine's words[1 .. t]; BOS is not
 // history).  Ban(t, row) is the union of
@@ -20,8 +21,8 @@
 //   nbanned[r] = |Ban|: distinct ids, UNK included (nullable); cutoff / kept as in cvc_sample_select_trunc_parts (nullable)
 //   a row without a candidate: word 0, logprob -inf
 // The kernel: one workgroup of 256 per row; the history in LDS (t <= 64: one lane per j), the ban set as a V-bit map in LDS (at
-// most 256 words, LDS atomicOr), one barrier, then every thread turns its bits into a mask of its register slots (NC <= 32) which
-// stands wherever the plain kernel tests v != unk.  Every reduction runs in a fixed order: bitwise deterministic.
+// most 256 words, LDS atomicOr), one barrier, then every thread turns its bits into the mask of its register slots (NC <= 32) that
+// the unconstrained forms fill with UNK's slot alone.  Every reduction runs in a fixed order: bitwise deterministic.
 #include "sample_select.h"
 
 extern "C" int cvc_constrained_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
@@ -29,26 +30,15 @@ extern "C" int cvc_constrained_select_parts(const float* parts, int nparts, long
                                             int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                             const int64_t* hist, long long hist_stride, const cvc_constraint* c, int32_t* nbanned,
                                             cvc_stream_t stream) {
-    const bool argmax = inv_tau == 0.f;
-    const int rc = select_check(parts, nparts, part_stride, M, V, inv_tau, rng_state, t, word, word_stride, argmax);
+    const int rc = select_check(parts, nparts, part_stride, M, V, inv_tau, rng_state, t, word, word_stride, inv_tau == 0.f);
     if (rc != 0) return rc;
     if (t > CONS_T_MAX) return CVC_E_TOOBIG;
-    if (top_k < 0 || !isfinite(top_p) || !(top_p > 0.f) || top_p > 1.f) return CVC_E_BADARG;
     if (!c || c->no_repeat_ngram < 0 || c->no_repeat_ngram > CONS_T_MAX || c->min_len < 0) return CVC_E_BADARG;
     if (c->nban < 0 || c->nban > CONS_LIST_MAX || c->nbad < 0 || c->nbad > CONS_LIST_MAX) return CVC_E_BADARG;
     if ((c->nban > 0 && !c->ban) || (c->nbad > 0 && !c->bad_end)) return CVC_E_BADARG;
     if (t > 0 && (!hist || hist_stride < 1)) return CVC_E_BADARG;
-    if (top_k >= V - 1) top_k = 0;                         // |C0| <= V - 1: C1 = C0
-    const bool trunc = top_k > 0 || top_p < 1.f;
-    if (argmax && trunc) return CVC_E_BADARG;              // no distribution to truncate
     const ConsArgs ca{hist, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
                       c->bad_end, c->nbad, nbanned};
-    // cutoff / kept asked for without truncation: the truncating form with both searches off fills them from C0 (same word, same bits)
-    if (trunc || cutoff != nullptr || kept != nullptr)
-        select_launch<true, true>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, rng_state, t, word, word_stride, logprob,
-                                  TruncArgs{top_k, top_p, cutoff, kept}, stream, ca);
-    else
-        select_launch<false, true>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, rng_state, t, word, word_stride, logprob,
-                                   NoTrunc{}, stream, ca);
-    return cvc_launch_status();
+    return select_run<true>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, top_k, top_p, rng_state, t, word, word_stride,
+                            logprob, cutoff, kept, stream, ca);
 }

@@ -35,6 +35,16 @@ __device__ __forceinline__ float wave_sum(float v) {
     v += CVC_DPP(v, 0x143, 0xC);       // row_bcast31 -> rows 2, 3
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// wave_sum over integers (the DPP network moves 32-bit words: same steps, same masks)
+__device__ __forceinline__ int wave_sum_int(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+    return __builtin_amdgcn_readlane(v, 63);
+}
 __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, CVC_DPP_KEEP(v, 0xB1, 0xF));
     v = fmaxf(v, CVC_DPP_KEEP(v, 0x4E, 0xF));

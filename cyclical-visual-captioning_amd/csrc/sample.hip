@@ -13,7 +13,7 @@
 //
 // The state is 4 words of device memory {seed_lo, seed_hi, call, 0}; cvc_sample_advance adds 1 to `call` (the first launch of a
 // sampled decode, so a graph replay draws fresh noise).  Every reduction runs in a fixed order: the result is bitwise
-// deterministic.  The row's logits stay in registers (NC per thread, V <= 256 * SAMPLE_NC_MAX), loaded as float4 where V % 4 == 0.
+// deterministic.  The row's logits stay in registers (NC per thread, V <= 256 * NC_MAX), loaded as float4 where V % 4 == 0.
 //
 // Truncation (cvc_sample_select_trunc_parts; the TRUNC flag of the same kernel): the arg-max runs over a candidate set C2 only.
 //   C0 = { v < V, v != unk }
@@ -25,35 +25,15 @@
 // through LDS in a fixed order -- non-negative terms in a fixed order, so the predicate is monotone in the cutoff and the result
 // bitwise deterministic.  s, the hash counters and the log-prob (full V, the model's, independent of tau / top_k / top_p) are those
 // of the plain kernel; cutoff[r] = min over C2 of z, kept[r] = |C2| (a row without a candidate: kept 0, cutoff +inf, word 0).
+// With truncation off (top_k = 0 or >= V - 1, top_p = 1) the word and the log-prob are the plain form's bit for bit; cutoff / kept,
+// where asked for, come from the truncating form with both searches off (C2 = C0).
 //
-// The kernel and its dispatch live in csrc/sample_select.h, shared with the constrained block (csrc/constrain.hip); this file
-// holds the two entry points, the advance kernel and the candidates kernel of the untruncated form.
+// The kernel and the function behind the entry points (top_k / top_p rules, choice of form) live in csrc/sample_select.h, shared
+// with the constrained block (csrc/constrain.hip); the row loader, the shared argument checks and the dispatch in
+// csrc/select_row.h, shared with the forced block too.  This file holds the two entry points and the advance kernel.
 #include "sample_select.h"
 
 namespace {
-
-// cutoff / kept of a row that is not truncated: the minimum over C0 and |C0| (logits summed in the finishing pass's order)
-__global__ __launch_bounds__(WG) void sample_candidates_kernel(const float* parts, int nparts, long long part_stride, const float* bias,
-                                                               int V, int unk, float* cutoff, int32_t* kept) {
-    __shared__ float red_k[4], red_n[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* x = parts + (size_t)row * V;
-    float n = 0.f, zmin = INFINITY;
-    for (int v = tid; v < V; v += WG) {
-        float s = x[v];
-        for (int k = 1; k < nparts; ++k) s += x[(size_t)k * part_stride + v];
-        if (bias != nullptr) s += bias[v];
-        if (v != unk && s == s) { n += 1.f; zmin = fminf(zmin, s); }
-    }
-    n = wave_sum(n);
-    zmin = -wave_max(-zmin);
-    if (lane == 0) { red_k[wave] = n; red_n[wave] = zmin; }
-    __syncthreads();
-    if (tid == 0) {
-        if (cutoff != nullptr) cutoff[row] = fminf(fminf(red_n[0], red_n[1]), fminf(red_n[2], red_n[3]));
-        if (kept != nullptr) kept[row] = (int32_t)((red_k[0] + red_k[1]) + (red_k[2] + red_k[3]));
-    }
-}
 
 __global__ void sample_advance_kernel(uint32_t* state) {
     if (threadIdx.x == 0) state[2] = state[2] + 1u;
@@ -66,9 +46,8 @@ extern "C" int cvc_sample_select_parts(const float* parts, int nparts, long long
                                        float* logprob, cvc_stream_t stream) {
     const int rc = select_check(parts, nparts, part_stride, M, V, inv_tau, rng_state, t, word, word_stride);
     if (rc != 0) return rc;
-    select_launch<false>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, rng_state, t, word, word_stride, logprob, NoTrunc{},
-                         stream);
-    return cvc_launch_status();
+    return select_run<false>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, 0, 1.f, rng_state, t, word, word_stride, logprob,
+                             nullptr, nullptr, stream);
 }
 
 extern "C" int cvc_sample_select_trunc_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
@@ -77,19 +56,8 @@ extern "C" int cvc_sample_select_trunc_parts(const float* parts, int nparts, lon
                                              cvc_stream_t stream) {
     const int rc = select_check(parts, nparts, part_stride, M, V, inv_tau, rng_state, t, word, word_stride);
     if (rc != 0) return rc;
-    if (top_k < 0 || !isfinite(top_p) || !(top_p > 0.f) || top_p > 1.f) return CVC_E_BADARG;
-    if (top_k >= V - 1) top_k = 0;                         // |C0| <= V - 1: C1 = C0
-    if (top_k == 0 && top_p == 1.f) {                      // truncation off: the plain kernel, then C0's minimum and size if asked for
-        select_launch<false>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, rng_state, t, word, word_stride, logprob,
-                             NoTrunc{}, stream);
-        if (cutoff != nullptr || kept != nullptr)
-            hipLaunchKernelGGL(sample_candidates_kernel, dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, bias, V,
-                               unk_idx, cutoff, kept);
-        return cvc_launch_status();
-    }
-    select_launch<true>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, rng_state, t, word, word_stride, logprob,
-                        TruncArgs{top_k, top_p, cutoff, kept}, stream);
-    return cvc_launch_status();
+    return select_run<false>(parts, nparts, part_stride, bias, M, V, unk_idx, inv_tau, top_k, top_p, rng_state, t, word, word_stride,
+                             logprob, cutoff, kept, stream);
 }
 
 extern "C" int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream) {

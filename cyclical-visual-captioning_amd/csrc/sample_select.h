@@ -1,16 +1,15 @@
-// The selection kernel of sampled decoding and its dispatch, shared by csrc/sample.hip (cvc_sample_select_parts /
-// cvc_sample_select_trunc_parts: contract in that file's header comment) and csrc/constrain.hip (cvc_constrained_select_parts:
-// the CONS flag of the same kernel, contract in that file).  One definition of the logit sum, the hash counters, the noise, the
-// truncation search and the log-prob: every form rounds alike.
+// The selection kernel of sampled decoding and the one function behind its entry points, shared by csrc/sample.hip
+// (cvc_sample_select_parts / cvc_sample_select_trunc_parts: contract in that file's header comment) and csrc/constrain.hip
+// (cvc_constrained_select_parts: the CONS flag of the same kernel, contract in that file).  One definition of the hash counters, the
+// noise, the candidate mask, the truncation search and the log-prob: every form rounds alike.  The row loader, the shared argument
+// checks and the NC / NP / VEC dispatch are those of every selection block (csrc/select_row.h).
 #pragma once
-#include "cvc_common.h"
+#include "select_row.h"
 #include "dropout_rng.h"
 #include <math.h>
 
 namespace {
 
-constexpr int WG = 256;
-constexpr int SAMPLE_NC_MAX = 32;              // logits per thread: V <= 8192, the bound of cvc_beam_select_parts
 constexpr uint32_t KEY_NEG_INF = 0x007fffffu;  // key of -inf: no float compares below it
 
 // what the truncating form of the kernel takes on top of the plain one's arguments (the plain one: nothing)
@@ -45,12 +44,10 @@ __device__ __forceinline__ float gumbel(uint32_t h) {
     return -logf(-logf(u));
 }
 
-// NC logits per thread; NP > 0: that many slabs summed with an unrolled loop, NP == 0: nparts at run time.  VEC (V % 4 == 0,
-// 16-byte aligned operands): NC / 4 float4 groups, element u at column (tid + (u / 4) * WG) * 4 + u % 4; otherwise column tid + u * WG.
-// Both sum a column's slabs in the same order (same bits); only the loads differ.
+// NC / NP / VEC: the loader form (csrc/select_row.h).  The candidates are the words whose register slot is not in the thread's
+// `banned` mask: UNK, and with CONS the row's whole ban set (a V-bit map in LDS, built from the history and the lists).
 // TRUNC: the cutoff search of the header comment in front of the Gumbel-max; the noise is then drawn for the kept words only.
-// CONS: the candidates are the words outside the row's ban set (a V-bit map in LDS, built from the history and the lists, then one
-// bit per register slot) instead of the words other than UNK; inv_tau == 0 is then the arg-max mode (s = z, no noise, state unread).
+// CONS: inv_tau == 0 is the arg-max mode (s = z, no noise, state unread).
 template <int NC, int NP, bool VEC, bool TRUNC, bool CONS>
 __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, int nparts, long long part_stride, const float* bias,
                                                            int V, int unk, float inv_tau, const uint32_t* state, uint32_t site,
@@ -65,48 +62,13 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
     const bool noisy = !CONS || inv_tau != 0.f;
     uint32_t seed_lo = 0, seed_hi = 0, call = 0;
     if (noisy) { seed_lo = state[0]; seed_hi = state[1]; call = state[2]; }
-    const float* x = parts + (size_t)row * V;
     float z[NC];
-    auto col = [&](int u) { return VEC ? (tid + (u >> 2) * WG) * 4 + (u & 3) : tid + u * WG; };
-    if constexpr (VEC) {
-#pragma unroll
-        for (int g = 0; g < NC / 4; ++g) {
-            const int e = (tid + g * WG) * 4;
-            f32x4 s = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (e < V) {                                  // V % 4 == 0: the whole group is inside the row
-                if constexpr (NP > 0) {
-                    f32x4 p[NP];
-#pragma unroll
-                    for (int k = 0; k < NP; ++k) p[k] = ld4(x + (size_t)k * part_stride + e);
-                    s = p[0];
-#pragma unroll
-                    for (int k = 1; k < NP; ++k) s += p[k];
-                } else {
-                    s = ld4(x + e);
-                    for (int k = 1; k < nparts; ++k) s += ld4(x + (size_t)k * part_stride + e);
-                }
-                if (bias != nullptr) s += ld4(bias + e);
-            }
-            z[4 * g] = s.x; z[4 * g + 1] = s.y; z[4 * g + 2] = s.z; z[4 * g + 3] = s.w;
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < NC; ++u) {
-            const int v = col(u);
-            float s = -INFINITY;
-            if (v < V) {
-                s = x[v];
-                for (int k = 1; k < nparts; ++k) s += x[(size_t)k * part_stride + v];
-                if (bias != nullptr) s += bias[v];
-            }
-            z[u] = s;
-        }
-    }
-    // CONS: bit u of `banned` = the word of register slot u is in the row's ban set
-    [[maybe_unused]] uint32_t banned = 0;
-    [[maybe_unused]] float se_full = 0.f;
+    load_logit_row<NC, NP, VEC>(parts + (size_t)row * V, nparts, part_stride, bias, V, tid, z);
+    auto col = [&](int u) { return ::col<VEC>(tid, u); };
+    // bit u of `banned` = the word of register slot u is not a candidate: UNK, with CONS any word of the row's ban set
+    static_assert(NC <= 32, "one ban bit per register slot");
+    uint32_t banned = 0;
     if constexpr (CONS) {
-        static_assert(NC <= 32, "one ban bit per register slot");
         __shared__ uint32_t bits[WG];                       // V <= 32 * WG
         __shared__ long long hist[CONS_T_MAX];
         const int t = ca.t;
@@ -132,30 +94,24 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
             const int v = col(u);
             if (v < V && ((bits[v >> 5] >> (v & 31)) & 1u)) banned |= 1u << u;
         }
-        int nb = __popc(bits[tid]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o, 64);
+        const int nb = wave_sum_int(__popc(bits[tid]));
         if (lane == 0) red_b[wave] = nb;                    // read by thread 0 after the barriers below
+    } else {
+        banned = slot_bit<VEC>(tid, unk, V);                // the one slot with col(u) == unk, without NC compares
     }
     // perturbed scores: the best (s, v) and its logit; the row's maximum logit
     float bs = -INFINITY, bz = -INFINITY, m = -INFINITY;
     int bi = 0x7fffffff;
     const uint32_t base = (uint32_t)row * (uint32_t)V;
-    [[maybe_unused]] float theta = -INFINITY, z_unk = -INFINITY, nkept = 0.f, zmin = INFINITY;
+    [[maybe_unused]] float theta = -INFINITY, se_full = 0.f, nkept = 0.f, zmin = INFINITY;
     if constexpr (TRUNC) {
         __shared__ float red_c[4], red_p[2][4];
-        // the row's maximum (UNK included: the log-prob's), then UNK leaves the candidates: its slot holds -inf like the padding
-        // (neither is ever counted: no probe runs at a cutoff of -inf, the last pass tests v) and the thread that owns it keeps z_unk
+        // the row's maximum (banned words included: the log-prob's) and the candidates' maximum
         float mc = -INFINITY;
 #pragma unroll
         for (int u = 0; u < NC; ++u) {
             m = fmaxf(m, z[u]);
-            if constexpr (CONS) {
-                if (!((banned >> u) & 1u)) mc = fmaxf(mc, z[u]);
-            } else {
-                if (col(u) == unk) { z_unk = z[u]; z[u] = -INFINITY; }
-                mc = fmaxf(mc, z[u]);
-            }
+            mc = fmaxf(mc, ((banned >> u) & 1u) ? -INFINITY : z[u]);
         }
         m = wave_max(m);
         mc = wave_max(mc);
@@ -163,17 +119,15 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
         __syncthreads();
         m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
         mc = fmaxf(fmaxf(red_c[0], red_c[1]), fmaxf(red_c[2], red_c[3]));
-        if constexpr (CONS) {
-            // many slots may leave the candidates: the thread's share of the log-sum-exp (the last pass's terms in its order) is taken
-            // now, then every banned slot holds -inf like the padding
-            if (m != -INFINITY) {
+        // the thread's share of the log-sum-exp over the full row (the plain form's terms in its order) is taken now; then every banned
+        // slot holds -inf like the padding (neither is ever counted: no probe runs at a cutoff of -inf, the last pass tests the mask)
+        if (m != -INFINITY) {
 #pragma unroll
-                for (int u = 0; u < NC; ++u) se_full += expf(z[u] - m);
-            }
-#pragma unroll
-            for (int u = 0; u < NC; ++u)
-                if ((banned >> u) & 1u) z[u] = -INFINITY;
+            for (int u = 0; u < NC; ++u) se_full += expf(z[u] - m);          // padding: exp(-inf) = 0
         }
+#pragma unroll
+        for (int u = 0; u < NC; ++u)
+            if ((banned >> u) & 1u) z[u] = -INFINITY;
         // workgroup sum in a fixed order; alternating slots: one barrier per probe
         int slot = 0;
         auto wg_sum = [&](float x) {
@@ -232,8 +186,8 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
         const int v = col(u);
         if (v < V) {
             if constexpr (!TRUNC) m = fmaxf(m, z[u]);
-            bool cand = CONS ? !((banned >> u) & 1u) : v != unk;
-            if constexpr (TRUNC) cand = cand && z[u] >= theta;
+            bool cand = !((banned >> u) & 1u);
+            if constexpr (TRUNC) cand = z[u] >= theta && cand;          // this order: one branch per slot (profiles/select_blocks_merge.md)
             if (cand) {
                 float s;
                 if (noisy) s = z[u] * inv_tau + gumbel(cvc_drop_hash(seed_lo, seed_hi, call, site, base + (uint32_t)v));
@@ -257,21 +211,14 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
         __syncthreads();
         nkept = (red_k[0] + red_k[1]) + (red_k[2] + red_k[3]);
         zmin = fminf(fminf(red_n[0], red_n[1]), fminf(red_n[2], red_n[3]));
-        if constexpr (!CONS) {
-#pragma unroll
-            for (int u = 0; u < NC; ++u)
-                if (col(u) == unk) z[u] = z_unk;           // the log-sum-exp runs over the full row
-        }
     } else {
         m = wave_max(m);
         if (lane == 0) { red_m[wave] = m; red_v[wave] = bs; red_i[wave] = bi; red_z[wave] = bz; }
         __syncthreads();
         m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
     }
-    float se = 0.f;
-    if constexpr (TRUNC && CONS) {
-        se = se_full;
-    } else if (m != -INFINITY) {
+    float se = se_full;
+    if (!TRUNC && m != -INFINITY) {
 #pragma unroll
         for (int u = 0; u < NC; ++u) se += expf(z[u] - m);          // padding: exp(-inf) = 0
     }
@@ -299,47 +246,35 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
 
 }  // namespace
 
-// argument checks shared by the entry points (argmax: the constrained block's mode without noise, inv_tau == 0 and no state)
+// argument checks of the entry points on top of select_row_check (argmax: the constrained block's mode without noise, inv_tau == 0
+// and no state)
 static int select_check(const float* parts, int nparts, long long part_stride, int M, int V, float inv_tau, const uint32_t* rng_state,
                         int t, const int64_t* word, int word_stride, bool argmax = false) {
-    if (!parts || (!rng_state && !argmax) || !word || nparts < 1 || M < 1 || V < 2 || word_stride < 1 || t < 0) return CVC_E_BADARG;
+    if ((!rng_state && !argmax) || t < 0) return CVC_E_BADARG;
     if (!argmax && (!(inv_tau > 0.f) || !isfinite(inv_tau))) return CVC_E_BADARG;
-    if (nparts > 1 && part_stride < (long long)M * V) return CVC_E_BADARG;
-    if ((long long)M * V > 0xffffffffLL) return CVC_E_TOOBIG;          // the hash counter r * V + v is one 32-bit word
-    if ((V + WG - 1) / WG > SAMPLE_NC_MAX) return CVC_E_TOOBIG;
-    return 0;
+    return select_row_check(parts, nparts, part_stride, M, V, word, word_stride);
 }
 
-// one dispatch for both forms: the same NC / NP / VEC choice, the TRUNC flag and its arguments on top
-template <bool TRUNC, bool CONS = false>
-static void select_launch(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V, int unk_idx,
-                          float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
-                          typename trunc_args<TRUNC>::type ta, cvc_stream_t stream, typename cons_args<CONS>::type ca = {}) {
-    const int nc = (V + WG - 1) / WG;
+// behind every entry point, after select_check: the top_k / top_p rules and the choice of form.  cutoff / kept asked for without
+// truncation: the truncating form with both searches off fills them from C0 (same word, same bits as the plain form)
+template <bool CONS>
+static int select_run(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V, int unk_idx, float inv_tau,
+                      int top_k, float top_p, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
+                      float* cutoff, int32_t* kept, cvc_stream_t stream, typename cons_args<CONS>::type ca = {}) {
+    if (top_k < 0 || !isfinite(top_p) || !(top_p > 0.f) || top_p > 1.f) return CVC_E_BADARG;
+    if (top_k >= V - 1) top_k = 0;                         // |C0| <= V - 1: C1 = C0
+    const bool trunc = top_k > 0 || top_p < 1.f;
+    if (inv_tau == 0.f && trunc) return CVC_E_BADARG;      // the arg-max mode: no distribution to truncate
     const uint32_t site = CVC_SAMPLE_SITE + (uint32_t)t;
-    const bool vec = (V & 3) == 0 && ((uintptr_t)parts & 15) == 0 && (nparts == 1 || (part_stride & 3) == 0) &&
-                     ((uintptr_t)bias & 15) == 0;
-#define CVC_SS(NC_, NP_, VEC_) hipLaunchKernelGGL((sample_select_kernel<NC_, NP_, VEC_, TRUNC, CONS>), dim3(M), dim3(WG), 0, \
-                                                  (hipStream_t)stream, parts, nparts, part_stride, bias, V, unk_idx, inv_tau, rng_state, \
-                                                  site, word, word_stride, logprob, ta, ca)
-#define CVC_SS_NP(NG_) do { switch (nparts) { case 1: CVC_SS(4 * NG_, 1, true); break; case 2: CVC_SS(4 * NG_, 2, true); break; \
-                                              case 4: CVC_SS(4 * NG_, 4, true); break; case 6: CVC_SS(4 * NG_, 6, true); break; \
-                                              case 8: CVC_SS(4 * NG_, 8, true); break; default: CVC_SS(4 * NG_, 0, true); break; } \
-                           } while (0)
-    if (vec) {                                             // float4 groups: V <= NG * 1024
-        const int ng = (V + 4 * WG - 1) / (4 * WG);
-        if (ng <= 1) CVC_SS_NP(1);
-        else if (ng <= 2) CVC_SS_NP(2);
-        else if (ng <= 4) CVC_SS_NP(4);
-        else if (ng <= 5) CVC_SS_NP(5);
-        else CVC_SS_NP(8);
-    } else if (nc <= 1) CVC_SS(1, 0, false);
-    else if (nc <= 2) CVC_SS(2, 0, false);
-    else if (nc <= 4) CVC_SS(4, 0, false);
-    else if (nc <= 8) CVC_SS(8, 0, false);
-    else if (nc <= 16) CVC_SS(16, 0, false);
-    else if (nc <= 20) CVC_SS(20, 0, false);
-    else CVC_SS(32, 0, false);
-#undef CVC_SS_NP
-#undef CVC_SS
+    auto launch = [&](auto trunc_, auto ta) {
+        select_dispatch(parts, nparts, part_stride, bias, V, [&](auto nc, auto np, auto vec) {
+            hipLaunchKernelGGL((sample_select_kernel<decltype(nc)::value, decltype(np)::value, decltype(vec)::value,
+                                                     decltype(trunc_)::value, CONS>),
+                               dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, bias, V, unk_idx, inv_tau, rng_state,
+                               site, word, word_stride, logprob, ta, ca);
+        });
+    };
+    if (trunc || cutoff != nullptr || kept != nullptr) launch(std::true_type{}, TruncArgs{top_k, top_p, cutoff, kept});
+    else launch(std::false_type{}, NoTrunc{});
+    return cvc_launch_status();
 }

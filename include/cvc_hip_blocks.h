@@ -125,7 +125,9 @@ int cvc_beam_select_parts(const float* parts, int nparts, long long part_stride,
                           const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx,
                           int first_step, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
                           float* workspace, cvc_stream_t stream);
-/* Sampled decoding (csrc/sample.hip): Gumbel-max sampling from softmax(z / tau) without UNK, one workgroup per row.
+/* Sampled decoding (csrc/sample.hip; the kernel in csrc/sample_select.h, the row loader, the argument checks and the dispatch that
+ * every selection block below shares in csrc/select_row.h): Gumbel-max sampling from softmax(z / tau) without UNK, one workgroup
+ * per row.
  *   z[r, :]  = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish (nparts = 1, bias = NULL:
  *              a finished [M, V] logit matrix); slab p starts part_stride floats after slab p-1
  *   h        = cvc_drop_hash(seed_lo, seed_hi, call, CVC_SAMPLE_SITE + t, r * V + v)      (csrc/dropout_rng.h)
@@ -149,14 +151,15 @@ int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream);
  *   word[r * word_stride] = argmax over v in C2 of s: the word cvc_sample_select_parts draws from the same state, if that lies in C2
  *   logprob[r] = the model's log-prob of the word (full V, independent of tau, top_k, top_p; NOT the truncated distribution's)
  *   cutoff[r] = min over C2 of z, kept[r] = |C2| (both nullable)
- * top_k < 0, top_p outside (0, 1] or not finite: CVC_E_BADARG.  Truncation off (top_k == 0 or >= V - 1, and top_p == 1): the
- * plain kernel is launched (same bits as cvc_sample_select_parts), cutoff / kept are filled from C0 if given.  Bitwise
- * deterministic. */
+ * top_k < 0, top_p outside (0, 1] or not finite: CVC_E_BADARG.  Truncation off (top_k == 0 or >= V - 1, and top_p == 1): word and
+ * logprob have the bits of cvc_sample_select_parts -- the plain kernel is launched, or, if cutoff / kept are given, the truncating
+ * one with both searches off, which fills them from C0.  Bitwise deterministic. */
 int cvc_sample_select_trunc_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
                                   int unk_idx, float inv_tau, int top_k, float top_p, const uint32_t* rng_state, int t,
                                   int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                   cvc_stream_t stream);
-/* Constrained decoding (csrc/constrain.hip): cvc_sample_select_trunc_parts over a candidate set that depends on the row's history.
+/* Constrained decoding (csrc/constrain.hip; the CONS flag of the kernel in csrc/sample_select.h): cvc_sample_select_trunc_parts
+ * over a candidate set that depends on the row's history.
  * Step t chooses y_t for a row with history y_0 .. y_{t-1}: element (s, r) at hist[s * hist_stride + r], s < t (the engine's
  * words[1 .. t]; BOS is not history).  Ban(t, r) is the union of
  *   {unk_idx};   ban[0 .. nban): a fixed list of word ids;
@@ -189,7 +192,8 @@ int cvc_constrained_select_parts(const float* parts, int nparts, long long part_
                                  int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                  const int64_t* hist, long long hist_stride, const cvc_constraint* c, int32_t* nbanned,
                                  cvc_stream_t stream);
-/* Teacher-forced decoding (csrc/forced.hip): the log-prob and the rank of a GIVEN word per row, one workgroup per row.
+/* Teacher-forced decoding (csrc/forced.hip; row loader, argument checks and dispatch of csrc/select_row.h): the log-prob and the
+ * rank of a GIVEN word per row, one workgroup per row.
  *   z[r, :]    = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish -- the bits the other
  *                selection blocks see (nparts = 1, bias = NULL: a finished [M, V] logit matrix)
  *   w          = word[r * word_stride], read only (the block writes no word); w outside [0, V): logprob[r] = NaN, rank[r] = -1,
@@ -197,7 +201,7 @@ int cvc_constrained_select_parts(const float* parts, int nparts, long long part_
  *   logprob[r] = z[r, w] - logsumexp_v z[r, v]   (nullable; full V, UNK included: the definition of cvc_sample_select_parts)
  *   rank[r]    = #{v : z[r, v] > z[r, w]} + #{v < w : z[r, v] == z[r, w]}   (nullable; 0 <=> w is the arg-max under the lower-index
  *                tie rule; NaN logits compare false)
- * V <= 8192, M * V < 2^32 (CVC_E_TOOBIG otherwise); the argument checks of cvc_sample_select_parts.  Bitwise deterministic. */
+ * V <= 8192, M * V < 2^32 (CVC_E_TOOBIG otherwise); the argument checks every selection block shares.  Bitwise deterministic. */
 int cvc_forced_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V,
                             const int64_t* word, int word_stride, float* logprob, int32_t* rank, cvc_stream_t stream);
 int cvc_tile_lstm_finish(const float* parts, int nparts, long long part_stride, const float* b_ih, const float* b_hh,

@@ -1,5 +1,5 @@
-"""Teacher-forced decode on the GPU (pytest -m gpu): the selection block (csrc/forced.hip) against tests/forced_ref.py, the engine's
-three paths against the CPU oracle over given words, graph replay across caption sets, consistency with the greedy engine, the
+"""Teacher-forced decode on the GPU (pytest -m gpu): the selection block (csrc/forced.hip) against tests/forced_ref.py and, on the
+words they draw, against the sampling blocks bit for bit (one row loader: csrc/select_row.h), the engine's three paths against the CPU oracle over given words, graph replay across caption sets, consistency with the greedy engine, the
 frame-masked output against the oracle's training pass, and the model / trainer plumbing."""
 import functools
 import json
@@ -10,6 +10,8 @@ import torch
 
 from cvc import synth
 import forced_ref as FR
+import test_gpu_sampling as TS               # the plain sampling block's launcher, the generator state
+import test_gpu_sampling_trunc as TT         # the truncating block's launcher
 from test_gpu_sampling import SEQ_TOL, LOGPROB_TOL
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +118,36 @@ def test_forced_block_vs_reference(dev, M, V, nparts, with_bias):
     rc5, none5, rk5 = forced_block(pd_, bd, wd, V, logprob=False)
     assert rc4 == 0 and rc5 == 0 and none4 is None and none5 is None
     assert torch.equal(bits(lp), bits(lp4)) and torch.equal(rk, rk5)
+
+
+# ------------------------------------------------------------------ one row loader for every selection block
+@pytest.mark.parametrize("M,V,nparts,with_bias", [(3, 33, 2, True),         # scalar loads, 1 logit per thread
+                                                  (64, 52, 2, True),        # float4, 2 unrolled slabs
+                                                  (5, 5000, 6, True),       # float4, 5 groups, 6 unrolled slabs: the production V
+                                                  (64, 4999, 1, False),     # scalar loads, 20 logits per thread
+                                                  (33, 8192, 3, True)])     # float4, 8 groups, run-time slab loop
+def test_forced_logprob_of_a_drawn_word_is_the_sampling_blocks_bit_for_bit(dev, M, V, nparts, with_bias):
+    """the forced block, given the word a sampling block drew, returns that block's log-prob bit for bit on every row: the same
+    logits (slab sum in the same order), the same log-sum-exp terms in the same order.  UNK holds the row maximum on every third
+    row: out of the samplers' candidates, inside every log-sum-exp."""
+    unk, inv_tau, t = synth.UNK_IDX, float(np.float32(1.0 / 0.7)), 5
+    g = torch.Generator().manual_seed(M * 131 + V + nparts + 11)
+    parts = torch.randn(nparts, M, V, generator=g) * (1.5 / np.sqrt(nparts))
+    bias = torch.randn(V, generator=g) * 0.3 if with_bias else None
+    parts[0, 0::3, unk] += 60.0
+    z = FR.finished(parts, bias)
+    assert (z[0::3].argmax(1) == unk).all()
+    pd_, bd = parts.contiguous().to(dev), None if bias is None else bias.to(dev)
+    state = TS.state_words(12345 + M + V, 3).to(dev)
+    w_plain, lp_plain = TS.select_block(pd_, bd, V, unk, inv_tau, state, t)
+    w_trunc, lp_trunc, _, _ = TT.trunc_block(pd_, bd, V, unk, inv_tau, 40, 0.9, state, t)
+    for label, w, lp in (("plain", w_plain, lp_plain), ("top_k 40, top_p 0.9", w_trunc, lp_trunc)):
+        assert int(w.min()) >= 0 and int(w.max()) < V and not bool((w == unk).any()) and bool(torch.isfinite(lp).all()), label
+        rc, lp_f, _ = forced_block(pd_, bd, w, V)
+        assert rc == 0
+        differ = int((bits(lp_f) != bits(lp)).sum())
+        print(f"[forced vs {label}] M={M} V={V} nparts={nparts}: {differ} of {M} rows differ in the log-prob's bits")
+        assert torch.equal(bits(lp_f), bits(lp)), label
 
 
 def test_forced_block_word_stride_and_argument_checks(dev):
