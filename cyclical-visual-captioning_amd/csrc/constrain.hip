@@ -33,9 +33,7 @@ extern "C" int cvc_constrained_select_parts(const float* parts, int nparts, long
     const int rc = select_check(parts, nparts, part_stride, M, V, inv_tau, rng_state, t, word, word_stride, inv_tau == 0.f);
     if (rc != 0) return rc;
     if (t > CONS_T_MAX) return CVC_E_TOOBIG;
-    if (!c || c->no_repeat_ngram < 0 || c->no_repeat_ngram > CONS_T_MAX || c->min_len < 0) return CVC_E_BADARG;
-    if (c->nban < 0 || c->nban > CONS_LIST_MAX || c->nbad < 0 || c->nbad > CONS_LIST_MAX) return CVC_E_BADARG;
-    if ((c->nban > 0 && !c->ban) || (c->nbad > 0 && !c->bad_end)) return CVC_E_BADARG;
+    if (!c || cons_rules_check(c) != 0) return CVC_E_BADARG;
     if (t > 0 && (!hist || hist_stride < 1)) return CVC_E_BADARG;
     const ConsArgs ca{hist, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
                       c->bad_end, c->nbad, nbanned};

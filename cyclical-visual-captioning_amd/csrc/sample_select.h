@@ -5,6 +5,7 @@
 // checks and the NC / NP / VEC dispatch are those of every selection block (csrc/select_row.h).
 #pragma once
 #include "select_row.h"
+#include "ban_set.h"
 #include "dropout_rng.h"
 #include <math.h>
 
@@ -18,19 +19,7 @@ struct TruncArgs { int top_k; float top_p; float* cutoff; int32_t* kept; };
 template <bool TRUNC> struct trunc_args { using type = NoTrunc; };
 template <> struct trunc_args<true> { using type = TruncArgs; };
 
-// what the constrained form takes on top (csrc/constrain.hip): the row's history hist[s * hist_stride + row], s < t, and the rules
-constexpr int CONS_T_MAX = 64;                 // history steps: one lane per step
-constexpr int CONS_LIST_MAX = 256;             // entries of a list: one thread per entry
-struct NoCons {};
-struct ConsArgs {
-    const int64_t* hist; long long hist_stride; int t;
-    int ngram, immediate, min_len;
-    const int32_t* ban; int nban;
-    const int32_t* bad_end; int nbad;
-    int32_t* nbanned;
-};
-template <bool CONS> struct cons_args { using type = NoCons; };
-template <> struct cons_args<true> { using type = ConsArgs; };
+// what the constrained form takes on top (csrc/constrain.hip): ConsArgs of csrc/ban_set.h, the row's history and the rules
 
 // the float of an order-preserving key: key(a) < key(b) <=> a < b over the non-NaN floats (-0 below +0; keys above key(+inf) and
 // below KEY_NEG_INF are NaNs)
@@ -45,7 +34,7 @@ __device__ __forceinline__ float gumbel(uint32_t h) {
 }
 
 // NC / NP / VEC: the loader form (csrc/select_row.h).  The candidates are the words whose register slot is not in the thread's
-// `banned` mask: UNK, and with CONS the row's whole ban set (a V-bit map in LDS, built from the history and the lists).
+// `banned` mask: UNK, and with CONS the row's whole ban set (a V-bit map in LDS, built from the history and the lists: csrc/ban_set.h).
 // TRUNC: the cutoff search of the header comment in front of the Gumbel-max; the noise is then drawn for the kept words only.
 // CONS: inv_tau == 0 is the arg-max mode (s = z, no noise, state unread).
 template <int NC, int NP, bool VEC, bool TRUNC, bool CONS>
@@ -71,24 +60,7 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
     if constexpr (CONS) {
         __shared__ uint32_t bits[WG];                       // V <= 32 * WG
         __shared__ long long hist[CONS_T_MAX];
-        const int t = ca.t;
-        bits[tid] = 0u;
-        if (tid < t) hist[tid] = ca.hist[(size_t)tid * ca.hist_stride + row];
-        __syncthreads();
-        auto ban = [&](long long v) { if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31)); };
-        if (tid == 0) {
-            ban(unk);
-            if (t < ca.min_len) ban(0);
-            if (ca.immediate && t >= 1) ban(hist[t - 1]);
-        }
-        if (tid < ca.nban) ban(ca.ban[tid]);
-        if (t >= 1 && tid < ca.nbad && (long long)ca.bad_end[tid] == hist[t - 1]) ban(0);
-        if (ca.ngram >= 1 && tid < t && tid >= ca.ngram - 1) {          // lane j: y_j is banned if the n - 1 words before it are the last n - 1
-            bool same = true;
-            for (int i = 1; i < ca.ngram; ++i) same = same && hist[tid - i] == hist[t - i];
-            if (same) ban(hist[tid]);
-        }
-        __syncthreads();
+        build_ban_map<WG>(ca, load_hist_step(ca, row, tid), V, unk, tid, bits, hist);   // (both barriers inside)
 #pragma unroll
         for (int u = 0; u < NC; ++u) {
             const int v = col(u);

@@ -7,6 +7,7 @@
 #include "cvc_common.h"
 #include "gsk.h"
 #include "dropout_rng.h"
+#include "ban_set.h"
 #include <math.h>
 
 namespace {
@@ -657,10 +658,16 @@ constexpr int ROW_CACHE = 32;        // values per thread kept in registers: V <
 // VEC == false (the general form: any V, any alignment, any number of slabs): scalar, bounds-checked loads and a run-time slab loop
 // in the same order, then the SAME code -- its log-sum-exp, candidates and scores are the fast form's bit for bit on the same
 // values (tests/test_gpu_tile_path.py; history and figures: profiles/tile_path_pins.md).
-template <int NG, int NP = 0, bool VEC = true>      // float4 groups per thread: V <= NG * 1024
+// HIST (cvc_beam_select_hist_parts): the row is a hypothesis with a history of its own (ca.hist, ca.t) and the rules of constrained
+// decoding.  After the row's loads are issued and its (max, sum) share is taken -- the log-sum-exp runs over the full row -- the
+// row's ban set is built as the V-bit LDS map of csrc/ban_set.h and every register slot whose column is in the map is set to -inf,
+// where the plain form does that for the one UNK slot; ca.nbanned[row] = the map's pop-count.
+template <int NG, int NP = 0, bool VEC = true, bool HIST = false>      // float4 groups per thread: V <= NG * 1024
 __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, int nparts, long long part_stride, const float* bias, int beam,
-                                                          int V, int unk, float* cand_v, int* cand_i, float* lse_out) {
+                                                          int V, int unk, float* cand_v, int* cand_i, float* lse_out,
+                                                          typename cons_args<HIST>::type ca) {
     __shared__ float wm[4], ws[4];
+    [[maybe_unused]] __shared__ int wb[4];
     __shared__ float wv[4 * BEAM_MAX];
     __shared__ int wi[4 * BEAM_MAX];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -693,6 +700,8 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
             }
         } else v4[g] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     }
+    [[maybe_unused]] long long hv = 0;                       // HIST: this thread's step of the history, requested behind the row's loads
+    if constexpr (HIST) hv = load_hist_step(ca, row, tid);
     float m = -INFINITY;
 #pragma unroll
     for (int g = 0; g < NG; ++g) m = fmaxf(fmaxf(m, fmaxf(v4[g].x, v4[g].y)), fmaxf(v4[g].z, v4[g].w));
@@ -707,11 +716,27 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if (m == -INFINITY) s = 0.f;                                      // a wave that holds only padding (-inf - -inf = nan)
     if (lane == 0) { wm[wave] = m; ws[wave] = s; }
-    // the beam best of this wave (unk never selected)
+    // the beam best of this wave (unk never selected; HIST: no word of the row's ban set)
+    if constexpr (HIST) {
+        __shared__ uint32_t bits[WG];                       // V <= 32 * WG
+        __shared__ long long hist[CONS_T_MAX];
+        build_ban_map<WG>(ca, hv, V, unk, tid, bits, hist);     // (both barriers inside)
 #pragma unroll
-    for (int g = 0; g < NG; ++g)
+        for (int g = 0; g < NG; ++g) {
+            const int v0 = (tid + g * WG) * 4;                  // a group's four columns share one word of the map
+            const uint32_t w = v0 < V ? bits[v0 >> 5] >> (v0 & 31) : 0u;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v4[g][e] = ((tid + g * WG) * 4 + e == unk) ? -INFINITY : v4[g][e];
+            for (int e = 0; e < 4; ++e)
+                if (v0 + e < V && ((w >> e) & 1u)) v4[g][e] = -INFINITY;
+        }
+        const int nb = wave_sum_int(__popc(bits[tid]));
+        if (lane == 0) wb[wave] = nb;                       // read by thread 0 after the barrier below
+    } else {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v4[g][e] = ((tid + g * WG) * 4 + e == unk) ? -INFINITY : v4[g][e];
+    }
     for (int sel = 0; sel < beam; ++sel) {
         float bv = -INFINITY;
         int bi = 0x7fffffff;
@@ -746,6 +771,9 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
             for (int w = 0; w < 4; ++w)
                 if (wm[w] != -INFINITY) S += ws[w] * expf(wm[w] - M);
             lse_out[row] = M + logf(S);
+            if constexpr (HIST) {
+                if (ca.nbanned != nullptr) ca.nbanned[row] = (wb[0] + wb[1]) + (wb[2] + wb[3]);
+            }
         }
         const int cw = lane / BEAM_MAX, cs = lane % BEAM_MAX;      // lane -> (wave, rank) candidate
         float cv = -INFINITY;
@@ -768,11 +796,22 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
     }
 }
 
+// HIST: the hypotheses carry their histories (element (s, r) at hist[s * stride + r]).  After the selection every lane knows the
+// parent and the word of each selected slot (the butterfly leaves the winner in all lanes); lane s copies step s < t of the parent's
+// history for each of the `beam` selections -- all loads first, then the stores -- and lane 0 appends the word at step t.  The copy
+// gathers across the clip's rows: hist_in and hist_out are distinct buffers.
+struct NoHist {};
+struct HistArgs { const int64_t* in; int64_t* out; long long stride; int t; };
+template <bool HIST> struct hist_args { using type = NoHist; };
+template <> struct hist_args<true> { using type = HistArgs; };
+
+template <bool HIST = false>
 __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, const int* cand_i, const float* lse,
                                                         const float* score_in, const uint8_t* done_in, int beam, int V,
                                                         int first_step, int64_t* parent, int64_t* word, float* score_out,
-                                                        uint8_t* done_out) {
+                                                        uint8_t* done_out, typename hist_args<HIST>::type ha) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    [[maybe_unused]] __shared__ int sel_k[BEAM_MAX], sel_v[BEAM_MAX];      // HIST: parent and word of every selected slot
     // lane -> candidate (k = lane / beam, r = lane % beam), beam*beam <= 64
     const int k = lane / beam, r = lane - k * beam;
     float cv = -INFINITY;
@@ -810,7 +849,27 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             score_out[b * beam + sel] = bv;
             done_out[b * beam + sel] = (done_in[b * beam + kk] != 0 || vv == 0) ? 1 : 0;
         }
+        if constexpr (HIST) {
+            if (lane == 0) {
+                const bool none = bi == 0x7fffffff;
+                sel_k[sel] = none ? 0 : bi / V;
+                sel_v[sel] = none ? 0 : bi - (bi / V) * V;
+            }
+        }
         if (flat == bi) { cv = -INFINITY; flat = 0x7fffffff; }      // taken (flat indices are unique)
+    }
+    if constexpr (HIST) {
+        __syncthreads();
+        int64_t h[BEAM_MAX];
+        const bool mine = lane < ha.t;
+#pragma unroll
+        for (int sel = 0; sel < BEAM_MAX; ++sel)
+            if (sel < beam && mine) h[sel] = ha.in[(size_t)lane * ha.stride + b * beam + sel_k[sel]];
+#pragma unroll
+        for (int sel = 0; sel < BEAM_MAX; ++sel) {
+            if (sel < beam && mine) ha.out[(size_t)lane * ha.stride + b * beam + sel] = h[sel];
+            if (sel < beam && lane == 0) ha.out[(size_t)ha.t * ha.stride + b * beam + sel] = sel_v[sel];
+        }
     }
 }
 
@@ -1174,13 +1233,23 @@ extern "C" int cvc_beam_select(const float* logits, const float* score_in, const
                                  done_out, workspace, stream);
 }
 
-extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long part_stride, const float* bias,
-                                     const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx,
-                                     int first_step, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
-                                     float* workspace, cvc_stream_t stream) {
+// the argument checks of the beam selection blocks
+static int beam_select_check(const float* logits, int nparts, const float* score_in, const uint8_t* done_in, int B, int beam, int V,
+                             const int64_t* parent, const int64_t* word, const float* score_out, const uint8_t* done_out,
+                             const float* workspace) {
     if (nparts < 1) return CVC_E_BADARG;
     if (!logits || !score_in || !done_in || !parent || !word || !score_out || !done_out || !workspace) return CVC_E_BADARG;
     if (B < 1 || beam < 1 || beam > BEAM_MAX || V < beam + 1 || V > WG * ROW_CACHE) return CVC_E_BADARG;
+    return 0;
+}
+
+// behind both entry points, after the checks: the loader form of the row scan, then the merge.  HIST: the forms of both kernels that
+// know the hypotheses' histories (ra: the row scan's history and rules, ma: the merge's gather).
+template <bool HIST>
+static int beam_select_run(const float* logits, int nparts, long long part_stride, const float* bias, const float* score_in,
+                           const uint8_t* done_in, int B, int beam, int V, int unk_idx, int first_step, int64_t* parent, int64_t* word,
+                           float* score_out, uint8_t* done_out, float* workspace, cvc_stream_t stream,
+                           typename cons_args<HIST>::type ra, typename hist_args<HIST>::type ma) {
     // workspace: [rows*8] candidate values, [rows*8] candidate indices, [rows] lse   (rows = B*beam)
     const int rows = B * beam;
     float* cand_v = workspace;
@@ -1194,8 +1263,8 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
     // 6 slabs: 64 workgroups pulling 600 KB each ingest at ~20 GB/s per compute unit; 320 row workgroups spread the same bytes
     // over the chip)
     if ((aligned && nparts == 1 && bias == nullptr) || slabs) {
-#define CVC_RT4P(NG_, NP_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, NP_>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
-                                              nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse)
+#define CVC_RT4P(NG_, NP_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, NP_, true, HIST>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
+                                              nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse, ra)
 #define CVC_RT4(NG_) do { switch (slabs ? nparts : 0) { case 2: CVC_RT4P(NG_, 2); break; case 4: CVC_RT4P(NG_, 4); break; \
                                                          case 6: CVC_RT4P(NG_, 6); break; case 8: CVC_RT4P(NG_, 8); break; \
                                                          default: CVC_RT4P(NG_, 0); break; } } while (0)
@@ -1212,8 +1281,8 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
 #undef CVC_RT4
 #undef CVC_RT4P
     } else {
-#define CVC_RT4G(NG_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, 0, false>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
-                                         nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse)
+#define CVC_RT4G(NG_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, 0, false, HIST>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
+                                         nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse, ra)
         switch ((V + 4 * WG - 1) / (4 * WG)) {
             case 1: CVC_RT4G(1); break;
             case 2: CVC_RT4G(2); break;
@@ -1226,9 +1295,39 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
         }
 #undef CVC_RT4G
     }
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
-                       beam, V, first_step, parent, word, score_out, done_out);
+    hipLaunchKernelGGL(beam_merge_kernel<HIST>, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
+                       beam, V, first_step, parent, word, score_out, done_out, ma);
     return cvc_launch_status();
+}
+
+extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                     const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx,
+                                     int first_step, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
+                                     float* workspace, cvc_stream_t stream) {
+    const int rc = beam_select_check(logits, nparts, score_in, done_in, B, beam, V, parent, word, score_out, done_out, workspace);
+    if (rc != 0) return rc;
+    return beam_select_run<false>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, first_step, parent, word,
+                                  score_out, done_out, workspace, stream, NoCons{}, NoHist{});
+}
+
+// Constrained beam search: cvc_beam_select_parts for hypotheses that carry their own histories (contract: include/cvc_hip_blocks.h).
+// The HIST forms of the two kernels above; first_step is t == 0; c == NULL: no rule but UNK.
+extern "C" int cvc_beam_select_hist_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                          const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                          const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                          int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
+                                          float* workspace, cvc_stream_t stream) {
+    const int rc = beam_select_check(logits, nparts, score_in, done_in, B, beam, V, parent, word, score_out, done_out, workspace);
+    if (rc != 0) return rc;
+    if (t < 0 || t > CONS_T_MAX) return CVC_E_TOOBIG;
+    if (c != nullptr && cons_rules_check(c) != 0) return CVC_E_BADARG;
+    if (!hist_out || (t > 0 && !hist_in) || (const int64_t*)hist_out == hist_in || hist_stride < (long long)B * beam) return CVC_E_BADARG;
+    const cvc_constraint none = {0, 0, 0, 0, nullptr, nullptr, 0};
+    if (c == nullptr) c = &none;
+    const ConsArgs ra{hist_in, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
+                      c->bad_end, c->nbad, nbanned};
+    return beam_select_run<true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0, parent, word,
+                                 score_out, done_out, workspace, stream, ra, HistArgs{hist_in, hist_out, hist_stride, t});
 }
 
 namespace {

@@ -66,7 +66,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
-                 min_len: int = 0, ban_words=None, bad_endings=None):
+                 min_len: int = 0, ban_words=None, bad_endings=None, beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -113,8 +113,17 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         them on: the sampling paths' launch lists with that block as word_select, with or without a temperature (without: the
         arg-max over the allowed words), with sample_n and top_k / top_p; no C driver; capture() works (t and the rules are launch
         constants, the lists live in engine-owned device buffers).  The engine owns self.nbanned [T, rows] int32 (the size of the
-        ban set) and run() returns the sampling engine's tuple in both modes.  Refused: beam > 1, forced_n, gsk / gate_ksplit /
-        lang_ksx, the packed path without the embedding-gate schedule, T > 64, malformed values and ids outside [0, V)."""
+        ban set) and run() returns the sampling engine's tuple in both modes.  Refused: beam > 1 without beam_history, forced_n,
+        gsk / gate_ksplit / lang_ksx, the packed path without the embedding-gate schedule, T > 64, malformed values and ids outside
+        [0, V).
+        beam_history: beam search whose hypotheses carry their own histories on the device ("Constrained beam
+        search"; needs beam > 1, T <= 64, no gsk / gate_ksplit / lang_ksx).  The engine owns self.bhist [2, T, rows] int64 and its
+        word_select launch is cvc_beam_select_hist_parts with hist_in = bhist[t & 1] and hist_out = bhist[(t + 1) & 1], on the tile
+        path (fused slabs or finished logits) and on the ring path; the launch list is walked from Python or captured (no C
+        driver).  run() returns what a beam engine returns, with the plain beam engine's bits; hypotheses() returns all `beam`
+        hypotheses of every clip in rank order (n-best).  With it the five constraints run under beam search: the rule is applied
+        to every hypothesis' own history (a frozen hypothesis is left alone), scores stay sums of the model's log-probs, and
+        self.nbanned [T, rows] is filled."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -134,10 +143,20 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             gate_ksplit, lang_ksx = False, False
         self.cons = _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings)
         self.constrained = bool(self.cons[0] or self.cons[1] or self.cons[2] or self.cons[3] or self.cons[4])
+        if not isinstance(beam_history, (bool, np.bool_)):
+            raise RuntimeError(f"DecodeEngine: beam_history must be a bool, got {beam_history!r}")
+        self.beam_hist = bool(beam_history)
+        if self.beam_hist:
+            if self.beam == 1:
+                raise RuntimeError("DecodeEngine: beam_history keeps the histories of beam search: it needs beam > 1")
+            if self.T > CONSTRAINT_T_MAX:
+                raise RuntimeError(f"DecodeEngine: beam_history covers T <= {CONSTRAINT_T_MAX} steps, got T = {self.T}")
+            if gsk or gate_ksplit or lang_ksx:
+                raise RuntimeError("DecodeEngine: beam_history runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
         if self.constrained:
-            if self.beam != 1:
-                raise RuntimeError("DecodeEngine: constrained decoding and beam search (beam > 1) exclude each other (beam histories "
-                                   "follow their parents)")
+            if self.beam != 1 and not self.beam_hist:
+                raise RuntimeError("DecodeEngine: constrained decoding under beam search (beam > 1) needs beam_history=True (a "
+                                   "hypothesis' history follows its parents: it has to travel with it)")
             if self.forced:
                 raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no constraints")
             if gsk or gate_ksplit or lang_ksx:
@@ -168,7 +187,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             gsk, gate_ksplit, lang_ksx = False, False, False
         self.sampling = temperature is not None
         # the next step's word is read from words[t + 1] (sampled there by the selection block, or given): the sampling launch lists
-        self.given = self.sampling or self.forced or self.constrained
+        # (constrained beam search chooses in the beam block and reorders by parent like every beam engine)
+        self.given = self.sampling or self.forced or (self.constrained and self.beam == 1)
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
             raise RuntimeError(f"DecodeEngine: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
         if not (0.0 < float(top_p) <= 1.0):
@@ -266,6 +286,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.bt_att = z(self.B, self.T, N)
             self.gather_tmp = [z(rows, R) for _ in range(4)]
             self.beam_ws = z(17 * rows)
+            if self.beam_hist:               # the hypotheses' own histories, ping-pong: step t reads [t & 1], writes [(t + 1) & 1]
+                self.bhist = torch.zeros(2, self.T, rows, dtype=torch.int64, device=dev)
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
@@ -323,7 +345,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         elif self.tile:
             self._alloc_tile()
         self._launches = self._build_launches()
-        if driver and not self.given and not self.bf16w and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
+        if driver and not self.given and not self.bf16w and not self.beam_hist and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
 
     # ------------------------------------------------------------------ C-ABI decode driver (csrc/decode_driver.hip)
@@ -542,6 +564,29 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         return ("word_select", L.cvc_sample_select_trunc_parts, head + (self.top_k, self.top_p) + tail +
                 (self.cutoff[t].data_ptr(), self.kept[t].data_ptr()))
 
+    def _word_select_beam(self, t, parts, nparts, part_stride, bias):
+        """A beam path's word_select launch of step t over logits parts[0] + ... (+ bias): the plain block, or with beam_history
+        the block that carries the hypotheses' histories (and applies the constraints to them; t and the rules are launch
+        constants)."""
+        L, B, beam, V = hip.lib(), self.B, self.beam, self.W.V
+        srd, swr = t & 1, (t + 1) & 1
+        head = (parts, nparts, part_stride, bias, self.score[srd].data_ptr(), self.done[srd].data_ptr(), B, beam, V, self.unk)
+        tail = (self.parent[t].data_ptr(), self.words[t + 1].data_ptr(), self.score[swr].data_ptr(), self.done[swr].data_ptr())
+        ws = self.beam_ws.data_ptr()
+        if not self.beam_hist:
+            return ("word_select", L.cvc_beam_select_parts, head + (1 if t == 0 else 0,) + tail + (ws,))
+        cons = (self._cons_desc, self.nbanned[t].data_ptr()) if self.constrained else (None, None)
+        return ("word_select", L.cvc_beam_select_hist_parts, head + (t, self.bhist[srd].data_ptr(), self.bhist[swr].data_ptr(),
+                                                                     self.rows, cons[0]) + tail + (cons[1], ws))
+
+    def hypotheses(self):
+        """n-best: all `beam` hypotheses of every clip after run(), in rank order -- (seq [B, beam, T] int64, score [B, beam]),
+        views of engine-owned buffers (beam_history=True: the histories the selection block carried, no backtracking)."""
+        if not self.beam_hist:
+            raise RuntimeError("DecodeEngine.hypotheses needs beam_history=True")
+        B, beam, T = self.B, self.beam, self.T
+        return self.bhist[T & 1].view(T, B, beam).permute(1, 2, 0), self.score[T & 1].view(B, beam)
+
     def _python_launches(self):
         if self._launches is None:
             self._keep = []
@@ -578,7 +623,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained)
+        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
+               self.beam_hist)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
@@ -608,7 +654,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def run(self):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
         engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],
-        logprob [B*n, T]), row b * n + j = sample j of clip b; a constrained engine returns that tuple with or without a temperature.  Forced mode: (seq = the given words, att2_weights, logprob,
+        logprob [B*n, T]), row b * n + j = sample j of clip b; a constrained engine with beam = 1 returns that tuple with or without a
+        temperature (constrained beam search: what a beam engine returns, (seq, att2_weights, final beam scores [B, beam])).  Forced mode: (seq = the given words, att2_weights, logprob,
         rank [B*n, T] int32), row b * n + j = caption j of clip b."""
         if self.graph is not None:
             self.graph.replay()
@@ -618,7 +665,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()                           # the fallback's results
         if self.forced:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t(), self.rank.t()
-        if self.sampling or self.constrained:
+        if self.sampling or (self.constrained and self.beam == 1):
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t()
         if self.beam == 1:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2)

@@ -85,10 +85,13 @@ class RingPath:
             else:
                 out.append(("logits", L.cvc_linear_fwd, (seg_o, 1, ptr(W.b_o), None, rows, V, ptr(self.logits), V)))
                 srd, swr = t & 1, (t + 1) & 1
-                out.append(("word_select", L.cvc_beam_select, (ptr(self.logits), ptr(self.score[srd]), ptr(self.done[srd]), B,
-                                                               beam, V, self.unk, 1 if t == 0 else 0, ptr(self.parent[t]),
-                                                               ptr(self.words[t + 1]), ptr(self.score[swr]),
-                                                               ptr(self.done[swr]), ptr(self.beam_ws))))
+                if self.beam_hist:
+                    out.append(self._word_select_beam(t, ptr(self.logits), 1, 0, None))
+                else:
+                    out.append(("word_select", L.cvc_beam_select, (ptr(self.logits), ptr(self.score[srd]), ptr(self.done[srd]), B,
+                                                                   beam, V, self.unk, 1 if t == 0 else 0, ptr(self.parent[t]),
+                                                                   ptr(self.words[t + 1]), ptr(self.score[swr]),
+                                                                   ptr(self.done[swr]), ptr(self.beam_ws))))
                 # reorder the freshly written state rows by parent (gather into tmp, copy back)
                 for i, buf in enumerate((self.h_att[wr], self.c_att[wr], self.h_lang[wr], self.c_lang[wr])):
                     out.append(("beam_reorder", L.cvc_gather_rows, (ptr(buf), ptr(self.parent[t]), rows, beam, R,

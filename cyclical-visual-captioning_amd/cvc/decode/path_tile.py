@@ -131,12 +131,8 @@ class TilePath:
                                                             ptr(self.logprob[t]))))
                 parent = None
             else:
-                srd, swr = t & 1, (t + 1) & 1
                 src = (ptr(self.parts_o), self.ks_o, rows * V, ptr(W.b_o)) if fused_sel else (ptr(self.logits), 1, 0, None)
-                out.append(("word_select", L.cvc_beam_select_parts, src + (ptr(self.score[srd]), ptr(self.done[srd]), B,
-                                                                           beam, V, self.unk, 1 if t == 0 else 0, ptr(self.parent[t]),
-                                                                           ptr(self.words[t + 1]), ptr(self.score[swr]),
-                                                                           ptr(self.done[swr]), ptr(self.beam_ws))))
+                out.append(self._word_select_beam(t, *src))
                 parent = ptr(self.parent[t])
             if t + 1 < self.T:
                 out.append(("beam_reorder", L.cvc_tile_reorder_pack, (parent, ptr(self.words[t + 1]), nq, ptr(self.t_h_att),

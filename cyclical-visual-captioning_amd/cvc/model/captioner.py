@@ -482,7 +482,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         bf16 mode does not cover (beam search, sample_n > 1, more than 64 rows) raises, it never decodes in fp32 instead.
         no_repeat_ngram / no_immediate_repeat / min_len / ban_words / bad_endings (arguments, else the model's attributes, read from
         opts): DecodeEngine's constrained decoding.  With any of them on the third result is the log-prob [B*n, T] in the arg-max
-        mode too; what the constrained engine does not cover (beam search) raises."""
+        mode too.  With beam_size > 1 the engine is built with beam_history=True (constrained beam search: the rule applies to every
+        hypothesis' own history) and the result is a beam decode's (seq, att2_weights, None)."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
             segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
@@ -518,12 +519,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 engine.load_features(feats)
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
-                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p, **cons)
+                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
+                                  beam_history=beam > 1 and any(cons.values()), **cons)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)
         res = engine.run()
-        if sampling or engine.constrained:
+        if sampling or (engine.constrained and beam == 1):
             return res[0].clone(), res[1].clone(), res[2].clone()
         return res[0].clone(), res[1].clone(), None
 

@@ -192,6 +192,34 @@ int cvc_constrained_select_parts(const float* parts, int nparts, long long part_
                                  int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                  const int64_t* hist, long long hist_stride, const cvc_constraint* c, int32_t* nbanned,
                                  cvc_stream_t stream);
+/* Constrained beam search (csrc/vocab.hip: the HIST forms of the row scan and the merge of cvc_beam_select_parts; the ban set is
+ * the one definition of csrc/ban_set.h that cvc_constrained_select_parts uses): one beam-search step for hypotheses that carry
+ * their own histories, with the rules of constrained decoding applied per hypothesis.
+ *   Hypothesis row r = b * beam + k enters step t with history y_0 .. y_{t-1}, the words on its own path from the root: element
+ *   (s, r) at hist_in[s * hist_stride + r], s < t (BOS is not history).
+ *   Ban(t, r)   = the set of cvc_constrained_select_parts applied to that history: {unk_idx}, ban[], n-gram completion, the
+ *                 previous word, word 0 while t < min_len, word 0 after a word of bad_end[].  c == NULL: no rule but UNK.
+ *   candidates  = a live row's (k, v) at score_in[k] + z[k, v] - lse[k], the log-sum-exp over the FULL row, banned words included
+ *                 (scores stay sums of the model's log-probs); -inf for v in Ban(t, r).  A frozen row (done_in) offers (k, 0) at
+ *                 its carried score: the ban is not applied to it, it has already ended.  first_step is t == 0: only row 0 of a
+ *                 clip is live.
+ *   selection   = the `beam` best of a clip's candidates, ties -> lowest flat (k, v); fewer finite candidates than `beam`: fillers
+ *                 at -inf with parent and word in range -- parent, word, score_out, done_out as cvc_beam_select_parts writes them,
+ *                 and with nothing banned but UNK the bits of that block on the same inputs.
+ *   histories   = for every selected slot (b, sel) with parent kk and word vv:
+ *                 hist_out[s * hist_stride + b * beam + sel] = hist_in[s * hist_stride + b * beam + kk] for s < t,
+ *                 hist_out[t * hist_stride + b * beam + sel] = vv.  The copy gathers across a clip's rows: hist_in (t steps) and
+ *                 hist_out (t + 1 steps) are distinct buffers that ping-pong like score and done; hist_in may be NULL at t == 0.
+ *   nbanned[r]  = |Ban(t, r)|, distinct ids, UNK included, for every row, frozen or not (nullable).
+ * workspace: 17 * B * beam floats.  The checks of cvc_beam_select_parts; t < 0 or t > 64: CVC_E_TOOBIG; the cvc_constraint checks
+ * of cvc_constrained_select_parts (n outside [0, 64], min_len < 0, list counts outside [0, 256], a NULL list with a count), NULL
+ * hist_in with t > 0, NULL hist_out, hist_in == hist_out, hist_stride < B * beam: CVC_E_BADARG.  Nothing is launched on a refusal.
+ * Bitwise deterministic.  The C driver cvc_decode_beam has no history form: the engine walks or captures its launch list. */
+int cvc_beam_select_hist_parts(const float* parts, int nparts, long long part_stride, const float* bias,
+                               const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                               const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                               int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
+                               float* workspace, cvc_stream_t stream);
 /* Teacher-forced decoding (csrc/forced.hip; row loader, argument checks and dispatch of csrc/select_row.h): the log-prob and the
  * rank of a GIVEN word per row, one workgroup per row.
  *   z[r, :]    = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish -- the bits the other

@@ -1,0 +1,219 @@
+"""Constrained beam search without a GPU: the building block cvc_beam_select_hist_parts in the library's table and its host-side
+argument checks, the engine's refusals, and the fp64 reference (tests/beam_constrain_ref.py) on the CPU oracle's decodes: with no
+rule it is oracle.ref_cpu.beam_search, with a rule the ban does the deciding and the margins allow an exact GPU comparison."""
+import ctypes
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from cvc import synth
+from oracle import ref_cpu as O
+import beam_constrain_ref as BR
+import constrain_ref as CR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+UNK = synth.UNK_IDX
+NAME = "cvc_beam_select_hist_parts"
+BADARG, TOOBIG = -1, -2
+
+
+# ------------------------------------------------------------------ the block: table, binding, argument checks
+def test_block_is_in_the_table_and_bound_with_the_headers_argument_count():
+    import subprocess
+    import build_hip
+    from cvc import hip
+    so = build_hip.build(verbose=False)
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cvc_hip_blocks.h")).read(), flags=re.S)
+    m = re.search(r"\bint\s+" + NAME + r"\s*\((.*?)\)\s*;", src, flags=re.S)
+    assert m
+    nargs = len([a for a in m.group(1).split(",") if a.strip()])
+    assert NAME in hip.BLOCKS and len(hip.SIGNATURES[NAME]) == nargs
+    # cvc_beam_select_parts with t for first_step, + hist_in, hist_out, hist_stride, the descriptor, nbanned
+    assert nargs == len(hip.SIGNATURES["cvc_beam_select_parts"]) + 5
+    lib = ctypes.CDLL(so)
+    lib.cvc_block.restype = ctypes.c_void_p
+    lib.cvc_block.argtypes = [ctypes.c_char_p]
+    assert lib.cvc_block(NAME.encode())
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
+    assert not re.search(r"\b" + NAME + r"\b", exported)                               # the exported ABI does not grow
+    blocks_src = open(os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc", "blocks.hip")).read()
+    assert f"CVC_B({NAME})" in blocks_src
+    # one definition of the ban set: both kernels call the shared header's function
+    csrc = os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc")
+    for f in ("sample_select.h", "vocab.hip"):
+        text = open(os.path.join(csrc, f)).read()
+        assert '#include "ban_set.h"' in text and "build_ban_map<WG>(" in text and "atomicOr" not in text, f
+
+
+def test_host_argument_checks_return_their_codes_and_launch_nothing():
+    from cvc import hip
+    fn = getattr(hip.lib(), NAME)
+    fake, fake2 = ctypes.c_void_p(16), ctypes.c_void_p(4096)
+
+    def call(parts=fake, nparts=1, stride=0, score=fake, done=fake, B=3, beam=5, V=50, t=0, hin=fake, hout=fake2, hstride=15,
+             n=0, imm=0, min_len=0, nban=0, ban=None, nbad=0, bad=None, desc=True, parent=fake, word=fake, score_out=fake,
+             done_out=fake, ws=fake):
+        c = hip.Constraint(n, imm, min_len, nban, ban, bad, nbad) if desc else None
+        return fn(parts, nparts, stride, None, score, done, B, beam, V, 1, t, hin, hout, hstride, c, parent, word, score_out, done_out,
+                  None, ws, None)
+
+    # the checks of cvc_beam_select_parts
+    for kw in (dict(parts=None), dict(score=None), dict(done=None), dict(parent=None), dict(word=None), dict(score_out=None),
+               dict(done_out=None), dict(ws=None), dict(nparts=0), dict(B=0), dict(beam=0), dict(beam=9), dict(V=5), dict(V=8193)):
+        assert call(**kw) == BADARG, kw
+    # the history
+    assert call(t=-1) == TOOBIG and call(t=65) == TOOBIG
+    assert call(t=3, hin=None) == BADARG and call(hout=None) == BADARG and call(t=0, hin=None, hout=None) == BADARG
+    assert call(hin=fake, hout=fake) == BADARG and call(t=4, hin=fake2, hout=fake2) == BADARG          # they ping-pong
+    assert call(hstride=14) == BADARG and call(hstride=0) == BADARG
+    # the rules
+    assert call(n=-1) == BADARG and call(n=65) == BADARG and call(min_len=-1) == BADARG
+    assert call(nban=-1, ban=fake) == BADARG and call(nban=257, ban=fake) == BADARG
+    assert call(nbad=-1, bad=fake) == BADARG and call(nbad=257, bad=fake) == BADARG
+    assert call(nban=3, ban=None) == BADARG and call(nbad=1, bad=None) == BADARG
+    # (a NULL descriptor is allowed -- no rule but UNK -- and then the other checks still hold)
+    assert call(desc=False, parts=None) == BADARG and call(desc=False, t=65) == TOOBIG
+
+
+# ------------------------------------------------------------------ the engine's refusals
+def test_engine_refuses_before_anything_is_allocated():
+    from cvc.decode import DecodeEngine
+    import inspect
+    assert list(inspect.signature(DecodeEngine.__init__).parameters)[-1] == "beam_history"
+    assert inspect.signature(DecodeEngine.__init__).parameters["beam_history"].default is False
+    W = types.SimpleNamespace(V=50, R=32, A=32, E=32)
+    new = lambda T=4, W=W, **kw: DecodeEngine.__init__(object.__new__(DecodeEngine), W, {}, T, 1, **kw)
+    # constraints under beam search need the histories; the message names both
+    for kw in (dict(no_repeat_ngram=3), dict(min_len=2), dict(ban_words=[3]), dict(bad_endings=[4]), dict(no_immediate_repeat=True)):
+        with pytest.raises(RuntimeError, match=r"beam search.*beam_history"):
+            new(beam=3, **kw)
+    with pytest.raises(RuntimeError, match="beam > 1"):
+        new(beam_history=True)
+    with pytest.raises(RuntimeError, match="beam > 1"):
+        new(beam_history=True, no_repeat_ngram=2)
+    with pytest.raises(RuntimeError, match="T <= 64"):
+        new(T=65, beam=3, beam_history=True)
+    for kw in (dict(gsk=True), dict(gate_ksplit=True), dict(lang_ksx=True)):
+        with pytest.raises(RuntimeError, match="default schedules"):
+            new(beam=3, beam_history=True, **kw)
+    with pytest.raises(RuntimeError, match="bool"):
+        new(beam=3, beam_history="yes")
+    # sampling, the forced mode and bf16 weights stay exclusive with beam search, with or without the histories
+    for hist in (False, True):
+        with pytest.raises(RuntimeError, match="beam search"):
+            new(beam=3, beam_history=hist, temperature=0.7)
+        with pytest.raises(RuntimeError, match="beam search"):
+            new(beam=3, beam_history=hist, forced_n=1)
+        with pytest.raises(RuntimeError, match="beam search"):
+            new(beam=3, beam_history=hist, weights_dtype="bf16")
+    # malformed rules are still refused
+    with pytest.raises(RuntimeError, match="bad_endings"):
+        new(beam=3, beam_history=True, bad_endings=[50])
+
+
+def test_model_and_docs_know_constrained_beam_search():
+    import inspect
+    from cvc.model import captioner
+    from cvc.decode import DecodeEngine
+    assert re.search(r"beam_history=beam > 1 and", inspect.getsource(captioner))
+    assert "beam_history" in DecodeEngine.__init__.__doc__ and "hypotheses" in DecodeEngine.__init__.__doc__
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "### Constrained beam search" in design and "cvc_decode_beam" in design.split("### Constrained beam search")[1]
+
+
+# ------------------------------------------------------------------ the reference
+@pytest.mark.parametrize("name,seed,beam", [("tiny", 4321, 2), ("cfg1", 4321, 3), ("cfg1", 5, 5)])
+def test_with_no_rule_the_reference_is_the_oracles_beam_search(name, seed, beam):
+    d = synth.CONFIGS[name]
+    P, f = O.to_torch(synth.hot_path_state_dict(d, seed)), O.to_torch(synth.clip_features(d, seed))
+    with torch.no_grad():
+        r = BR.decode(P, f, d.T, UNK, beam)
+        seq, _, scores = O.beam_search(P, f, d.T, UNK, beam)
+    assert torch.equal(r["seq"][:, 0], seq) and not r["fired"].any()
+    np.testing.assert_allclose(r["score"].numpy(), scores.double().numpy(), rtol=0, atol=5e-5)      # fp32 sums of T log-probs
+    assert (r["nbanned"] == 1).all()
+    # the histories the reference carried are the parents walked back from every final rank
+    assert torch.equal(BR.backtrack_all(r["word"], r["parent"]), r["seq"])
+    # what the rules are for: every unconstrained hypothesis repeats a word and a bigram
+    for h in r["seq"].view(-1, d.T).tolist():
+        assert BR.repeats_ngram(h, 1) and BR.repeats_ngram(h, 2)
+
+
+# clips fired / fired steps / the issue's measured smallest margin, per case of BR.ENGINE_CASES
+EXPECT = [(3, None, 1.4e-3), (3, None, 1.4e-3), (3, None, 1.4e-3), (4, 15, 1.9e-3), (4, 21, 1.4e-3), (4, None, 5.9e-4), (4, 13, 2.6e-4)]
+
+
+@pytest.mark.parametrize("i", range(len(BR.ENGINE_CASES)))
+def test_the_ban_decides_and_the_margins_allow_an_exact_comparison(i):
+    name, seed, beam, rules = BR.ENGINE_CASES[i]
+    d, P, f, r = BR.shared_decode(i)
+    clips, steps, margin = EXPECT[i]
+    print(name, seed, beam, rules, "clips fired", int(r["fired"].any(1).sum()), "steps", int(r["fired"].sum()), "margin", r["margin"].min())
+    assert d.B == clips and r["fired"].any(1).all()
+    if steps is not None:
+        assert int(r["fired"].sum()) == steps
+    assert r["margin"].min() >= BR.MARGIN_MIN
+    assert abs(r["margin"].min() - margin) <= 0.05 * margin + 1e-5            # the figure of the issue's table, to its two digits
+    # properties: no finite hypothesis, cut at its first 0, repeats an n-gram; no UNK anywhere
+    n = rules["no_repeat_ngram"]
+    seq, score = r["seq"].view(-1, d.T).numpy(), r["score"].view(-1).numpy()
+    assert np.isfinite(score).any()
+    for h, s in zip(seq, score):
+        if np.isfinite(s):
+            assert not BR.repeats_ngram(BR.cut(h), n), h
+    assert not (seq == UNK).any()
+    assert (r["nbanned"] >= 1).all() and (r["nbanned"][0] == 1).all()
+    assert torch.equal(BR.backtrack_all(r["word"], r["parent"]), r["seq"])
+
+
+def test_banned_words_never_appear():
+    d = synth.CONFIGS["cfg1"]
+    P, f = O.to_torch(synth.hot_path_state_dict(d, 4321)), O.to_torch(synth.clip_features(d, 4321))
+    with torch.no_grad():
+        free = BR.decode(P, f, d.T, UNK, 3)
+        ban = sorted(set(free["seq"][:, :, 0].reshape(-1).tolist()) - {0})
+        assert ban
+        r = BR.decode(P, f, d.T, UNK, 3, ban_words=ban, no_repeat_ngram=2)
+    assert not np.isin(r["seq"].numpy(), ban + [UNK]).any()
+    assert r["fired"][:, 0].all() and (r["nbanned"][0] == 1 + len(ban)).all()
+
+
+def eager_eos(P, delta):
+    """the checkpoint with word 0's logit bias raised: a captioner that likes to stop (the synthetic ones never do) -- the
+    construction of tests/test_constrained_cpu.py, re-stated"""
+    P = dict(P)
+    P["logit.bias"] = P["logit.bias"].clone()
+    P["logit.bias"][0] += delta
+    return P
+
+
+@pytest.mark.parametrize("name,delta,L,beam", [("tiny", 0.2, 3, 2), ("cfg1", 0.8, 6, 3)])
+def test_min_len_and_bad_endings_on_an_eager_checkpoint(name, delta, L, beam):
+    d = synth.CONFIGS[name]
+    P, f = O.to_torch(synth.hot_path_state_dict(d, 4321)), O.to_torch(synth.clip_features(d, 4321))
+    P = eager_eos(P, delta)
+    with torch.no_grad():
+        free = BR.decode(P, f, d.T, UNK, beam)
+        fs = free["seq"]
+        # the rules have something to do: the free beam decode stops before L in every clip (its best hypothesis does)
+        assert all(len(BR.cut(h)) < L for h in fs[:, 0].tolist())
+        ends = [BR.cut(h) for h in fs.view(-1, d.T).tolist()]
+        bad = sorted({h[-1] for h in ends if h and len(h) < d.T})
+        assert bad
+        r = BR.decode(P, f, d.T, UNK, beam, min_len=L, bad_endings=bad)
+    assert r["fired"][:, :L].any(1).all()
+    seq, score = r["seq"].view(-1, d.T).tolist(), r["score"].view(-1).numpy()
+    assert np.isfinite(score).any()
+    for h, s in zip(seq, score):
+        if not np.isfinite(s):
+            continue
+        c = BR.cut(h)
+        assert len(c) >= L                                     # never stops before L
+        if len(c) < d.T:
+            assert c[-1] not in bad                            # ... nor right after a listed ending
+    # min_len bans word 0 on the live rows of the first L steps: UNK + word 0
+    assert (r["nbanned"][0] == 2).all()
