@@ -46,6 +46,9 @@ const Entry table[] = {
     CVC_B(cvc_forced_select_parts),
     CVC_B(cvc_constrained_select_parts),
     CVC_B(cvc_beam_select_hist_parts),
+    CVC_B(cvc_beam_select_groups_parts),
+    CVC_B(cvc_beam_rank),
+    CVC_B(cvc_beam_backtrack_from),
     CVC_B(cvc_tile_lstm_finish),
     CVC_B(cvc_tile_lstm_finish_embgate),
     CVC_B(cvc_tile_reorder_pack),

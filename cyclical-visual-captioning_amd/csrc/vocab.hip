@@ -805,21 +805,61 @@ struct HistArgs { const int64_t* in; int64_t* out; long long stride; int t; };
 template <bool HIST> struct hist_args { using type = NoHist; };
 template <> struct hist_args<true> { using type = HistArgs; };
 
-template <bool HIST = false>
+// GROUPS (cvc_beam_select_groups_parts, always with HIST): diverse beam search, beam = G * bd, slot k of a clip in group g = k / bd.
+// The rule, once (restated by include/cvc_hip_blocks.h and in fp64 by tests/beam_groups_ref.py):
+//   base      c(k, v) = score[k] + z[k, v] - lse[k], exactly the HIST form's candidate (full-row log-sum-exp, -inf in the row's ban
+//             set, a frozen row offers only (k, 0) at its carried score); step 0: only the first slot of each group (k % bd == 0) is
+//             live, the others are at -inf.
+//   penalty   groups are served in order g = 0 .. G-1 within the step; pen(v) = the number of slots selected at this step by groups
+//             < g whose parent row was live (not frozen) and whose word is v (Hamming diversity);
+//             aug(k, v) = c(k, v) - lambda * (float)pen(v) in fp32: one rounded multiply, then one rounded subtract (group_aug()
+//             below, compiled with contraction off: never an fma).  A frozen row's candidate is not penalised and its selection does
+//             not count toward pen, nor does a filler (a slot selected at -inf: it is no hypothesis and its word is arbitrary); -inf stays -inf.
+//   selection group g takes the bd best of its bd * V candidates by aug, ties -> lowest flat (k, v) with k the clip-wide slot; the
+//             j-th best goes to slot g * bd + j.  score_out is the UNAUGMENTED c; done_out, nbanned and the history gather as in
+//             the HIST form.  The parent of every selected slot lies in its own group; fewer finite candidates than bd: fillers at
+//             -inf with the parent in the group and the word in range; every candidate NaN: the group's first slot, word 0.
+// The row scan (stage 1) does not change: group g penalises at most g * bd <= beam - bd distinct words, and a penalty only lowers
+// a value, so at least bd of a row's unpenalised top-`beam` stay unpenalised; each of those is >= everything outside that set under
+// the same tie rule, hence the penalised top-bd of a row lies inside the `beam` candidates the row scan already writes.
+// Still one wave per clip, one candidate per lane: the G * bd selection rounds are the `beam` butterfly rounds, with the lanes of
+// the other groups offering nothing.  Lane 0 keeps (parent live and value finite ? word : -1) of every selected slot in LDS next to
+// sel_k / sel_v; at the start of a group each of its lanes counts the entries equal to its candidate's word.  The winner's own lane
+// (flat indices are unique) writes score_out from its unaugmented value.  No atomics, no scratch.
+// c - lambda * pen with the product rounded on its own.  hipcc's default for device code is -ffp-contract=fast and HIP's __fmul_rn /
+// __fsub_rn are plain operators that contract like any other (csrc/label_glue.hip), so contraction is switched off for this function;
+// the instructions carry no contract flag and stay a v_mul_f32 and a v_sub_f32 after inlining (checked in the disassembly).
+__device__ __forceinline__ float group_aug(float c, float lambda, int pen) {
+#pragma clang fp contract(off)
+    const float p = lambda * (float)pen;
+    return c - p;
+}
+
+struct NoGroups {};
+struct GroupArgs { int groups; float lambda; };
+template <bool GROUPS> struct group_args { using type = NoGroups; };
+template <> struct group_args<true> { using type = GroupArgs; };
+
+template <bool HIST = false, bool GROUPS = false>
 __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, const int* cand_i, const float* lse,
                                                         const float* score_in, const uint8_t* done_in, int beam, int V,
                                                         int first_step, int64_t* parent, int64_t* word, float* score_out,
-                                                        uint8_t* done_out, typename hist_args<HIST>::type ha) {
+                                                        uint8_t* done_out, typename hist_args<HIST>::type ha,
+                                                        typename group_args<GROUPS>::type ga) {
+    static_assert(HIST || !GROUPS, "the GROUPS form is a history form");
     const int b = blockIdx.x, lane = threadIdx.x;
     [[maybe_unused]] __shared__ int sel_k[BEAM_MAX], sel_v[BEAM_MAX];      // HIST: parent and word of every selected slot
+    [[maybe_unused]] __shared__ int sel_p[BEAM_MAX];                       // GROUPS: its word if the parent was live, else -1
     // lane -> candidate (k = lane / beam, r = lane % beam), beam*beam <= 64
     const int k = lane / beam, r = lane - k * beam;
     float cv = -INFINITY;
     int flat = 0x7fffffff;
+    [[maybe_unused]] int bd = beam, pw = -2;             // GROUPS: slots per group; this lane's word if it can be penalised
+    if constexpr (GROUPS) bd = beam / ga.groups;
     if (k < beam) {
         const int row = b * beam + k;
         float sc = score_in[row];
-        if (first_step && k > 0) sc = -INFINITY;
+        if (first_step && (GROUPS ? k % bd != 0 : k > 0)) sc = -INFINITY;
         if (done_in[row]) {
             // frozen hypothesis: candidates (k, 0) at the carried score, every other (k, v) at -inf; keep the
             // -inf fillers at distinct low flat indices so that tie-breaking matches a full scan
@@ -830,11 +870,26 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             const int vi = cand_i[row * BEAM_MAX + r];
             cv = (v == -INFINITY || sc == -INFINITY) ? -INFINITY : sc + (v - lse[row]);
             flat = vi == 0x7fffffff ? 0x7fffffff : k * V + vi;
+            if constexpr (GROUPS) pw = vi == 0x7fffffff ? -2 : vi;
         }
     }
+    [[maybe_unused]] float aug = -INFINITY;              // GROUPS: the candidate's augmented value while its group is served
+    [[maybe_unused]] int g0 = 0;                         // GROUPS: first slot of the group being served
     for (int sel = 0; sel < beam; ++sel) {
         float bv = cv;
         int bi = flat;
+        if constexpr (GROUPS) {
+            if (sel == g0 + bd) g0 = sel;
+            const bool mine = k >= g0 && k < g0 + bd;
+            if (sel == g0) {                             // a new group: the penalties of the words the groups before it took
+                __syncthreads();
+                int pen = 0;
+                for (int s = 0; s < g0; ++s) pen += sel_p[s] == pw ? 1 : 0;
+                aug = mine ? group_aug(cv, ga.lambda, pen) : -INFINITY;
+            }
+            bv = aug;
+            bi = mine ? flat : 0x7fffffff;
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o, 64);
@@ -843,16 +898,21 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
         }
         if (lane == 0) {
             int kk = bi / V, vv = bi - kk * V;
-            if (bi == 0x7fffffff) { kk = 0; vv = 0; }      // every candidate NaN: parent / word feed gathers, keep them in range
+            if (bi == 0x7fffffff) { kk = GROUPS ? g0 : 0; vv = 0; }      // every candidate NaN: parent / word feed gathers, keep them in range
             parent[b * beam + sel] = kk;
             word[b * beam + sel] = vv;
-            score_out[b * beam + sel] = bv;
-            done_out[b * beam + sel] = (done_in[b * beam + kk] != 0 || vv == 0) ? 1 : 0;
+            if (!GROUPS || bi == 0x7fffffff) score_out[b * beam + sel] = bv;
+            const bool frozen = done_in[b * beam + kk] != 0;
+            done_out[b * beam + sel] = (frozen || vv == 0) ? 1 : 0;
+            if constexpr (GROUPS) sel_p[sel] = (frozen || bi == 0x7fffffff || bv == -INFINITY) ? -1 : vv;
+        }
+        if constexpr (GROUPS) {
+            if (flat == bi && bi != 0x7fffffff) { score_out[b * beam + sel] = cv; aug = -INFINITY; }      // the winner's lane
         }
         if constexpr (HIST) {
             if (lane == 0) {
                 const bool none = bi == 0x7fffffff;
-                sel_k[sel] = none ? 0 : bi / V;
+                sel_k[sel] = none ? (GROUPS ? g0 : 0) : bi / V;
                 sel_v[sel] = none ? 0 : bi - (bi / V) * V;
             }
         }
@@ -1243,13 +1303,15 @@ static int beam_select_check(const float* logits, int nparts, const float* score
     return 0;
 }
 
-// behind both entry points, after the checks: the loader form of the row scan, then the merge.  HIST: the forms of both kernels that
-// know the hypotheses' histories (ra: the row scan's history and rules, ma: the merge's gather).
-template <bool HIST>
+// behind the entry points, after the checks: the loader form of the row scan, then the merge.  HIST: the forms of both kernels that
+// know the hypotheses' histories (ra: the row scan's history and rules, ma: the merge's gather).  GROUPS: the HIST row scan and the
+// merge that serves the groups in turn (ga: their number and the diversity strength).
+template <bool HIST, bool GROUPS = false>
 static int beam_select_run(const float* logits, int nparts, long long part_stride, const float* bias, const float* score_in,
                            const uint8_t* done_in, int B, int beam, int V, int unk_idx, int first_step, int64_t* parent, int64_t* word,
                            float* score_out, uint8_t* done_out, float* workspace, cvc_stream_t stream,
-                           typename cons_args<HIST>::type ra, typename hist_args<HIST>::type ma) {
+                           typename cons_args<HIST>::type ra, typename hist_args<HIST>::type ma,
+                           typename group_args<GROUPS>::type ga = {}) {
     // workspace: [rows*8] candidate values, [rows*8] candidate indices, [rows] lse   (rows = B*beam)
     const int rows = B * beam;
     float* cand_v = workspace;
@@ -1295,8 +1357,8 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
         }
 #undef CVC_RT4G
     }
-    hipLaunchKernelGGL(beam_merge_kernel<HIST>, dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
-                       beam, V, first_step, parent, word, score_out, done_out, ma);
+    hipLaunchKernelGGL((beam_merge_kernel<HIST, GROUPS>), dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
+                       beam, V, first_step, parent, word, score_out, done_out, ma, ga);
     return cvc_launch_status();
 }
 
@@ -1312,11 +1374,13 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
 
 // Constrained beam search: cvc_beam_select_parts for hypotheses that carry their own histories (contract: include/cvc_hip_blocks.h).
 // The HIST forms of the two kernels above; first_step is t == 0; c == NULL: no rule but UNK.
-extern "C" int cvc_beam_select_hist_parts(const float* logits, int nparts, long long part_stride, const float* bias,
-                                          const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
-                                          const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
-                                          int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
-                                          float* workspace, cvc_stream_t stream) {
+// groups == 0: the history block; groups >= 1 (cvc_beam_select_groups_parts): the GROUPS merge, groups == 1 included -- it is
+// the history block bit for bit (nothing is ever penalised) and the tests pin that on the form that serves the groups.
+static int beam_select_hist(const float* logits, int nparts, long long part_stride, const float* bias,
+                            const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                            const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                            int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
+                            float* workspace, cvc_stream_t stream, int groups, float lambda) {
     const int rc = beam_select_check(logits, nparts, score_in, done_in, B, beam, V, parent, word, score_out, done_out, workspace);
     if (rc != 0) return rc;
     if (t < 0 || t > CONS_T_MAX) return CVC_E_TOOBIG;
@@ -1326,19 +1390,51 @@ extern "C" int cvc_beam_select_hist_parts(const float* logits, int nparts, long 
     if (c == nullptr) c = &none;
     const ConsArgs ra{hist_in, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
                       c->bad_end, c->nbad, nbanned};
-    return beam_select_run<true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0, parent, word,
-                                 score_out, done_out, workspace, stream, ra, HistArgs{hist_in, hist_out, hist_stride, t});
+    const HistArgs ma{hist_in, hist_out, hist_stride, t};
+    if (groups == 0)
+        return beam_select_run<true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0, parent,
+                                     word, score_out, done_out, workspace, stream, ra, ma);
+    return beam_select_run<true, true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0, parent,
+                                       word, score_out, done_out, workspace, stream, ra, ma, GroupArgs{groups, lambda});
+}
+
+extern "C" int cvc_beam_select_hist_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                          const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                          const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                          int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
+                                          float* workspace, cvc_stream_t stream) {
+    return beam_select_hist(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t, hist_in, hist_out, hist_stride, c,
+                            parent, word, score_out, done_out, nbanned, workspace, stream, 0, 0.f);
+}
+
+// Diverse (group) beam search: cvc_beam_select_hist_parts with the clip's slots in `groups` groups served in turn and a Hamming
+// diversity penalty of strength lambda between them (the rule: the comment of beam_merge_kernel's GROUPS form; contract:
+// include/cvc_hip_blocks.h).
+extern "C" int cvc_beam_select_groups_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                            const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                            const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                            int groups, float lambda, int64_t* parent, int64_t* word, float* score_out,
+                                            uint8_t* done_out, int32_t* nbanned, float* workspace, cvc_stream_t stream) {
+    if (groups < 1 || (beam >= 1 && beam % groups != 0) || !(lambda >= 0.f) || isinf(lambda)) return CVC_E_BADARG;
+    return beam_select_hist(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t, hist_in, hist_out, hist_stride, c,
+                            parent, word, score_out, done_out, nbanned, workspace, stream, groups, lambda);
 }
 
 namespace {
 // rank-0 hypothesis of every clip: walk the parent pointers back from the last step (one thread), then copy the words and
 // the attention rows of the path (the attention of step t was computed for the PARENT row of the word chosen at step t)
+// (start: the slot to walk back from, clip b's at start[b * start_stride], clamped like a parent; NULL: slot 0)
 __global__ __launch_bounds__(256) void beam_backtrack_kernel(const int64_t* words, const int64_t* parent, const float* att, int beam,
-                                                            int T, int N, int rows, int64_t* seq, float* att_out) {
+                                                            int T, int N, int rows, int64_t* seq, float* att_out,
+                                                            const int64_t* start = nullptr, long long start_stride = 1) {
     __shared__ int path[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) {
         int k = 0;
+        if (start != nullptr) {
+            const long long s = start[(size_t)b * start_stride];
+            k = s < 0 ? 0 : (s >= beam ? beam - 1 : (int)s);
+        }
         for (int t = T - 1; t >= 0; --t) {
             const size_t at = (size_t)t * rows + (size_t)b * beam + k;
             seq[(size_t)b * T + t] = words[at];
@@ -1354,13 +1450,65 @@ __global__ __launch_bounds__(256) void beam_backtrack_kernel(const int64_t* word
         att_out[((size_t)b * T + t) * N + n] = att[((size_t)t * rows + (size_t)b * beam + path[t]) * N + n];
     }
 }
+
+// Final ranking of a clip's hypotheses, one wave per clip.  len(r) = position of the first 0 in r's history + 1, or T without one:
+// lane s holds step s of the row and the ballot of (word == 0) gives the position.  norm(r) = score(r) / len(r)^alpha in fp32
+// (alpha == 0: score(r) itself, no power is evaluated; -inf stays -inf).  Lane k then counts the slots that come before slot k --
+// larger norm, ties -> lowest slot, NaN last -- and writes order[b, that count] = k.
+__global__ __launch_bounds__(64) void beam_rank_kernel(const int64_t* hist, long long stride, const float* score, int beam, int T,
+                                                       float alpha, int64_t* order, float* norm, int32_t* len) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int mylen = T;
+    for (int k = 0; k < beam; ++k) {
+        const bool zero = lane < T && hist[(size_t)lane * stride + (size_t)b * beam + k] == 0;
+        const unsigned long long m = __ballot(zero);
+        const int l = m != 0ull ? __ffsll((long long)m) : T;
+        if (lane == k) mylen = l;
+    }
+    float nv = -INFINITY;
+    if (lane < beam) {
+        const float sc = score[b * beam + lane];
+        nv = alpha == 0.f ? sc : sc / powf((float)mylen, alpha);
+        norm[b * beam + lane] = nv;
+        len[b * beam + lane] = mylen;
+    }
+    const bool nan_me = nv != nv;
+    int before = 0;
+    for (int j = 0; j < beam; ++j) {
+        const float nj = __shfl(nv, j, 64);
+        const bool nan_j = nj != nj;
+        const bool first = nan_me ? (!nan_j || j < lane) : (!nan_j && (nj > nv || (nj == nv && j < lane)));
+        before += first ? 1 : 0;
+    }
+    if (lane < beam) order[b * beam + before] = lane;
+}
 }  // namespace
+
+extern "C" int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
+                             int64_t* order, float* norm, int32_t* len, cvc_stream_t stream) {
+    if (!hist || !score || !order || !norm || !len || B < 1 || beam < 1 || beam > BEAM_MAX || T < 1) return CVC_E_BADARG;
+    if (hist_stride < (long long)B * beam || !(alpha >= 0.f) || isinf(alpha)) return CVC_E_BADARG;
+    if (T > CONS_T_MAX) return CVC_E_TOOBIG;
+    hipLaunchKernelGGL(beam_rank_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, hist, hist_stride, score, beam, T, alpha, order, norm,
+                       len);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_beam_backtrack_from(const int64_t* words, const int64_t* parent, const float* att, int B, int beam, int T, int N,
+                                       const int64_t* start, long long start_stride, int64_t* seq, float* att_out,
+                                       cvc_stream_t stream) {
+    if (!words || !parent || !att || !start || !seq || !att_out || B < 1 || beam < 1 || T < 1 || T > 256 || N < 1) return CVC_E_BADARG;
+    if (start_stride < 1) return CVC_E_BADARG;
+    hipLaunchKernelGGL(beam_backtrack_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, words, parent, att, beam, T, N, B * beam,
+                       seq, att_out, start, start_stride);
+    return cvc_launch_status();
+}
 
 extern "C" int cvc_beam_backtrack(const int64_t* words, const int64_t* parent, const float* att, int B, int beam, int T, int N,
                                   int64_t* seq, float* att_out, cvc_stream_t stream) {
     if (!words || !parent || !att || !seq || !att_out || B < 1 || beam < 1 || T < 1 || T > 256 || N < 1) return CVC_E_BADARG;
     hipLaunchKernelGGL(beam_backtrack_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, words, parent, att, beam, T, N, B * beam,
-                       seq, att_out);
+                       seq, att_out, (const int64_t*)nullptr, 1ll);
     return cvc_launch_status();
 }
 

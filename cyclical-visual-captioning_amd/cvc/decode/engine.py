@@ -66,7 +66,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  driver: bool = True, gsk: Optional[bool] = None, embgate: Optional[bool] = None, lang_ksx: Optional[bool] = None,
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
-                 min_len: int = 0, ban_words=None, bad_endings=None, beam_history: bool = False):
+                 min_len: int = 0, ban_words=None, bad_endings=None, beam_groups: int = 1, diversity: float = 0.0,
+                 length_penalty: float = 0.0, beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -123,7 +124,19 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         driver).  run() returns what a beam engine returns, with the plain beam engine's bits; hypotheses() returns all `beam`
         hypotheses of every clip in rank order (n-best).  With it the five constraints run under beam search: the rule is applied
         to every hypothesis' own history (a frozen hypothesis is left alone), scores stay sums of the model's log-probs, and
-        self.nbanned [T, rows] is filled."""
+        self.nbanned [T, rows] is filled.
+        beam_groups, diversity, length_penalty: diverse (group) beam search and a length penalty on the final ranking (DESIGN
+        section 7, "Diverse beam search"; the rule is the comment of cvc_beam_select_groups_parts in include/cvc_hip_blocks.h).
+        beam_groups = G > 1 splits a clip's beam = G * bd slots into G groups that are served in turn within a step, later groups
+        paying diversity = lambda >= 0 per earlier live selection of the same word (Hamming diversity); the word_select launch is
+        cvc_beam_select_groups_parts on the tile path (fused slabs or finished logits) and on the ring path, G, lambda and t are
+        launch constants (capture() works), and it composes with the five constraints.  length_penalty = alpha > 0 ranks the final
+        hypotheses by norm = score / len^alpha, len = the words up to and including the first 0.  With either on, the decode ends
+        with cvc_beam_rank (self.order [B, beam] int64, self.norm, self.hyp_len) and cvc_beam_backtrack_from(order[:, 0]), both
+        inside a captured graph: run() returns the best hypothesis by norm, its attention rows and the final scores, and
+        hypotheses(ranked=True) returns (seq, score, norm, group) in that order.  Both need beam_history=True and beam > 1;
+        beam % beam_groups != 0, a negative diversity and diversity != 0 with one group are refused.  1 / 0.0 / 0.0 (the default):
+        nothing changes."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -153,6 +166,26 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 raise RuntimeError(f"DecodeEngine: beam_history covers T <= {CONSTRAINT_T_MAX} steps, got T = {self.T}")
             if gsk or gate_ksplit or lang_ksx:
                 raise RuntimeError("DecodeEngine: beam_history runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
+        if isinstance(beam_groups, bool) or not isinstance(beam_groups, (int, np.integer)) or beam_groups < 1:
+            raise RuntimeError(f"DecodeEngine: beam_groups must be an integer >= 1 (1 = off), got {beam_groups!r}")
+        if not (0.0 <= float(diversity) < float("inf")):
+            raise RuntimeError(f"DecodeEngine: diversity must be a finite number >= 0 (negative values are refused), got {diversity!r}")
+        if not (0.0 <= float(length_penalty) < float("inf")):
+            raise RuntimeError(f"DecodeEngine: length_penalty must be a finite number >= 0, got {length_penalty!r}")
+        self.groups, self.diversity, self.length_penalty = int(beam_groups), float(diversity), float(length_penalty)
+        self.grouped = self.groups > 1
+        self.ranked = self.grouped or self.length_penalty != 0.0          # the decode ends with cvc_beam_rank / cvc_beam_backtrack_from
+        if self.ranked:
+            what = "beam_groups > 1" if self.grouped else "length_penalty != 0"
+            if self.beam == 1:
+                raise RuntimeError(f"DecodeEngine: {what} is an option of beam search: it needs beam > 1")
+            if not self.beam_hist:
+                raise RuntimeError(f"DecodeEngine: {what} needs beam_history=True (the groups and the ranking read the hypotheses' "
+                                   "own histories)")
+            if self.beam % self.groups != 0:
+                raise RuntimeError(f"DecodeEngine: beam_groups = {self.groups} must divide beam = {self.beam}")
+        if self.diversity != 0.0 and not self.grouped:
+            raise RuntimeError("DecodeEngine: diversity acts between groups: it needs beam_groups > 1")
         if self.constrained:
             if self.beam != 1 and not self.beam_hist:
                 raise RuntimeError("DecodeEngine: constrained decoding under beam search (beam > 1) needs beam_history=True (a "
@@ -282,12 +315,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.score = z(2, rows)
             self.done = torch.zeros(2, rows, dtype=torch.uint8, device=dev)
             self.parent = torch.zeros(self.T, rows, dtype=torch.int64, device=dev)
-            self.bt_seq = torch.zeros(self.B, self.T, dtype=torch.int64, device=dev)      # rank-0 hypothesis (cvc_beam_backtrack)
+            self.bt_seq = torch.zeros(self.B, self.T, dtype=torch.int64, device=dev)      # the returned hypothesis (cvc_beam_backtrack: rank 0; ranked engines: the best by norm)
             self.bt_att = z(self.B, self.T, N)
             self.gather_tmp = [z(rows, R) for _ in range(4)]
             self.beam_ws = z(17 * rows)
             if self.beam_hist:               # the hypotheses' own histories, ping-pong: step t reads [t & 1], writes [(t + 1) & 1]
                 self.bhist = torch.zeros(2, self.T, rows, dtype=torch.int64, device=dev)
+            if self.ranked:                  # the final ranking (cvc_beam_rank): slots by norm, norm, len
+                self.order = torch.zeros(self.B, self.beam, dtype=torch.int64, device=dev)
+                self.norm = z(self.B, self.beam)
+                self.hyp_len = torch.zeros(self.B, self.beam, dtype=torch.int32, device=dev)
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
@@ -576,16 +613,27 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if not self.beam_hist:
             return ("word_select", L.cvc_beam_select_parts, head + (1 if t == 0 else 0,) + tail + (ws,))
         cons = (self._cons_desc, self.nbanned[t].data_ptr()) if self.constrained else (None, None)
-        return ("word_select", L.cvc_beam_select_hist_parts, head + (t, self.bhist[srd].data_ptr(), self.bhist[swr].data_ptr(),
-                                                                     self.rows, cons[0]) + tail + (cons[1], ws))
+        hist = (t, self.bhist[srd].data_ptr(), self.bhist[swr].data_ptr(), self.rows, cons[0])
+        if self.grouped:
+            return ("word_select", L.cvc_beam_select_groups_parts, head + hist + (self.groups, self.diversity) + tail + (cons[1], ws))
+        return ("word_select", L.cvc_beam_select_hist_parts, head + hist + tail + (cons[1], ws))
 
-    def hypotheses(self):
-        """n-best: all `beam` hypotheses of every clip after run(), in rank order -- (seq [B, beam, T] int64, score [B, beam]),
-        views of engine-owned buffers (beam_history=True: the histories the selection block carried, no backtracking)."""
+    def hypotheses(self, ranked: bool = False):
+        """n-best: all `beam` hypotheses of every clip after run(), in slot order (one group: rank order by score) -- (seq
+        [B, beam, T] int64, score [B, beam]), views of engine-owned buffers (beam_history=True: the histories the selection block
+        carried, no backtracking).  ranked=True (beam_groups > 1 or a length_penalty): (seq, score, norm, group [B, beam] int64) in
+        the order of cvc_beam_rank -- norm descending, ties to the lowest slot -- as new tensors."""
         if not self.beam_hist:
             raise RuntimeError("DecodeEngine.hypotheses needs beam_history=True")
         B, beam, T = self.B, self.beam, self.T
-        return self.bhist[T & 1].view(T, B, beam).permute(1, 2, 0), self.score[T & 1].view(B, beam)
+        seq, score = self.bhist[T & 1].view(T, B, beam).permute(1, 2, 0), self.score[T & 1].view(B, beam)
+        if not ranked:
+            return seq, score
+        if not self.ranked:
+            raise RuntimeError("DecodeEngine.hypotheses(ranked=True) needs beam_groups > 1 or a length_penalty")
+        o = self.order
+        return (seq.gather(1, o.unsqueeze(2).expand(B, beam, T)), score.gather(1, o), self.norm.gather(1, o),
+                o // (beam // self.groups))
 
     def _python_launches(self):
         if self._launches is None:
@@ -609,7 +657,15 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         else:
             self._reset()
             self._run_launches()
-        if self.beam > 1:                                  # rank-0 hypothesis: one launch (was ~60 indexing launches per decode)
+        if self.beam > 1 and self.ranked:                  # the final ranking, then the best hypothesis by norm: two launches
+            L, T = hip.lib(), self.T
+            hip._check(L.cvc_beam_rank(self.bhist[T & 1].data_ptr(), self.rows, self.score[T & 1].data_ptr(), self.B, self.beam, T,
+                                       self.length_penalty, self.order.data_ptr(), self.norm.data_ptr(), self.hyp_len.data_ptr(),
+                                       hip._stream()), "cvc_beam_rank")
+            hip._check(L.cvc_beam_backtrack_from(self.words[1:].data_ptr(), self.parent.data_ptr(), self.att_steps.data_ptr(), self.B,
+                                                 self.beam, T, self.N, self.order.data_ptr(), self.beam, self.bt_seq.data_ptr(),
+                                                 self.bt_att.data_ptr(), hip._stream()), "cvc_beam_backtrack_from")
+        elif self.beam > 1:                                # rank-0 hypothesis: one launch (was ~60 indexing launches per decode)
             hip._check(hip.lib().cvc_beam_backtrack(self.words[1:].data_ptr(), self.parent.data_ptr(), self.att_steps.data_ptr(),
                                                     self.B, self.beam, self.T, self.N, self.bt_seq.data_ptr(),
                                                     self.bt_att.data_ptr(), hip._stream()), "cvc_beam_backtrack")
@@ -624,7 +680,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
         key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist)
+               self.beam_hist, self.grouped, self.ranked)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
@@ -655,7 +711,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
         engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],
         logprob [B*n, T]), row b * n + j = sample j of clip b; a constrained engine with beam = 1 returns that tuple with or without a
-        temperature (constrained beam search: what a beam engine returns, (seq, att2_weights, final beam scores [B, beam])).  Forced mode: (seq = the given words, att2_weights, logprob,
+        temperature (constrained beam search: what a beam engine returns, (seq, att2_weights, final beam scores [B, beam])).  A beam
+        engine's seq is the rank-0 hypothesis; with beam_groups > 1 or a length_penalty it is the best hypothesis by norm = score /
+        len^alpha (self.order[:, 0]), with its attention rows, and the scores stay in slot order.  Forced mode: (seq = the given words, att2_weights, logprob,
         rank [B*n, T] int32), row b * n + j = caption j of clip b."""
         if self.graph is not None:
             self.graph.replay()
@@ -672,7 +730,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         return self._backtrack()
 
     def _backtrack(self):
-        """Rank-0 hypothesis of every clip (cvc_beam_backtrack, enqueued with the decode) and the final beam scores."""
+        """The returned hypothesis of every clip and the final beam scores [B, beam] in slot order: rank 0 (cvc_beam_backtrack), or on
+        an engine with beam_groups > 1 or a length_penalty the best hypothesis by norm (cvc_beam_rank, then cvc_beam_backtrack_from
+        order[:, 0]); enqueued with the decode."""
         return self.bt_seq, self.bt_att, self.score[self.T & 1].view(self.B, self.beam)
 
     def _backtrack_host(self):

@@ -47,6 +47,11 @@ def main(argv=None, sample=None, score=None):
     parser.add_argument("--min_caption_len", type=int, default=0, help="no end of sentence before this many words; 0 = off")
     parser.add_argument("--ban_words", type=str, default="", help="comma-separated words (or word ids) that are never chosen")
     parser.add_argument("--bad_endings", type=str, default="", help="comma-separated words (or word ids) a caption may not end on")
+    # diverse (group) beam search and the length penalty of the final ranking (DecodeEngine beam_groups / diversity / length_penalty)
+    parser.add_argument("--group_size", type=int, default=1, help="groups of diverse beam search (divides --beam_size); 1 = off")
+    parser.add_argument("--diversity_lambda", type=float, default=0.0, help="Hamming diversity penalty between the groups; 0 = off")
+    parser.add_argument("--length_penalty", type=float, default=0.0,
+                        help="rank the final hypotheses by score / length^alpha; 0 = by score")
     parser.add_argument("--no_cfg", action="store_true", help="skip the YAML overlay (pure CLI)")
     parser.add_argument("--synthetic_raw", action="store_true",
                         help="feed raw frame / region features through the once-per-clip encoder (model/backbone.py) "
@@ -101,6 +106,8 @@ def main(argv=None, sample=None, score=None):
 
     if opt.no_repeat_ngram < 0 or opt.min_caption_len < 0:
         raise SystemExit("--no_repeat_ngram and --min_caption_len must be >= 0")
+    if opt.group_size < 1 or opt.diversity_lambda < 0 or opt.length_penalty < 0:
+        raise SystemExit("--group_size must be >= 1, --diversity_lambda and --length_penalty >= 0")
     opt.ban_word_ids = word_ids(opt.ban_words, opt.wtoi, "--ban_words")
     opt.bad_ending_ids = word_ids(opt.bad_endings, opt.wtoi, "--bad_endings")
     model = build_model(opt, device)

@@ -106,6 +106,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.min_caption_len = int(getattr(opts, "min_caption_len", 0))
         self.ban_words = tuple(getattr(opts, "ban_word_ids", None) or ())
         self.bad_endings = tuple(getattr(opts, "bad_ending_ids", None) or ())
+        # diverse (group) beam search and the final ranking's length penalty (DecodeEngine beam_groups / diversity / length_penalty)
+        self.beam_groups = int(getattr(opts, "group_size", 1))
+        self.diversity_lambda = float(getattr(opts, "diversity_lambda", 0.0))
+        self.length_penalty = float(getattr(opts, "length_penalty", 0.0))
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
         self.decode_weights_dtype = getattr(opts, "decode_weights", "fp32")
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
@@ -470,7 +474,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 pnt_mask, beam_size: Optional[int] = None, sample_max: Optional[int] = None, temperature: Optional[float] = None,
                 sample_n: Optional[int] = None, seed: Optional[int] = None, decode_weights: Optional[str] = None,
                 top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
-                no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None):
+                no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
+                beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -483,7 +488,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         no_repeat_ngram / no_immediate_repeat / min_len / ban_words / bad_endings (arguments, else the model's attributes, read from
         opts): DecodeEngine's constrained decoding.  With any of them on the third result is the log-prob [B*n, T] in the arg-max
         mode too.  With beam_size > 1 the engine is built with beam_history=True (constrained beam search: the rule applies to every
-        hypothesis' own history) and the result is a beam decode's (seq, att2_weights, None)."""
+        hypothesis' own history) and the result is a beam decode's (seq, att2_weights, None).
+        beam_groups / diversity_lambda / length_penalty (arguments, else the model's attributes, read from opts.group_size /
+        diversity_lambda / length_penalty): DecodeEngine's diverse beam search and length-normalised final ranking; with
+        beam_size > 1 and any of them on the engine is built with beam_history=True and seq is the best hypothesis by norm (all of
+        them: engine.hypotheses(ranked=True)).  With beam_size == 1 the engine refuses them."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
             segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
@@ -502,11 +511,14 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                     min_len=self.min_caption_len if min_len is None else min_len,
                     ban_words=tuple(self.ban_words if ban_words is None else ban_words),
                     bad_endings=tuple(self.bad_endings if bad_endings is None else bad_endings))
+        groups = self.beam_groups if beam_groups is None else int(beam_groups)
+        lam = self.diversity_lambda if diversity_lambda is None else float(diversity_lambda)
+        alpha = self.length_penalty if length_penalty is None else float(length_penalty)
         weights = self.decode_weights()
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, tuple(cons.values()))
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, tuple(cons.values()), groups, lam, alpha)
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -520,7 +532,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
                                   sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
-                                  beam_history=beam > 1 and any(cons.values()), **cons)
+                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0),
+                                  beam_groups=groups, diversity=lam, length_penalty=alpha, **cons)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)

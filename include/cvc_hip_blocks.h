@@ -220,6 +220,45 @@ int cvc_beam_select_hist_parts(const float* parts, int nparts, long long part_st
                                const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
                                int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
                                float* workspace, cvc_stream_t stream);
+/* Diverse (group) beam search (Vijayakumar et al. 2016; csrc/vocab.hip: the GROUPS form of the merge of cvc_beam_select_hist_parts,
+ * the row scan is that block's): cvc_beam_select_hist_parts with the clip's `beam` = groups * bd slots in `groups` groups that are
+ * served in turn within the step, later groups penalised for the words earlier ones took.  Slot k belongs to group g = k / bd.
+ *   base        c(k, v) = the candidate of cvc_beam_select_hist_parts: score_in[k] + z[k, v] - lse[k], the log-sum-exp over the full
+ *               row, -inf for v in Ban(t, r), a frozen row offers only (k, 0) at its carried score.  t == 0: only the first slot of
+ *               each group (k % bd == 0) is live, the others are at -inf.
+ *   penalty     for group g, pen(v) = the number of slots selected at this step by groups < g whose parent row was live (not frozen)
+ *               and whose word is v (Hamming diversity); aug(k, v) = c(k, v) - lambda * (float)pen(v) in fp32, one rounded
+ *               multiply followed by one rounded subtract (no fma).  A frozen row's candidate is not penalised and its selection
+ *               does not count toward pen, nor does a filler (a slot selected at -inf: its word is left open below, so it cannot
+ *               be part of the rule); -inf stays -inf.
+ *   selection   group g takes the bd best of its bd * V candidates by aug, ties -> lowest flat (k, v) with k the clip-wide slot;
+ *               the j-th best goes to slot g * bd + j.  The parent of every selected slot lies in its own group.  Fewer finite
+ *               candidates than bd: fillers at -inf with the parent in the group and the word in range; every candidate NaN: the
+ *               group's first slot and word 0.
+ *   outputs     score_out = the UNAUGMENTED c (scores stay sums of the model's log-probs); parent, word, done_out, the histories
+ *               and nbanned as cvc_beam_select_hist_parts writes them.
+ * groups == 1 is cvc_beam_select_hist_parts bit for bit in every output (lambda then has nothing to act on).  The checks of
+ * cvc_beam_select_hist_parts with their codes; groups < 1, beam % groups != 0, lambda negative or not finite: CVC_E_BADARG.  Nothing
+ * is launched on a refusal.  Bitwise deterministic; workspace: 17 * B * beam floats. */
+int cvc_beam_select_groups_parts(const float* parts, int nparts, long long part_stride, const float* bias,
+                                 const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                 const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                 int groups, float lambda, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
+                                 int32_t* nbanned, float* workspace, cvc_stream_t stream);
+/* Final ranking of the hypotheses a history block carried (one launch per decode).  Row r = b * beam + k, its history element (s, r)
+ * at hist[s * hist_stride + r], s < T.
+ *   len[r]      = position of the first 0 in r's history + 1, or T if there is none.
+ *   norm[r]     = score[r] / len[r]^alpha in fp32; alpha == 0: score[r] itself (no power is evaluated).  -inf stays -inf.
+ *   order[b, :] = the clip's slots by norm descending, ties -> lowest slot, NaN last.
+ * B < 1, beam outside [1, 8], T < 1, hist_stride < B * beam, alpha negative or not finite, a NULL pointer: CVC_E_BADARG; T > 64:
+ * CVC_E_TOOBIG. */
+int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
+                  int64_t* order, float* norm, int32_t* len, cvc_stream_t stream);
+/* cvc_beam_backtrack (include/cvc_hip.h) from slot start[b * start_stride] of clip b instead of slot 0 (the same kernel; the slot
+ * is clamped to [0, beam) like a parent; start_stride = beam reads column 0 of cvc_beam_rank's order in place).  start == 0
+ * everywhere: the bits of cvc_beam_backtrack.  Its checks; NULL start, start_stride < 1: CVC_E_BADARG. */
+int cvc_beam_backtrack_from(const int64_t* words, const int64_t* parent, const float* att, int B, int beam, int T, int N,
+                            const int64_t* start, long long start_stride, int64_t* seq, float* att_out, cvc_stream_t stream);
 /* Teacher-forced decoding (csrc/forced.hip; row loader, argument checks and dispatch of csrc/select_row.h): the log-prob and the
  * rank of a GIVEN word per row, one workgroup per row.
  *   z[r, :]    = parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias), the order of cvc_tile_linear_finish -- the bits the other
