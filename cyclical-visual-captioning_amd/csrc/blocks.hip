@@ -48,6 +48,8 @@ const Entry table[] = {
     CVC_B(cvc_beam_select_hist_parts),
     CVC_B(cvc_beam_select_groups_parts),
     CVC_B(cvc_beam_rank),
+    CVC_B(cvc_beam_select_force_parts),
+    CVC_B(cvc_beam_rank_force),
     CVC_B(cvc_beam_backtrack_from),
     CVC_B(cvc_tile_lstm_finish),
     CVC_B(cvc_tile_lstm_finish_embgate),

@@ -9,6 +9,7 @@
 #include "dropout_rng.h"
 #include "ban_set.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -662,10 +663,35 @@ constexpr int ROW_CACHE = 32;        // values per thread kept in registers: V <
 // decoding.  After the row's loads are issued and its (max, sum) share is taken -- the log-sum-exp runs over the full row -- the
 // row's ban set is built as the V-bit LDS map of csrc/ban_set.h and every register slot whose column is in the map is set to -inf,
 // where the plain form does that for the one UNK slot; ca.nbanned[row] = the map's pop-count.
-template <int NG, int NP = 0, bool VEC = true, bool HIST = false>      // float4 groups per thread: V <= NG * 1024
+// FORCE (cvc_beam_select_force_parts, always with HIST; the rule: the comment of beam_merge_kernel's BANKS form): a row may advance
+// to the next bank by any of its clip's unmet forced words, and its sorted top-`beam` need not hold them.  After the ban map is
+// applied and before the selection rounds overwrite taken values, the thread whose register slot holds column w_j writes that
+// value -- raw, post-ban, the bits cand_v would carry -- to ca.fws[4 * row + j] for every active entry j of the clip (-inf for an
+// unused entry), and thread 0 writes the word ca.fws[4 * row + 3]: bits 0-2 the row's met mask (the history is already in LDS),
+// bits 8-10 the clip's active entries; ca.nmet[row] = the met mask's pop-count.  Nothing else in the scan changes: cand_v, cand_i,
+// lse and nbanned are the HIST form's bit for bit.
+struct ForceArgs : ConsArgs { const int32_t* force; int nforce; float* fws; int32_t* nmet; };
+template <bool HIST, bool FORCE> struct scan_args { using type = typename cons_args<HIST>::type; };
+template <> struct scan_args<true, true> { using type = ForceArgs; };
+
+// Forced words of a clip, f[0 .. C): bit j is set iff entry j is active -- 0 < f[j] < V, f[j] != unk and no earlier entry of the
+// clip holds the same word.  The one definition the row scan, the merge and the final ranking share.
+__device__ __forceinline__ int force_active(const int32_t* f, int C, int V, int unk) {
+    int m = 0;
+    for (int j = 0; j < C; ++j) {
+        const int w = f[j];
+        bool ok = w > 0 && w < V && w != unk;
+        for (int i = 0; i < j; ++i) ok = ok && f[i] != w;
+        m |= ok ? 1 << j : 0;
+    }
+    return m;
+}
+
+template <int NG, int NP = 0, bool VEC = true, bool HIST = false, bool FORCE = false>      // float4 groups per thread: V <= NG * 1024
 __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, int nparts, long long part_stride, const float* bias, int beam,
                                                           int V, int unk, float* cand_v, int* cand_i, float* lse_out,
-                                                          typename cons_args<HIST>::type ca) {
+                                                          typename scan_args<HIST, FORCE>::type ca) {
+    static_assert(HIST || !FORCE, "the FORCE form is a history form");
     __shared__ float wm[4], ws[4];
     [[maybe_unused]] __shared__ int wb[4];
     __shared__ float wv[4 * BEAM_MAX];
@@ -731,6 +757,34 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
         }
         const int nb = wave_sum_int(__popc(bits[tid]));
         if (lane == 0) wb[wave] = nb;                       // read by thread 0 after the barrier below
+        if constexpr (FORCE) {
+            const int32_t* f = ca.force + (size_t)(row / beam) * ca.nforce;
+            const int act = force_active(f, ca.nforce, V, unk);
+            int met = 0;
+            for (int j = 0; j < ca.nforce; ++j) {
+                if (!((act >> j) & 1)) {
+                    if (tid == 0) ca.fws[(size_t)row * 4 + j] = -INFINITY;
+                    continue;
+                }
+                const int w = f[j];                         // 0 < w < V: one register slot of one thread holds it
+                float fv = -INFINITY;
+                bool own = false;
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const bool hit = (tid + g * WG) * 4 + e == w;
+                        own = own | hit;
+                        fv = hit ? v4[g][e] : fv;
+                    }
+                if (own) ca.fws[(size_t)row * 4 + j] = fv;
+                if (wave == 0) met |= __ballot(lane < ca.t && hist[lane] == (long long)w) != 0ull ? 1 << j : 0;
+            }
+            if (tid == 0) {
+                reinterpret_cast<int*>(ca.fws)[(size_t)row * 4 + 3] = (act << 8) | met;
+                if (ca.nmet != nullptr) ca.nmet[row] = __popc(met);
+            }
+        }
     } else {
 #pragma unroll
         for (int g = 0; g < NG; ++g)
@@ -837,40 +891,96 @@ __device__ __forceinline__ float group_aug(float c, float lambda, int pen) {
 
 struct NoGroups {};
 struct GroupArgs { int groups; float lambda; };
-template <bool GROUPS> struct group_args { using type = NoGroups; };
-template <> struct group_args<true> { using type = GroupArgs; };
 
-template <bool HIST = false, bool GROUPS = false>
+// BANKS (cvc_beam_select_force_parts, always with HIST, never with GROUPS): lexically constrained beam search (Anderson et al. 2017;
+// the bank formulation of Post & Vilar 2018).  The rule, once (restated by include/cvc_hip_blocks.h and in fp64 by tests/force_ref.py):
+//   forced    force[b * C + j], j < C = nforce in {1, 2, 3}, int32.  Entry j of clip b is ACTIVE iff 0 < w < V, w != unk and no
+//             entry j' < j of the clip holds the same w (force_active()); anything else is unused.
+//   banks     beam = (C + 1) * bd; slots [j * bd, (j + 1) * bd) of a clip are bank j.  For row r = (b, k) entering step t with history
+//             y_0 .. y_{t-1}: met(r) = the active entries of clip b whose word occurs in the history, n(r) = |met(r)|.  Routing uses
+//             n(r) from the history, never the slot.
+//   base      c(k, v) = score[k] + z[k, v] - lse[k], exactly the HIST form's candidate (full-row log-sum-exp, -inf in the row's ban
+//             set -- a forced word in it is -inf for this step like any banned word -- and a frozen row offers only (k, 0) at its
+//             carried score); step 0: only slot 0 of a clip is live.
+//   target    the bank of (k, v) is n(r) + 1 if r is live and v is an active forced word of the clip that is not in met(r), else n(r).
+//   selection bank j takes the bd best candidates whose target is j over ALL rows of the clip, ties -> lowest flat (k, v) with k the
+//             clip-wide slot; the i-th best goes to slot j * bd + i.  Fewer than bd finite candidates: the rest of the bank are
+//             fillers -- score_out = -inf, parent in [0, beam), word in [0, V), done_out / the history gather / the append as for
+//             any slot; what a filler holds besides its -inf score is not part of the rule.  A row at -inf offers only -inf.
+//   outputs   score_out = c (scores stay sums of the model's log-probs); parent, word, done_out, the histories and nbanned as in the
+//             HIST form.  No implicit end-of-sentence rule: a hypothesis may end in any bank.
+//   invariant every slot with a finite score in bank j has exactly j active forced words in its history.
+// Why the row scan's sorted top-`beam` is still enough: a live row has at most C unmet forced words, so the bd best candidates that
+// STAY in the row's bank lie among the first bd + C entries of the list the row scan already writes (bd + C <= beam); the candidates
+// that ADVANCE are at most C per row, the row's values at its unmet forced words, which the top list need not hold -- the FORCE form
+// of the row scan reports them.  Per clip the merge sees at most beam * (bd + 2 C) candidates: 64 at beam 8, C = 3, fewer for every
+// other allowed (beam, C).  Still one wave per clip and one candidate per lane: lane -> (k = lane / (bd + 2 C), r = lane % (bd + 2 C)),
+// r < bd + C the r-th list entry, the others the advance lane of entry r - (bd + C).  A list entry that is an unmet forced word offers
+// nothing from its list lane -- the advance lane carries it -- so flat indices stay unique.  The C + 1 banks are served in turn over
+// the `beam` butterfly rounds, the lanes whose target is not the served bank offering (-inf, no index), as GROUPS masks; the winner's
+// own lane writes score_out.  No scratch, nothing but shuffles and the sel_k / sel_v words of LDS.
+struct BankArgs { const int32_t* force; int nforce; const float* fws; int unk; };
+template <bool GROUPS, bool BANKS = false> struct group_args { using type = NoGroups; };
+template <> struct group_args<true, false> { using type = GroupArgs; };
+template <> struct group_args<false, true> { using type = BankArgs; };
+
+template <bool HIST = false, bool GROUPS = false, bool BANKS = false>
 __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, const int* cand_i, const float* lse,
                                                         const float* score_in, const uint8_t* done_in, int beam, int V,
                                                         int first_step, int64_t* parent, int64_t* word, float* score_out,
                                                         uint8_t* done_out, typename hist_args<HIST>::type ha,
-                                                        typename group_args<GROUPS>::type ga) {
-    static_assert(HIST || !GROUPS, "the GROUPS form is a history form");
+                                                        typename group_args<GROUPS, BANKS>::type ga) {
+    static_assert(HIST || !(GROUPS || BANKS), "the GROUPS and BANKS forms are history forms");
+    static_assert(!(GROUPS && BANKS), "groups and banks exclude each other");
     const int b = blockIdx.x, lane = threadIdx.x;
     [[maybe_unused]] __shared__ int sel_k[BEAM_MAX], sel_v[BEAM_MAX];      // HIST: parent and word of every selected slot
     [[maybe_unused]] __shared__ int sel_p[BEAM_MAX];                       // GROUPS: its word if the parent was live, else -1
-    // lane -> candidate (k = lane / beam, r = lane % beam), beam*beam <= 64
-    const int k = lane / beam, r = lane - k * beam;
+    // lane -> candidate (k = lane / beam, r = lane % beam), beam*beam <= 64; BANKS: (bd + 2 C) lanes per row, see above
+    int k = lane / beam, r = lane - k * beam;
     float cv = -INFINITY;
     int flat = 0x7fffffff;
     [[maybe_unused]] int bd = beam, pw = -2;             // GROUPS: slots per group; this lane's word if it can be penalised
+    [[maybe_unused]] int tb = 0, adv = -1;               // BANKS: the candidate's target bank; the entry of an advance lane
     if constexpr (GROUPS) bd = beam / ga.groups;
+    if constexpr (BANKS) {
+        bd = beam / (ga.nforce + 1);
+        const int per = bd + 2 * ga.nforce;
+        k = lane / per;
+        r = lane - k * per;
+        adv = r - (bd + ga.nforce);
+    }
     if (k < beam) {
         const int row = b * beam + k;
         float sc = score_in[row];
         if (first_step && (GROUPS ? k % bd != 0 : k > 0)) sc = -INFINITY;
+        [[maybe_unused]] int unmet = 0;                  // BANKS: the clip's active entries the row's history does not hold
+        if constexpr (BANKS) {
+            const int fm = reinterpret_cast<const int*>(ga.fws)[(size_t)row * 4 + 3];
+            tb = __popc(fm & 7);
+            unmet = (fm >> 8) & ~fm & 7;
+        }
         if (done_in[row]) {
             // frozen hypothesis: candidates (k, 0) at the carried score, every other (k, v) at -inf; keep the
             // -inf fillers at distinct low flat indices so that tie-breaking matches a full scan
             cv = r == 0 ? sc : -INFINITY;
-            flat = k * V + r;
-        } else {
+            flat = adv >= 0 ? 0x7fffffff : k * V + r;
+        } else if (adv < 0) {
             const float v = cand_v[row * BEAM_MAX + r];
             const int vi = cand_i[row * BEAM_MAX + r];
             cv = (v == -INFINITY || sc == -INFINITY) ? -INFINITY : sc + (v - lse[row]);
             flat = vi == 0x7fffffff ? 0x7fffffff : k * V + vi;
             if constexpr (GROUPS) pw = vi == 0x7fffffff ? -2 : vi;
+            if constexpr (BANKS) {
+                for (int j = 0; j < ga.nforce; ++j)
+                    if (((unmet >> j) & 1) && ga.force[(size_t)b * ga.nforce + j] == vi) { cv = -INFINITY; flat = 0x7fffffff; }
+            }
+        } else if constexpr (BANKS) {
+            if ((unmet >> adv) & 1) {
+                const float v = ga.fws[(size_t)row * 4 + adv];
+                cv = (v == -INFINITY || sc == -INFINITY) ? -INFINITY : sc + (v - lse[row]);
+                flat = k * V + ga.force[(size_t)b * ga.nforce + adv];
+                tb += 1;
+            }
         }
     }
     [[maybe_unused]] float aug = -INFINITY;              // GROUPS: the candidate's augmented value while its group is served
@@ -890,6 +1000,11 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             bv = aug;
             bi = mine ? flat : 0x7fffffff;
         }
+        if constexpr (BANKS) {
+            const bool mine = tb == sel / bd;
+            bv = mine ? cv : -INFINITY;
+            bi = mine ? flat : 0x7fffffff;
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o, 64);
@@ -901,13 +1016,16 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             if (bi == 0x7fffffff) { kk = GROUPS ? g0 : 0; vv = 0; }      // every candidate NaN: parent / word feed gathers, keep them in range
             parent[b * beam + sel] = kk;
             word[b * beam + sel] = vv;
-            if (!GROUPS || bi == 0x7fffffff) score_out[b * beam + sel] = bv;
+            if (!(GROUPS || BANKS) || bi == 0x7fffffff) score_out[b * beam + sel] = bv;
             const bool frozen = done_in[b * beam + kk] != 0;
             done_out[b * beam + sel] = (frozen || vv == 0) ? 1 : 0;
             if constexpr (GROUPS) sel_p[sel] = (frozen || bi == 0x7fffffff || bv == -INFINITY) ? -1 : vv;
         }
         if constexpr (GROUPS) {
             if (flat == bi && bi != 0x7fffffff) { score_out[b * beam + sel] = cv; aug = -INFINITY; }      // the winner's lane
+        }
+        if constexpr (BANKS) {
+            if (flat == bi && bi != 0x7fffffff) score_out[b * beam + sel] = cv;                           // the winner's lane
         }
         if constexpr (HIST) {
             if (lane == 0) {
@@ -1306,12 +1424,13 @@ static int beam_select_check(const float* logits, int nparts, const float* score
 // behind the entry points, after the checks: the loader form of the row scan, then the merge.  HIST: the forms of both kernels that
 // know the hypotheses' histories (ra: the row scan's history and rules, ma: the merge's gather).  GROUPS: the HIST row scan and the
 // merge that serves the groups in turn (ga: their number and the diversity strength).
-template <bool HIST, bool GROUPS = false>
+// BANKS: the FORCE row scan and the merge that serves the banks in turn (ra, ga: the forced words and the rows' workspace slots).
+template <bool HIST, bool GROUPS = false, bool BANKS = false>
 static int beam_select_run(const float* logits, int nparts, long long part_stride, const float* bias, const float* score_in,
                            const uint8_t* done_in, int B, int beam, int V, int unk_idx, int first_step, int64_t* parent, int64_t* word,
                            float* score_out, uint8_t* done_out, float* workspace, cvc_stream_t stream,
-                           typename cons_args<HIST>::type ra, typename hist_args<HIST>::type ma,
-                           typename group_args<GROUPS>::type ga = {}) {
+                           typename scan_args<HIST, BANKS>::type ra, typename hist_args<HIST>::type ma,
+                           typename group_args<GROUPS, BANKS>::type ga = {}) {
     // workspace: [rows*8] candidate values, [rows*8] candidate indices, [rows] lse   (rows = B*beam)
     const int rows = B * beam;
     float* cand_v = workspace;
@@ -1325,7 +1444,7 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
     // 6 slabs: 64 workgroups pulling 600 KB each ingest at ~20 GB/s per compute unit; 320 row workgroups spread the same bytes
     // over the chip)
     if ((aligned && nparts == 1 && bias == nullptr) || slabs) {
-#define CVC_RT4P(NG_, NP_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, NP_, true, HIST>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
+#define CVC_RT4P(NG_, NP_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, NP_, true, HIST, BANKS>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
                                               nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse, ra)
 #define CVC_RT4(NG_) do { switch (slabs ? nparts : 0) { case 2: CVC_RT4P(NG_, 2); break; case 4: CVC_RT4P(NG_, 4); break; \
                                                          case 6: CVC_RT4P(NG_, 6); break; case 8: CVC_RT4P(NG_, 8); break; \
@@ -1343,7 +1462,7 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
 #undef CVC_RT4
 #undef CVC_RT4P
     } else {
-#define CVC_RT4G(NG_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, 0, false, HIST>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
+#define CVC_RT4G(NG_) hipLaunchKernelGGL((beam_rowtop4_kernel<NG_, 0, false, HIST, BANKS>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, \
                                          nparts, part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse, ra)
         switch ((V + 4 * WG - 1) / (4 * WG)) {
             case 1: CVC_RT4G(1); break;
@@ -1357,7 +1476,7 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
         }
 #undef CVC_RT4G
     }
-    hipLaunchKernelGGL((beam_merge_kernel<HIST, GROUPS>), dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
+    hipLaunchKernelGGL((beam_merge_kernel<HIST, GROUPS, BANKS>), dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
                        beam, V, first_step, parent, word, score_out, done_out, ma, ga);
     return cvc_launch_status();
 }
@@ -1376,11 +1495,13 @@ extern "C" int cvc_beam_select_parts(const float* logits, int nparts, long long 
 // The HIST forms of the two kernels above; first_step is t == 0; c == NULL: no rule but UNK.
 // groups == 0: the history block; groups >= 1 (cvc_beam_select_groups_parts): the GROUPS merge, groups == 1 included -- it is
 // the history block bit for bit (nothing is ever penalised) and the tests pin that on the form that serves the groups.
+// nforce >= 1 (cvc_beam_select_force_parts): the FORCE row scan and the BANKS merge.
 static int beam_select_hist(const float* logits, int nparts, long long part_stride, const float* bias,
                             const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
                             const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
                             int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
-                            float* workspace, cvc_stream_t stream, int groups, float lambda) {
+                            float* workspace, cvc_stream_t stream, int groups, float lambda, const int32_t* force = nullptr,
+                            int nforce = 0, int32_t* nmet = nullptr) {
     const int rc = beam_select_check(logits, nparts, score_in, done_in, B, beam, V, parent, word, score_out, done_out, workspace);
     if (rc != 0) return rc;
     if (t < 0 || t > CONS_T_MAX) return CVC_E_TOOBIG;
@@ -1391,6 +1512,12 @@ static int beam_select_hist(const float* logits, int nparts, long long part_stri
     const ConsArgs ra{hist_in, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
                       c->bad_end, c->nbad, nbanned};
     const HistArgs ma{hist_in, hist_out, hist_stride, t};
+    if (nforce > 0) {              // the rows' forced-word slots lie behind the history block's 17 floats per row
+        float* fws = workspace + (size_t)17 * B * beam;
+        return beam_select_run<true, false, true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0,
+                                                  parent, word, score_out, done_out, workspace, stream,
+                                                  ForceArgs{ra, force, nforce, fws, nmet}, ma, BankArgs{force, nforce, fws, unk_idx});
+    }
     if (groups == 0)
         return beam_select_run<true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0, parent,
                                      word, score_out, done_out, workspace, stream, ra, ma);
@@ -1418,6 +1545,19 @@ extern "C" int cvc_beam_select_groups_parts(const float* logits, int nparts, lon
     if (groups < 1 || (beam >= 1 && beam % groups != 0) || !(lambda >= 0.f) || isinf(lambda)) return CVC_E_BADARG;
     return beam_select_hist(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t, hist_in, hist_out, hist_stride, c,
                             parent, word, score_out, done_out, nbanned, workspace, stream, groups, lambda);
+}
+
+// Lexically constrained beam search: cvc_beam_select_hist_parts with `nforce` forced words per clip and the clip's slots in
+// nforce + 1 banks by the number of forced words met (the rule: the comment of beam_merge_kernel's BANKS form; contract:
+// include/cvc_hip_blocks.h).  workspace: 21 * B * beam floats.
+extern "C" int cvc_beam_select_force_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                           const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                           const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                           const int32_t* force, int nforce, int64_t* parent, int64_t* word, float* score_out,
+                                           uint8_t* done_out, int32_t* nbanned, int32_t* nmet, float* workspace, cvc_stream_t stream) {
+    if (!force || nforce < 1 || nforce > 3 || (beam >= 1 && beam % (nforce + 1) != 0)) return CVC_E_BADARG;
+    return beam_select_hist(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t, hist_in, hist_out, hist_stride, c,
+                            parent, word, score_out, done_out, nbanned, workspace, stream, 0, 0.f, force, nforce, nmet);
 }
 
 namespace {
@@ -1455,15 +1595,31 @@ __global__ __launch_bounds__(256) void beam_backtrack_kernel(const int64_t* word
 // lane s holds step s of the row and the ballot of (word == 0) gives the position.  norm(r) = score(r) / len(r)^alpha in fp32
 // (alpha == 0: score(r) itself, no power is evaluated; -inf stays -inf).  Lane k then counts the slots that come before slot k --
 // larger norm, ties -> lowest slot, NaN last -- and writes order[b, that count] = k.
-__global__ __launch_bounds__(64) void beam_rank_kernel(const int64_t* hist, long long stride, const float* score, int beam, int T,
-                                                       float alpha, int64_t* order, float* norm, int32_t* len) {
+// FORCE (cvc_beam_rank_force): nmet(r) = the number of the clip's active forced words (force_active()) in the row's T-step history,
+// one more ballot per entry; the slots then sort by the key (norm is NaN, norm == -inf, nmet descending, norm descending, slot):
+// the best hypothesis is the best-normed one among those that met the most forced words, and the fillers at -inf come after
+// every hypothesis.
+struct NoRankForce {};
+struct RankForceArgs { const int32_t* force; int nforce, V, unk; int32_t* nmet; };
+template <bool FORCE>
+__device__ __forceinline__ void beam_rank_body(const int64_t* hist, long long stride, const float* score, int beam, int T, float alpha,
+                                               int64_t* order, float* norm, int32_t* len,
+                                               std::conditional_t<FORCE, RankForceArgs, NoRankForce> fa) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int mylen = T;
+    [[maybe_unused]] int mymet = 0, act = 0;
+    if constexpr (FORCE) act = force_active(fa.force + (size_t)b * fa.nforce, fa.nforce, fa.V, fa.unk);
     for (int k = 0; k < beam; ++k) {
-        const bool zero = lane < T && hist[(size_t)lane * stride + (size_t)b * beam + k] == 0;
-        const unsigned long long m = __ballot(zero);
+        const long long h = lane < T ? (long long)hist[(size_t)lane * stride + (size_t)b * beam + k] : -1ll;
+        const unsigned long long m = __ballot(h == 0);
         const int l = m != 0ull ? __ffsll((long long)m) : T;
         if (lane == k) mylen = l;
+        if constexpr (FORCE) {
+            int met = 0;
+            for (int j = 0; j < fa.nforce; ++j)
+                if ((act >> j) & 1) met += __ballot(h == (long long)fa.force[(size_t)b * fa.nforce + j]) != 0ull ? 1 : 0;
+            if (lane == k) mymet = met;
+        }
     }
     float nv = -INFINITY;
     if (lane < beam) {
@@ -1471,26 +1627,61 @@ __global__ __launch_bounds__(64) void beam_rank_kernel(const int64_t* hist, long
         nv = alpha == 0.f ? sc : sc / powf((float)mylen, alpha);
         norm[b * beam + lane] = nv;
         len[b * beam + lane] = mylen;
+        if constexpr (FORCE) fa.nmet[b * beam + lane] = mymet;
     }
     const bool nan_me = nv != nv;
+    [[maybe_unused]] const int cls = nan_me ? 2 : (nv == -INFINITY ? 1 : 0);
     int before = 0;
     for (int j = 0; j < beam; ++j) {
         const float nj = __shfl(nv, j, 64);
         const bool nan_j = nj != nj;
-        const bool first = nan_me ? (!nan_j || j < lane) : (!nan_j && (nj > nv || (nj == nv && j < lane)));
+        bool first = nan_me ? (!nan_j || j < lane) : (!nan_j && (nj > nv || (nj == nv && j < lane)));
+        if constexpr (FORCE) {
+            const int mj = __shfl(mymet, j, 64), cj = nan_j ? 2 : (nj == -INFINITY ? 1 : 0);
+            first = cj != cls ? cj < cls : (mj != mymet ? mj > mymet : ((cls == 0 && nj != nv) ? nj > nv : j < lane));
+        }
         before += first ? 1 : 0;
     }
     if (lane < beam) order[b * beam + before] = lane;
 }
+__global__ __launch_bounds__(64) void beam_rank_kernel(const int64_t* hist, long long stride, const float* score, int beam, int T,
+                                                       float alpha, int64_t* order, float* norm, int32_t* len) {
+    beam_rank_body<false>(hist, stride, score, beam, T, alpha, order, norm, len, NoRankForce{});
+}
+__global__ __launch_bounds__(64) void beam_rank_force_kernel(const int64_t* hist, long long stride, const float* score, int beam, int T,
+                                                             float alpha, int64_t* order, float* norm, int32_t* len, RankForceArgs fa) {
+    beam_rank_body<true>(hist, stride, score, beam, T, alpha, order, norm, len, fa);
+}
 }  // namespace
 
-extern "C" int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
-                             int64_t* order, float* norm, int32_t* len, cvc_stream_t stream) {
+// the argument checks of the two ranking blocks
+static int beam_rank_check(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
+                           const int64_t* order, const float* norm, const int32_t* len) {
     if (!hist || !score || !order || !norm || !len || B < 1 || beam < 1 || beam > BEAM_MAX || T < 1) return CVC_E_BADARG;
     if (hist_stride < (long long)B * beam || !(alpha >= 0.f) || isinf(alpha)) return CVC_E_BADARG;
     if (T > CONS_T_MAX) return CVC_E_TOOBIG;
+    return 0;
+}
+
+extern "C" int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
+                             int64_t* order, float* norm, int32_t* len, cvc_stream_t stream) {
+    const int rc = beam_rank_check(hist, hist_stride, score, B, beam, T, alpha, order, norm, len);
+    if (rc != 0) return rc;
     hipLaunchKernelGGL(beam_rank_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, hist, hist_stride, score, beam, T, alpha, order, norm,
                        len);
+    return cvc_launch_status();
+}
+
+// cvc_beam_rank for the hypotheses of cvc_beam_select_force_parts: slots that met more forced words come first (contract:
+// include/cvc_hip_blocks.h)
+extern "C" int cvc_beam_rank_force(const int64_t* hist, long long hist_stride, const float* score, const int32_t* force, int nforce,
+                                   int B, int beam, int T, int V, int unk_idx, float alpha, int64_t* order, float* norm, int32_t* len,
+                                   int32_t* nmet, cvc_stream_t stream) {
+    if (!force || !nmet || nforce < 1 || nforce > 3 || V < 1) return CVC_E_BADARG;
+    const int rc = beam_rank_check(hist, hist_stride, score, B, beam, T, alpha, order, norm, len);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(beam_rank_force_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, hist, hist_stride, score, beam, T, alpha, order,
+                       norm, len, RankForceArgs{force, nforce, V, unk_idx, nmet});
     return cvc_launch_status();
 }
 

@@ -67,7 +67,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
                  min_len: int = 0, ban_words=None, bad_endings=None, beam_groups: int = 1, diversity: float = 0.0,
-                 length_penalty: float = 0.0, beam_history: bool = False):
+                 length_penalty: float = 0.0, force_n: int = 0, beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -136,7 +136,19 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         inside a captured graph: run() returns the best hypothesis by norm, its attention rows and the final scores, and
         hypotheses(ranked=True) returns (seq, score, norm, group) in that order.  Both need beam_history=True and beam > 1;
         beam % beam_groups != 0, a negative diversity and diversity != 0 with one group are refused.  1 / 0.0 / 0.0 (the default):
-        nothing changes."""
+        nothing changes.
+        force_n: 0 = off.  C in 1 .. 3: lexically constrained beam search ("Forced words"; the rule is the comment of
+        cvc_beam_select_force_parts in include/cvc_hip_blocks.h) -- up to C words per clip that the caption should contain
+        (load_force_words(); -1 = unused, so clips may have fewer).  A clip's beam = (C + 1) * bd slots are C + 1 banks by the number
+        of forced words a hypothesis has met; a candidate goes to the bank of its row's count, one higher if its word is a forced
+        word the row has not met, and every bank keeps its own bd best.  The word_select launch is cvc_beam_select_force_parts on
+        the tile path (fused slabs or finished logits) and on the ring path, C and t are launch constants and the words live in an
+        engine-owned device buffer (a captured graph serves new batches); it composes with the five constraints and with
+        length_penalty.  The decode ends with cvc_beam_rank_force (self.order, self.norm, self.hyp_len, self.final_nmet
+        [B, beam] int32) and cvc_beam_backtrack_from(order[:, 0]), both inside a captured graph: run() returns the best-normed
+        hypothesis among those that met the most forced words, hypotheses(ranked=True) returns (seq, score, norm, nmet) in that
+        order, and self.nmet [T, rows] int32 holds the count of every row entering step t.  Needs beam_history=True, beam > 1 and
+        beam % (force_n + 1) == 0; refused with beam_groups > 1."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -174,7 +186,24 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             raise RuntimeError(f"DecodeEngine: length_penalty must be a finite number >= 0, got {length_penalty!r}")
         self.groups, self.diversity, self.length_penalty = int(beam_groups), float(diversity), float(length_penalty)
         self.grouped = self.groups > 1
-        self.ranked = self.grouped or self.length_penalty != 0.0          # the decode ends with cvc_beam_rank / cvc_beam_backtrack_from
+        if isinstance(force_n, bool) or not isinstance(force_n, (int, np.integer)) or not 0 <= force_n <= 3:
+            raise RuntimeError(f"DecodeEngine: force_n must be an integer in 0 .. 3 (0 = off), got {force_n!r}")
+        self.force_n = int(force_n)
+        self.forcing = self.force_n >= 1
+        if self.forcing:
+            if self.beam == 1:
+                raise RuntimeError("DecodeEngine: force_n is an option of beam search: it needs beam > 1")
+            if not self.beam_hist:
+                raise RuntimeError("DecodeEngine: force_n needs beam_history=True (the forced words a hypothesis has met are read from "
+                                   "its own history)")
+            if self.beam % (self.force_n + 1) != 0:
+                raise RuntimeError(f"DecodeEngine: force_n = {self.force_n} needs beam % (force_n + 1) == 0 (one bank per number of "
+                                   f"forced words met), got beam = {self.beam}")
+            if self.grouped:
+                raise RuntimeError("DecodeEngine: force_n and beam_groups > 1 exclude each other (banks and groups both divide the "
+                                   "clip's slots)")
+        # the decode ends with cvc_beam_rank (cvc_beam_rank_force) / cvc_beam_backtrack_from
+        self.ranked = self.grouped or self.length_penalty != 0.0 or self.forcing
         if self.ranked:
             what = "beam_groups > 1" if self.grouped else "length_penalty != 0"
             if self.beam == 1:
@@ -318,13 +347,17 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.bt_seq = torch.zeros(self.B, self.T, dtype=torch.int64, device=dev)      # the returned hypothesis (cvc_beam_backtrack: rank 0; ranked engines: the best by norm)
             self.bt_att = z(self.B, self.T, N)
             self.gather_tmp = [z(rows, R) for _ in range(4)]
-            self.beam_ws = z(17 * rows)
+            self.beam_ws = z((21 if self.forcing else 17) * rows)
             if self.beam_hist:               # the hypotheses' own histories, ping-pong: step t reads [t & 1], writes [(t + 1) & 1]
                 self.bhist = torch.zeros(2, self.T, rows, dtype=torch.int64, device=dev)
             if self.ranked:                  # the final ranking (cvc_beam_rank): slots by norm, norm, len
                 self.order = torch.zeros(self.B, self.beam, dtype=torch.int64, device=dev)
                 self.norm = z(self.B, self.beam)
                 self.hyp_len = torch.zeros(self.B, self.beam, dtype=torch.int32, device=dev)
+            if self.forcing:                 # the forced words (load_force_words), n(r) of the rows entering each step, n of the final slots
+                self.force_words = torch.full((self.B, self.force_n), -1, dtype=torch.int32, device=dev)
+                self.nmet = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)
+                self.final_nmet = torch.zeros(self.B, self.beam, dtype=torch.int32, device=dev)
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
@@ -542,6 +575,26 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.words[1:].copy_(words.t())
         return self
 
+    def load_force_words(self, words):
+        """Lexically constrained beam search (force_n = C >= 1): the words the captions should contain, [B, C] integers, -1 (or any
+        inactive entry: 0, UNK, a duplicate) = unused.  Copied into the engine-owned self.force_words (int32) -- a stream-ordered
+        copy, so a captured graph serves new batches as load_features() does it.  Refused: another shape, an id >= V, a word that
+        ban_words forbids."""
+        if not self.forcing:
+            raise RuntimeError("DecodeEngine.load_force_words: this engine forces no words (force_n = 0)")
+        w = torch.as_tensor(np.asarray(words.cpu()) if isinstance(words, torch.Tensor) else np.asarray(words))
+        if tuple(w.shape) != (self.B, self.force_n) or w.dtype.is_floating_point or w.dtype == torch.bool:
+            raise RuntimeError(f"DecodeEngine.load_force_words: words must be integers [{self.B}, {self.force_n}], got {w.dtype} "
+                               f"{tuple(w.shape)}")
+        big = sorted({int(v) for v in w.reshape(-1).tolist() if v >= self.W.V})
+        if big:
+            raise RuntimeError(f"DecodeEngine.load_force_words: ids outside [0, V = {self.W.V}): {big}")
+        both = sorted({int(v) for v in w.reshape(-1).tolist()} & set(self.cons[3]))
+        if both:
+            raise RuntimeError(f"DecodeEngine.load_force_words: words that ban_words forbids cannot be forced: {both}")
+        self.force_words.copy_(w.to(torch.int32))
+        return self
+
     def _region_set(self, t):
         """The region feature set of step t's attention passes; the forced mode with a frame mask bound adds the mask and the
         frame-masked output of that step."""
@@ -616,13 +669,17 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         hist = (t, self.bhist[srd].data_ptr(), self.bhist[swr].data_ptr(), self.rows, cons[0])
         if self.grouped:
             return ("word_select", L.cvc_beam_select_groups_parts, head + hist + (self.groups, self.diversity) + tail + (cons[1], ws))
+        if self.forcing:
+            return ("word_select", L.cvc_beam_select_force_parts, head + hist + (self.force_words.data_ptr(), self.force_n) + tail +
+                    (cons[1], self.nmet[t].data_ptr(), ws))
         return ("word_select", L.cvc_beam_select_hist_parts, head + hist + tail + (cons[1], ws))
 
     def hypotheses(self, ranked: bool = False):
         """n-best: all `beam` hypotheses of every clip after run(), in slot order (one group: rank order by score) -- (seq
         [B, beam, T] int64, score [B, beam]), views of engine-owned buffers (beam_history=True: the histories the selection block
         carried, no backtracking).  ranked=True (beam_groups > 1 or a length_penalty): (seq, score, norm, group [B, beam] int64) in
-        the order of cvc_beam_rank -- norm descending, ties to the lowest slot -- as new tensors."""
+        the order of cvc_beam_rank -- norm descending, ties to the lowest slot -- as new tensors; with force_n the fourth is nmet
+        [B, beam] int32, the forced words each hypothesis met, and the order is cvc_beam_rank_force's."""
         if not self.beam_hist:
             raise RuntimeError("DecodeEngine.hypotheses needs beam_history=True")
         B, beam, T = self.B, self.beam, self.T
@@ -630,10 +687,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if not ranked:
             return seq, score
         if not self.ranked:
-            raise RuntimeError("DecodeEngine.hypotheses(ranked=True) needs beam_groups > 1 or a length_penalty")
+            raise RuntimeError("DecodeEngine.hypotheses(ranked=True) needs beam_groups > 1, a length_penalty or force_n")
         o = self.order
         return (seq.gather(1, o.unsqueeze(2).expand(B, beam, T)), score.gather(1, o), self.norm.gather(1, o),
-                o // (beam // self.groups))
+                self.final_nmet.gather(1, o) if self.forcing else o // (beam // self.groups))
 
     def _python_launches(self):
         if self._launches is None:
@@ -659,9 +716,15 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self._run_launches()
         if self.beam > 1 and self.ranked:                  # the final ranking, then the best hypothesis by norm: two launches
             L, T = hip.lib(), self.T
-            hip._check(L.cvc_beam_rank(self.bhist[T & 1].data_ptr(), self.rows, self.score[T & 1].data_ptr(), self.B, self.beam, T,
-                                       self.length_penalty, self.order.data_ptr(), self.norm.data_ptr(), self.hyp_len.data_ptr(),
-                                       hip._stream()), "cvc_beam_rank")
+            if self.forcing:
+                hip._check(L.cvc_beam_rank_force(self.bhist[T & 1].data_ptr(), self.rows, self.score[T & 1].data_ptr(),
+                                                 self.force_words.data_ptr(), self.force_n, self.B, self.beam, T, self.W.V, self.unk,
+                                                 self.length_penalty, self.order.data_ptr(), self.norm.data_ptr(),
+                                                 self.hyp_len.data_ptr(), self.final_nmet.data_ptr(), hip._stream()), "cvc_beam_rank_force")
+            else:
+                hip._check(L.cvc_beam_rank(self.bhist[T & 1].data_ptr(), self.rows, self.score[T & 1].data_ptr(), self.B, self.beam, T,
+                                           self.length_penalty, self.order.data_ptr(), self.norm.data_ptr(), self.hyp_len.data_ptr(),
+                                           hip._stream()), "cvc_beam_rank")
             hip._check(L.cvc_beam_backtrack_from(self.words[1:].data_ptr(), self.parent.data_ptr(), self.att_steps.data_ptr(), self.B,
                                                  self.beam, T, self.N, self.order.data_ptr(), self.beam, self.bt_seq.data_ptr(),
                                                  self.bt_att.data_ptr(), hip._stream()), "cvc_beam_backtrack_from")
@@ -680,7 +743,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
         key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist, self.grouped, self.ranked)
+               self.beam_hist, self.grouped, self.ranked, self.forcing)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode

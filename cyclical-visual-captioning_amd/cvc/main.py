@@ -52,6 +52,11 @@ def main(argv=None, sample=None, score=None):
     parser.add_argument("--diversity_lambda", type=float, default=0.0, help="Hamming diversity penalty between the groups; 0 = off")
     parser.add_argument("--length_penalty", type=float, default=0.0,
                         help="rank the final hypotheses by score / length^alpha; 0 = by score")
+    # lexically constrained beam search (DecodeEngine force_n): words every caption should contain, or the clip's detections
+    parser.add_argument("--force_words", type=str, default="", help="up to 3 comma-separated words (or word ids) every caption should "
+                                                                    "contain (beam search; beam_size a multiple of their number + 1)")
+    parser.add_argument("--force_detected", type=int, default=0,
+                        help="force per clip the words of its C best-scored detection classes (C <= 3); 0 = off")
     parser.add_argument("--no_cfg", action="store_true", help="skip the YAML overlay (pure CLI)")
     parser.add_argument("--synthetic_raw", action="store_true",
                         help="feed raw frame / region features through the once-per-clip encoder (model/backbone.py) "
@@ -108,6 +113,9 @@ def main(argv=None, sample=None, score=None):
         raise SystemExit("--no_repeat_ngram and --min_caption_len must be >= 0")
     if opt.group_size < 1 or opt.diversity_lambda < 0 or opt.length_penalty < 0:
         raise SystemExit("--group_size must be >= 1, --diversity_lambda and --length_penalty >= 0")
+    opt.force_word_ids = word_ids(opt.force_words, opt.wtoi, "--force_words")
+    if len(opt.force_word_ids) > 3 or not 0 <= opt.force_detected <= 3 or (opt.force_word_ids and opt.force_detected):
+        raise SystemExit("--force_words takes at most 3 words, --force_detected lies in 0 .. 3, and only one of them is given")
     opt.ban_word_ids = word_ids(opt.ban_words, opt.wtoi, "--ban_words")
     opt.bad_ending_ids = word_ids(opt.bad_endings, opt.wtoi, "--bad_endings")
     model = build_model(opt, device)

@@ -40,6 +40,26 @@ def decode_sequence(itow, itod, ltow, itoc, wtod, seq, vocab_size, opt):
     return out
 
 
+def detected_force_words(proposals, num, C, itod, wtoi, unk_idx):
+    """The words to force per clip from its detections (DecodeEngine.load_force_words): proposals [B, P, 7] with the columns the
+    data loader documents (class at 5, score at 6), num [B, 7] with the count of valid proposals at 1.  Of the clip's valid proposals'
+    classes whose itod name is a single word of the vocabulary wtoi other than UNK and word 0, the C distinct ones with the
+    highest proposal score, ties to the lower class index.  -> [B, C] int64 on the host, missing entries -1."""
+    props, num = torch.as_tensor(proposals).detach().cpu(), torch.as_tensor(num).detach().cpu()
+    out = torch.full((props.shape[0], int(C)), -1, dtype=torch.int64)
+    for b in range(props.shape[0]):
+        best = {}
+        for p in props[b, :max(0, min(int(num[b, 1]), props.shape[1]))].tolist():
+            cls = int(p[5])
+            name = itod.get(str(cls), itod.get(cls))
+            if name is None or name not in wtoi or int(wtoi[name]) in (0, int(unk_idx)):
+                continue
+            best[cls] = max(best.get(cls, float("-inf")), float(p[6]))
+        for j, cls in enumerate(sorted(best, key=lambda c: (-best[c], c))[:int(C)]):
+            out[b, j] = int(wtoi[itod.get(str(cls), itod.get(cls))])
+    return out
+
+
 def _text_mask(target):
     m = target.gt(0)
     return torch.cat([torch.ones_like(m[:, :1]), m[:, :-1]], 1)   # includes the first EOS (:135-137)

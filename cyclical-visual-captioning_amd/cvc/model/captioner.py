@@ -110,6 +110,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.beam_groups = int(getattr(opts, "group_size", 1))
         self.diversity_lambda = float(getattr(opts, "diversity_lambda", 0.0))
         self.length_penalty = float(getattr(opts, "length_penalty", 0.0))
+        # lexically constrained beam search (DecodeEngine force_n): word ids every caption should contain, or per clip the words of
+        # its force_detected best-scored detection classes (cvc.misc.utils.detected_force_words)
+        self.force_words = tuple(getattr(opts, "force_word_ids", None) or ())
+        self.force_detected = int(getattr(opts, "force_detected", 0))
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
         self.decode_weights_dtype = getattr(opts, "decode_weights", "fp32")
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
@@ -475,7 +479,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 sample_n: Optional[int] = None, seed: Optional[int] = None, decode_weights: Optional[str] = None,
                 top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
                 no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
-                beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None):
+                beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None,
+                force_words=None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -492,7 +497,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         beam_groups / diversity_lambda / length_penalty (arguments, else the model's attributes, read from opts.group_size /
         diversity_lambda / length_penalty): DecodeEngine's diverse beam search and length-normalised final ranking; with
         beam_size > 1 and any of them on the engine is built with beam_history=True and seq is the best hypothesis by norm (all of
-        them: engine.hypotheses(ranked=True)).  With beam_size == 1 the engine refuses them."""
+        them: engine.hypotheses(ranked=True)).  With beam_size == 1 the engine refuses them.
+        force_words (argument, else the model's attributes, read from opts.force_word_ids / opts.force_detected): words the captions
+        should contain, DecodeEngine's force_n -- a [B, C] integer tensor (-1 = unused) or a list of C ids applied to every clip,
+        C <= 3; the engine is built with beam_history=True and force_n = C, the words are loaded into it for every batch, and seq is
+        the best-normed hypothesis among those that met the most forced words."""
         _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
             segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
@@ -514,11 +523,19 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         groups = self.beam_groups if beam_groups is None else int(beam_groups)
         lam = self.diversity_lambda if diversity_lambda is None else float(diversity_lambda)
         alpha = self.length_penalty if length_penalty is None else float(length_penalty)
+        if force_words is None:
+            if self.force_detected > 0:
+                force_words = utils.detected_force_words(proposals, num, self.force_detected, self.opts.itod, self.opts.wtoi, self.unk_idx)
+            elif self.force_words:
+                force_words = self.force_words
+        if force_words is not None and not isinstance(force_words, torch.Tensor):        # ids applied to every clip
+            force_words = torch.tensor([int(w) for w in force_words], dtype=torch.int64).view(1, -1).expand(fc_feats.shape[0], -1)
+        force_n = 0 if force_words is None else int(force_words.shape[-1])
         weights = self.decode_weights()
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, tuple(cons.values()), groups, lam, alpha)
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha)
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -532,11 +549,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
                                   sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
-                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0),
-                                  beam_groups=groups, diversity=lam, length_penalty=alpha, **cons)
+                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0),
+                                  beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n, **cons)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)
+        if force_n > 0:
+            engine.load_force_words(force_words)
         res = engine.run()
         if sampling or (engine.constrained and beam == 1):
             return res[0].clone(), res[1].clone(), res[2].clone()

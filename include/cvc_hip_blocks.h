@@ -254,6 +254,45 @@ int cvc_beam_select_groups_parts(const float* parts, int nparts, long long part_
  * CVC_E_TOOBIG. */
 int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
                   int64_t* order, float* norm, int32_t* len, cvc_stream_t stream);
+/* Lexically constrained beam search (Anderson et al. 2017; the bank formulation of Post & Vilar 2018; csrc/vocab.hip: the FORCE form
+ * of the row scan and the BANKS form of the merge of cvc_beam_select_hist_parts): cvc_beam_select_hist_parts with up to C = nforce
+ * words per clip that a caption should contain, and the clip's slots in C + 1 banks by the number of forced words met.
+ *   forced      force[b * C + j], int32 on the device, C in {1, 2, 3}.  Entry j of clip b is ACTIVE iff 0 < w < V, w != unk_idx and no
+ *               entry j' < j of the clip holds the same w; anything else (-1, 0, UNK, out of range, a duplicate) is unused, so a clip
+ *               may have fewer than C forced words, or none.  Words only, no phrases.
+ *   banks       beam = (C + 1) * bd; slots [j * bd, (j + 1) * bd) of a clip are bank j.  For row r = (b, k) entering step t with
+ *               history y_0 .. y_{t-1}: met(r) = the active entries of clip b whose word occurs in the history, n(r) = |met(r)|.
+ *               Routing uses n(r) from the history, not the slot.
+ *   candidates  the base value c(k, v) is the candidate of cvc_beam_select_hist_parts: score_in[k] + z[k, v] - lse[k], the
+ *               log-sum-exp over the full row, -inf for v in Ban(t, r) -- a forced word the ban set holds at this step is -inf for
+ *               this step like any banned word -- and a frozen row offers only (k, 0) at its carried score.  t == 0: only slot 0 of
+ *               a clip is live.  The TARGET bank of (k, v) is n(r) + 1 if r is live and v is an active forced word of clip b that
+ *               is not in met(r), else n(r).
+ *   selection   bank j takes the bd best candidates whose target bank is j, over all rows of the clip, ties -> lowest flat (k, v)
+ *               with k the clip-wide slot; the i-th best goes to slot j * bd + i.  Fewer than bd finite candidates: the rest of the
+ *               bank are fillers -- score_out = -inf, parent in [0, beam), word in [0, V), done_out, the history gather and the
+ *               append as for any slot; what a filler holds besides its -inf score is not part of the rule.  A row at -inf offers
+ *               only -inf thereafter.
+ *   outputs     score_out = c (scores stay sums of the model's log-probs); parent, word, done_out, the histories and nbanned as
+ *               cvc_beam_select_hist_parts writes them; nmet[r] = n(r) for every input row (nullable).  There is no implicit
+ *               end-of-sentence rule: a hypothesis may end in any bank; min_len and bad_end compose as before.
+ *   invariant   every slot with a finite score in bank j has exactly j active forced words in its history.
+ * workspace: 21 * B * beam floats (the 17 of cvc_beam_select_hist_parts, then per row its values at the forced words and its met
+ * mask).  The checks of cvc_beam_select_hist_parts with their codes; nforce outside [1, 3], beam % (nforce + 1) != 0, NULL force:
+ * CVC_E_BADARG.  Nothing is launched on a refusal.  Bitwise deterministic. */
+int cvc_beam_select_force_parts(const float* parts, int nparts, long long part_stride, const float* bias,
+                                const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                const int32_t* force, int nforce, int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out,
+                                int32_t* nbanned, int32_t* nmet, float* workspace, cvc_stream_t stream);
+/* cvc_beam_rank for the hypotheses of cvc_beam_select_force_parts (force, nforce, V, unk_idx as there).  len and norm as
+ * cvc_beam_rank defines them; nmet[r] = the number of the clip's active forced words in r's T-step history.
+ *   order[b, :] = the clip's slots by the key: norm is NaN, last; then norm == -inf; nmet descending; norm descending; lowest slot.
+ * The best hypothesis is the best-normed one among those that met the most forced words.  The checks of cvc_beam_rank; NULL force or
+ * nmet, nforce outside [1, 3], V < 1: CVC_E_BADARG. */
+int cvc_beam_rank_force(const int64_t* hist, long long hist_stride, const float* score, const int32_t* force, int nforce, int B,
+                        int beam, int T, int V, int unk_idx, float alpha, int64_t* order, float* norm, int32_t* len, int32_t* nmet,
+                        cvc_stream_t stream);
 /* cvc_beam_backtrack (include/cvc_hip.h) from slot start[b * start_stride] of clip b instead of slot 0 (the same kernel; the slot
  * is clamped to [0, beam) like a parent; start_stride = beam reads column 0 of cvc_beam_rank's order in place).  start == 0
  * everywhere: the bits of cvc_beam_backtrack.  Its checks; NULL start, start_stride < 1: CVC_E_BADARG. */
