@@ -580,7 +580,11 @@ bool fast_ok(const cvc_gemm_seg* segs, int nsegs, int Nout_rows) {
     for (int s = 0; s < nsegs; ++s) {
         if (segs[s].k % RK) return false;
         if ((segs[s].ldx & 3) || (segs[s].ldw & 3)) return false;
-        if ((long long)Nout_rows * segs[s].ldw >= (1LL << 32) - 64) return false;   // 32-bit element offsets
+        // the ring kernel forms per-lane BYTE offsets in 32 bits (woff / xoff): the chunk of the last weight row and of the
+        // last of a slab's 64 dense activation rows must end below 2^32.  (A gathered table's height is not visible here:
+        // rows * ldx * 4 < 2^32 is the caller's, see cvc_gemm_seg.)  Anything wider takes the direct-load kernel (size_t offsets).
+        if (((long long)Nout_rows - 1) * segs[s].ldw * 4 + RK * 4 > (1LL << 32)) return false;
+        if (segs[s].idx == nullptr && 63LL * segs[s].ldx * 4 + RK * 4 > (1LL << 32)) return false;
         gathers += segs[s].idx != nullptr;
     }
     return gathers <= 1;

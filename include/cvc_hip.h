@@ -114,6 +114,10 @@ typedef struct {
     int relu;            /* max(0, x) on load (the embedding's ReLU)                            */
 } cvc_gemm_seg;
 
+/* Offsets: the LDS-DMA fast path (every k % 32 == 0, at most one gather segment) addresses rows by 32-bit BYTE offsets; the host
+ * takes it only where (Nout - 1) * ldw * 4 + 128 <= 2^32 and, for a dense x, 63 * ldx * 4 + 128 <= 2^32, and sends every other
+ * shape to the direct-load kernel (64-bit offsets).  The height of a gathered table is not visible to it: a gather segment
+ * REQUIRES rows * ldx * 4 < 2^32 for its table (all entry points below and cvc_lstm_cell_fwd). */
 /* y[M, Nout] (ld ldy) = concat-GEMM + bias[Nout] (nullable) + bias2[Nout] (nullable) */
 CVC_API int cvc_linear_fwd(const cvc_gemm_seg* segs, int nsegs, const float* bias, const float* bias2,
                    int M, int Nout, float* y, int ldy, cvc_stream_t stream);

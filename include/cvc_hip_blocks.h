@@ -47,8 +47,24 @@ int cvc_tile_gemm_big(int on, int min_wgs);
  * workgroups (one per compute unit), else 1.  chunk_rows = rows one workgroup walks, workgroups = the grid size.  Host only; any of
  * the three outputs may be NULL.  CVC_E_BADARG for M, N < 1 or K not a positive multiple of 16. */
 int cvc_tile_gemm_plan(int M, int N, int K, int* ksplit, int* chunk_rows, int* workgroups);
+/* Split-K form of cvc_linear_fwd (cvc_hip.h; segments as there): y_parts [ksplit][M][Nout] contiguous, slice s at
+ * y_parts + s * M * Nout.  Slice s holds the product over whole 32-column chunks [nch s / ksplit, nch (s + 1) / ksplit) (integer
+ * division) of EVERY segment, nch = ceil(k / 32) of that segment, a ragged last chunk ending at k; slice 0 also holds the bias
+ * (nullable).  A slice that owns no chunk of any segment is written all the same: exact zeros (slice 0: the bias itself).  The
+ * consumer sums the slices in a fixed order.  CVC_E_BADARG: M < 1 or M > 64, Nout < 1, ksplit < 1 or ksplit > 64, y_parts NULL,
+ * a gather segment (idx != NULL) with ksplit > 1, and every segment cvc_linear_fwd refuses (nsegs outside 1 .. 4, k < 4 or
+ * k % 4, ldx % 4, ldw % 4, x or w NULL or off 16-byte alignment); nothing is launched and y_parts is untouched then.  Pinned by
+ * tests/test_gpu_skinny_gemm.py. */
 int cvc_linear_splitk_fwd(const cvc_gemm_seg* segs, int nsegs, const float* bias, int M, int Nout,
                           int ksplit, float* y_parts, cvc_stream_t stream);
+/* cvc_linear_fwd with the word-selection records fused into the epilogue: top2_part [ceil(Nout / 32)][64][6] floats; block b,
+ * row m < M holds {v1, i1, v2, i2, mx, se} of columns [32 b, min(32 b + 32, Nout)) of y (bias included): the largest value and its
+ * column, the second largest and its column (columns are GLOBAL int32 indices stored as float bits), mx == v1 bit for bit and
+ * se = sum exp(y - mx) over the block's valid columns.  v1 / v2 are the bits of the same launch's y.  Equal values: the lower
+ * column comes first (top-1 before top-2, and the kept one of two equal candidates for top-2).  A block with one valid column
+ * has (v2, i2) = (-inf, 0x7fffffff).  Rows >= M of every block are untouched.  y_or_null [M][Nout] (ld Nout) receives the logits
+ * if given; the records are the same bits either way.  CVC_E_BADARG: top2_part NULL, M < 1, Nout < 1, a refused segment (see
+ * above); CVC_E_TOOBIG: M > 64; nothing is launched and neither output is touched then.  cvc_top2_final merges the records. */
 int cvc_linear_top2_fwd(const cvc_gemm_seg* segs, int nsegs, const float* bias, int M, int Nout,
                         float* y_or_null, float* top2_part, cvc_stream_t stream);
 int cvc_top2_final(const float* part, int nblocks, int M, int unk_idx, int64_t* word, int word_stride,
