@@ -1,6 +1,6 @@
 // The ban set of constrained decoding, once: what a selection kernel that knows its row's history takes on top of its own arguments,
 // the checks of the rules, and the V-bit LDS map built from the history and the lists.  Shared by the sampling kernel's CONS form
-// (csrc/sample_select.h, cvc_constrained_select_parts) and the beam row scan's HIST form (csrc/vocab.hip,
+// (csrc/sample_select.h, cvc_constrained_select_parts) and the beam row scan's HIST form (csrc/beam.hip,
 // cvc_beam_select_hist_parts), so the two cannot drift.  The rule: the comment of cvc_constrained_select_parts in
 // include/cvc_hip_blocks.h.
 #pragma once

@@ -1,5 +1,5 @@
 // Segment arithmetic of the grouped stream-K GEMM (gemm_gsk.hip), shared with the kernels that sum its partial tiles:
-// the late LSTM gate kernel (gemm_packed.hip), the score pass's query load (attn_scores.h) and the word selection (vocab.hip).
+// the late LSTM gate kernel (gemm_packed.hip), the score pass's query load (attn_scores.h) and the greedy word selection (vocab.hip).
 //
 // A launch walks a linear space of UNITS, one unit = (256-row tile, one 32-k chunk): the tiles of group 0 first (tile-major,
 // chunk-minor), then group 1, ...  Workgroup w owns units [w U, (w + 1) U).  Its intersection with a tile is one SEGMENT of that

@@ -25,8 +25,6 @@ template <> struct trunc_args<true> { using type = TruncArgs; };
 // below KEY_NEG_INF are NaNs)
 __device__ __forceinline__ float unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) { return (va > vb) | ((va == vb) & (ia < ib)); }
-
 // the Gumbel perturbation of hash value h (its 23 high bits)
 __device__ __forceinline__ float gumbel(uint32_t h) {
     const float u = ((float)(h >> 9) + 0.5f) * 0x1p-23f;

@@ -4,12 +4,11 @@
 // slab 0 + slab 1 + ... + bias), so every block sees the logits of the greedy / beam selection bit for bit; the argument checks and
 // the NC / NP / VEC choice of the entry points are here too, once.
 #pragma once
-#include "cvc_common.h"
+#include "row_block.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int WG = 256;
 constexpr int NC_MAX = 32;                     // logits per thread: V <= 8192, the bound of cvc_beam_select_parts
 
 // the column of register slot u.  VEC: NC / 4 float4 groups, slot u at column (tid + (u / 4) * WG) * 4 + u % 4; otherwise tid + u * WG

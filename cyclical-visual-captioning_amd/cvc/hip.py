@@ -246,12 +246,12 @@ SIGNATURES = {
                                      _P, _P],
     "cvc_beam_select_hist_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _P, _P, _P, _P, _P,
                                    _P, _P],
-    # diverse (group) beam search and the length-normalised final ranking (csrc/vocab.hip; building blocks)
+    # diverse (group) beam search and the length-normalised final ranking (csrc/beam.hip; building blocks)
     "cvc_beam_select_groups_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _I, _F, _P, _P, _P,
                                      _P, _P, _P, _P],
     "cvc_beam_rank": [_P, _LL, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "cvc_beam_backtrack_from": [_P, _P, _P, _I, _I, _I, _I, _P, _LL, _P, _P, _P],
-    # lexically constrained beam search: forced words per clip, banks, and its final ranking (csrc/vocab.hip; building blocks)
+    # lexically constrained beam search: forced words per clip, banks, and its final ranking (csrc/beam.hip; building blocks)
     "cvc_beam_select_force_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _P, _I, _P, _P, _P,
                                     _P, _P, _P, _P, _P],
     "cvc_beam_rank_force": [_P, _LL, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P],

@@ -208,7 +208,7 @@ int cvc_constrained_select_parts(const float* parts, int nparts, long long part_
                                  int64_t* word, int word_stride, float* logprob, float* cutoff, int32_t* kept,
                                  const int64_t* hist, long long hist_stride, const cvc_constraint* c, int32_t* nbanned,
                                  cvc_stream_t stream);
-/* Constrained beam search (csrc/vocab.hip: the HIST forms of the row scan and the merge of cvc_beam_select_parts; the ban set is
+/* Constrained beam search (csrc/beam.hip: the HIST forms of the row scan and the merge of cvc_beam_select_parts; the ban set is
  * the one definition of csrc/ban_set.h that cvc_constrained_select_parts uses): one beam-search step for hypotheses that carry
  * their own histories, with the rules of constrained decoding applied per hypothesis.
  *   Hypothesis row r = b * beam + k enters step t with history y_0 .. y_{t-1}, the words on its own path from the root: element
@@ -236,7 +236,7 @@ int cvc_beam_select_hist_parts(const float* parts, int nparts, long long part_st
                                const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
                                int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, int32_t* nbanned,
                                float* workspace, cvc_stream_t stream);
-/* Diverse (group) beam search (Vijayakumar et al. 2016; csrc/vocab.hip: the GROUPS form of the merge of cvc_beam_select_hist_parts,
+/* Diverse (group) beam search (Vijayakumar et al. 2016; csrc/beam.hip: the GROUPS form of the merge of cvc_beam_select_hist_parts,
  * the row scan is that block's): cvc_beam_select_hist_parts with the clip's `beam` = groups * bd slots in `groups` groups that are
  * served in turn within the step, later groups penalised for the words earlier ones took.  Slot k belongs to group g = k / bd.
  *   base        c(k, v) = the candidate of cvc_beam_select_hist_parts: score_in[k] + z[k, v] - lse[k], the log-sum-exp over the full
@@ -270,7 +270,7 @@ int cvc_beam_select_groups_parts(const float* parts, int nparts, long long part_
  * CVC_E_TOOBIG. */
 int cvc_beam_rank(const int64_t* hist, long long hist_stride, const float* score, int B, int beam, int T, float alpha,
                   int64_t* order, float* norm, int32_t* len, cvc_stream_t stream);
-/* Lexically constrained beam search (Anderson et al. 2017; the bank formulation of Post & Vilar 2018; csrc/vocab.hip: the FORCE form
+/* Lexically constrained beam search (Anderson et al. 2017; the bank formulation of Post & Vilar 2018; csrc/beam.hip: the FORCE form
  * of the row scan and the BANKS form of the merge of cvc_beam_select_hist_parts): cvc_beam_select_hist_parts with up to C = nforce
  * words per clip that a caption should contain, and the clip's slots in C + 1 banks by the number of forced words met.
  *   forced      force[b * C + j], int32 on the device, C in {1, 2, 3}.  Entry j of clip b is ACTIVE iff 0 < w < V, w != unk_idx and no

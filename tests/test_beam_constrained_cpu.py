@@ -44,7 +44,7 @@ def test_block_is_in_the_table_and_bound_with_the_headers_argument_count():
     assert f"CVC_B({NAME})" in blocks_src
     # one definition of the ban set: both kernels call the shared header's function
     csrc = os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc")
-    for f in ("sample_select.h", "vocab.hip"):
+    for f in ("sample_select.h", "beam.hip"):
         text = open(os.path.join(csrc, f)).read()
         assert '#include "ban_set.h"' in text and "build_ban_map<WG>(" in text and "atomicOr" not in text, f
 

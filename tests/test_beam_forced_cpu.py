@@ -52,10 +52,10 @@ def test_blocks_are_in_the_table_and_bound_with_the_headers_argument_counts():
     assert nargs[NAMES[1]] == len(hip.SIGNATURES["cvc_beam_rank"]) + 5
     # one definition: the header states the rule, the kernels' comment states it, the workspace size is said
     header = open(os.path.join(ROOT, "include", "cvc_hip_blocks.h")).read()
-    vocab = open(os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc", "vocab.hip")).read()
-    for text in (header, vocab):
+    beam = open(os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc", "beam.hip")).read()
+    for text in (header, beam):
         assert all(k in text for k in ("ACTIVE iff 0 < w < V", "Routing uses", "invariant", "21 * B * beam floats"))
-    assert "bd + 2 C" in vocab and "64 at beam 8, C = 3" in vocab                          # the sufficiency argument, in the kernel comment
+    assert "bd + 2 C" in beam and "64 at beam 8, C = 3" in beam                            # the sufficiency argument, in the kernel comment
 
 
 def test_host_argument_checks_return_their_codes_and_launch_nothing():

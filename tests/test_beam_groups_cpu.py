@@ -50,8 +50,8 @@ def test_blocks_are_in_the_table_and_bound_with_the_headers_argument_counts():
     assert nargs[NAMES[0]] == len(hip.SIGNATURES["cvc_beam_select_hist_parts"]) + 2
     assert nargs[NAMES[1]] == 11
     assert nargs[NAMES[2]] == len(hip.SIGNATURES["cvc_beam_backtrack"]) + 2
-    vocab = open(os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc", "vocab.hip")).read()
-    merge = vocab.split("void beam_merge_kernel(")[1].split("__global__")[0]
+    beam = open(os.path.join(ROOT, "cyclical-visual-captioning_amd", "csrc", "beam.hip")).read()
+    merge = beam.split("void beam_merge_kernel(")[1].split("__global__")[0]
     assert "atomic" not in merge
 
 

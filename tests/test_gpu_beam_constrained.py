@@ -1,4 +1,4 @@
-"""Constrained beam search on the GPU (pytest -m gpu): the selection block cvc_beam_select_hist_parts (csrc/vocab.hip, the HIST forms
+"""Constrained beam search on the GPU (pytest -m gpu): the selection block cvc_beam_select_hist_parts (csrc/beam.hip, the HIST forms
 of the beam row scan and merge) against the fp64 reference (tests/beam_constrain_ref.py) on every clip, the block with nothing banned
 against the plain beam blocks bit for bit, the engine with beam_history=True against the plain beam engine, its n-best against host
 backtracking, the constrained engine against the reference decoder on tile and ring, graph replay, and the model / CLI plumbing.

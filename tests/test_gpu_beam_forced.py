@@ -1,5 +1,5 @@
 """Lexically constrained beam search (forced words per clip) on the GPU (pytest -m gpu): the selection block
-cvc_beam_select_force_parts (csrc/vocab.hip, the FORCE form of the row scan and the BANKS form of the beam merge) against the fp64
+cvc_beam_select_force_parts (csrc/beam.hip, the FORCE form of the row scan and the BANKS form of the beam merge) against the fp64
 reference (tests/force_ref.py) on every clip, with no active entry against cvc_beam_select_hist_parts at beam bd, cvc_beam_rank_force
 against the host, the engine against the reference decoder on tile and ring, graph replay across batches with other forced words,
 force_n = 0 against the history engine, and the model / CLI plumbing.

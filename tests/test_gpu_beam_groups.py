@@ -1,5 +1,5 @@
 """Diverse (group) beam search and the length-normalised final ranking on the GPU (pytest -m gpu): the selection block
-cvc_beam_select_groups_parts (csrc/vocab.hip, the GROUPS form of the beam merge) against the fp64 reference
+cvc_beam_select_groups_parts (csrc/beam.hip, the GROUPS form of the beam merge) against the fp64 reference
 (tests/beam_groups_ref.py) on every clip, one group against cvc_beam_select_hist_parts bit for bit, cvc_beam_rank and
 cvc_beam_backtrack_from against the host, the engine against the reference decoder on tile and ring, lambda = 0 against the narrower
 beam engine, graph replay, and the model / CLI plumbing.

@@ -1,7 +1,7 @@
 """GPU tests (pytest -m gpu) of the decode engine's TILE path and of the beam bookkeeping, every entry point called by name through
 the C-ABI: cvc_tile_rows_alloc, cvc_tile_gemm, cvc_tile_linear_finish, cvc_tile_lstm_finish, cvc_tile_lstm_finish_embgate,
 cvc_tile_pack_rows, cvc_tile_pack_rows_any, cvc_tile_pack_cols, cvc_tile_reorder_pack (csrc/gemm_tile.hip), cvc_beam_select,
-cvc_beam_select_parts, cvc_beam_backtrack, cvc_gather_rows (csrc/vocab.hip).  Cases and host references: tests/tile_path_cases.py;
+cvc_beam_select_parts, cvc_beam_backtrack, cvc_gather_rows (csrc/beam.hip).  Cases and host references: tests/tile_path_cases.py;
 what the tables reach is checked without a GPU in tests/test_tile_path_cpu.py; observed values: profiles/tile_path_pins.md.
 
 Every output is pre-filled with NaN (fragment buffers with the bf16 NaN 0x7FC0, integer outputs with a sentinel): what the contract
@@ -413,7 +413,7 @@ EXACT_FAST = [n for n in T.BEAM_NAMES if not n.startswith(("random", "general", 
 def test_beam_float4_and_general_scans_agree_bit_for_bit(dev, lib, name):
     """The integer cases of the float4 scan against the general scan on the same values (the logits one float off alignment):
     parent, word, score and done bit for bit, on the live prefix.  Both scans give a thread the same elements and share all code
-    behind the loads (csrc/vocab.hip::beam_rowtop4_kernel), so their log-sum-exp agree to the bit.  Before they did -- a general scan
+    behind the loads (csrc/beam.hip::beam_rowtop4_kernel), so their log-sum-exp agree to the bit.  Before they did -- a general scan
     with its own element order and a block-wide max / sum -- 21 of these 31 cases failed here on the score (1 - 2 ulp, up to 9.5e-7;
     parent, word and done agreed): profiles/tile_path_pins.md."""
     L = lib.lib()

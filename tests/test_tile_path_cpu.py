@@ -11,7 +11,7 @@ import tile_path_cases as T
 
 # ------------------------------------------------------------------ constants and fragments
 def test_constants_are_the_sources():
-    """BEAM_MAX, ROW_CACHE, WG (csrc/vocab.hip), FRAG and the form switch (csrc/gemm_tile.hip): a changed constant fails here until
+    """BEAM_MAX, ROW_CACHE (csrc/beam.hip), WG (csrc/row_block.h), FRAG and the form switch (csrc/gemm_tile.hip): a changed constant fails here until
     the case tables follow"""
     assert T.source_constants() == dict(BEAM_MAX=T.BEAM_MAX, ROW_CACHE=T.ROW_CACHE, WG=T.WG, FRAG=T.FRAG, WIDE_KSTEPS=T.WIDE_KSTEPS)
     assert T.KSTEP == 3 * T.FRAG and T.WG * T.ROW_CACHE == 8192 and T.BEAM_MAX == 8

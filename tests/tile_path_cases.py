@@ -1,7 +1,7 @@
 """Shared pieces of tests/test_gpu_tile_path.py and tests/test_tile_path_cpu.py (not collected: no test_ prefix): the case tables
 and host references of the decode engine's TILE path (csrc/gemm_tile.hip: cvc_tile_gemm, cvc_tile_linear_finish,
 cvc_tile_lstm_finish(_embgate), cvc_tile_reorder_pack, cvc_tile_pack_rows(_any), cvc_tile_pack_cols) and of the beam bookkeeping
-(csrc/vocab.hip: cvc_beam_select(_parts), cvc_beam_backtrack, cvc_gather_rows).
+(csrc/beam.hip: cvc_beam_select(_parts), cvc_beam_backtrack, cvc_gather_rows).
 
 Everything here runs on the CPU.  The arithmetic that sends a size to a branch of the source (chunk height MH, K-slice length,
 XCD remap, form switch, NG / NP instantiation) is restated as small functions; tests/test_tile_path_cpu.py checks the tables
@@ -25,13 +25,14 @@ BEAM_MAX, ROW_CACHE, WG, WIDE_KSTEPS, FRAG = 8, 32, 256, 64, 512
 
 
 def source_constants():
-    """BEAM_MAX, ROW_CACHE, WG of csrc/vocab.hip; FRAG and the k steps per workgroup from which the default form of cvc_tile_gemm is
-    the wide one, of csrc/gemm_tile.hip"""
+    """BEAM_MAX, ROW_CACHE of csrc/beam.hip and the WG it takes from csrc/row_block.h; FRAG and the k steps per workgroup from which
+    the default form of cvc_tile_gemm is the wide one, of csrc/gemm_tile.hip"""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cyclical-visual-captioning_amd", "csrc")
-    voc, til = open(os.path.join(csrc, "vocab.hip")).read(), open(os.path.join(csrc, "gemm_tile.hip")).read()
+    beam, blk, til = (open(os.path.join(csrc, f)).read() for f in ("beam.hip", "row_block.h", "gemm_tile.hip"))
+    assert '#include "row_block.h"' in beam and not re.search(r"constexpr\s+int\s+WG\b", beam)      # no WG of its own
     ci = lambda src, name: int(re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)", src).group(1))
     wide = re.search(r"cvc_tile_loader_waves == 3 && a\.ksteps / ksplit >= (\d+)", til)
-    return dict(BEAM_MAX=ci(voc, "BEAM_MAX"), ROW_CACHE=ci(voc, "ROW_CACHE"), WG=ci(voc, "WG"), FRAG=ci(til, "FRAG"),
+    return dict(BEAM_MAX=ci(beam, "BEAM_MAX"), ROW_CACHE=ci(beam, "ROW_CACHE"), WG=ci(blk, "WG"), FRAG=ci(til, "FRAG"),
                 WIDE_KSTEPS=int(wide.group(1)))
 
 
