@@ -78,6 +78,9 @@ const Entry table[] = {
     CVC_B(cvc_lstm_seq_bwd),
     CVC_B(cvc_packed_lstm_bf16w_fwd),
     CVC_B(cvc_packed_linear_bf16w_fwd),
+    CVC_B(cvc_packed_linear_keys_fwd),
+    CVC_B(cvc_packed_lstm_embgate_keys_fwd),
+    CVC_B(cvc_keys_finalize),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

@@ -113,6 +113,13 @@ int run_packed_eg(cvc_decode_plan* p, hipStream_t st) {
     CVC_TRY(cvc_linear_fwd(&seg, 1, d.b_ih_att, d.b_hh_att, rows, 4 * R, d.gate_fc, 4 * R, st));
     const long long ws_att = (long long)(2 * R / 4) * 128, ws_lang = (long long)(3 * R / 4) * 128;     // block strides of the packs
     const bool split2 = cvc_gemm_packed_split(-1) == 2;
+    // fused tail (cvc_decode_desc.tail): no word-selection launch; keys of step t at tail_keys + t * 256, its UNK keys behind all T
+    // steps' candidate keys, both zero at the start of every decode
+    const bool fused = d.tail != 0;
+    const int nblk_v = (V + 31) / 32;
+    unsigned long long* key_unk0 = d.tail_keys + (size_t)d.T * 64 * 4;
+    if (fused)
+        CVC_TRY(reset(d.tail_keys, nullptr, (size_t)d.T * 64 * 5 * sizeof(unsigned long long), st));
     for (int t = 0; t < d.T; ++t) {
         const int rd = t & 1, wr = (t + 1) & 1;
         float *XA_r = d.xa[rd], *XA_w = d.xa[wr], *XL_r = d.xl[rd], *XL_w = d.xl[wr];
@@ -120,6 +127,11 @@ int run_packed_eg(cvc_decode_plan* p, hipStream_t st) {
         // attention cell contracts over one chunk only (its gates are the table row + the hoisted fc term) and the language cell
         // below stops before its h_lang columns
         const bool first = t == 0 && split2;
+        if (fused && t > 0)  // the word is decoded from the previous step's keys (step 0: BOS from words[0])
+            CVC_TRY(cvc_packed_lstm_embgate_keys_fwd((const float*)d.w_att, ws_att, XA_r, 2 * R, nullptr, nullptr, d.gate_fc, d.emb_gate,
+                                                     d.tail_keys + (size_t)(t - 1) * 64 * 4, key_unk0 + (size_t)(t - 1) * 64, d.unk_idx,
+                                                     d.ca[rd], rows, R, quad_off(XL_r, R), quad_off(XA_w, R), d.ca[wr], d.att_w_cached, st));
+        else
         CVC_TRY(cvc_packed_lstm_embgate_ex_fwd((const float*)d.w_att, ws_att, XA_r, first ? 32 : 2 * R, nullptr, nullptr, d.gate_fc,
                                                d.emb_gate, d.words + (size_t)t * rows, d.ca[rd], rows, R, quad_off(XL_r, R),
                                                quad_off(XA_w, R), d.ca[wr], d.att_w_cached, st));
@@ -139,10 +151,17 @@ int run_packed_eg(cvc_decode_plan* p, hipStream_t st) {
         else
         CVC_TRY(cvc_packed_lstm_fwd((const float*)d.w_lang, XL_r, 3 * R, d.b_ih_lang, d.b_hh_lang, nullptr, d.cl[rd], rows, R, XA_w,
                                     quad_off(XL_w, 2 * R), d.cl[wr], st));
+        if (fused) {
+            CVC_TRY(cvc_packed_linear_keys_fwd((const float*)d.w_o, XA_w, R, d.b_o, rows, V, d.unk_idx, d.tail_keys + (size_t)t * 64 * 4,
+                                               key_unk0 + (size_t)t * 64, d.tail_ms + (size_t)t * nblk_v * 64 * 2, st));
+            continue;
+        }
         CVC_TRY(cvc_packed_linear_fwd((const float*)d.w_o, XA_w, R, d.b_o, rows, V, 1, nullptr, V, d.top2_part, st));
-        CVC_TRY(cvc_top2_final(d.top2_part, (V + 31) / 32, rows, d.unk_idx, d.words + (size_t)(t + 1) * rows, 1,
+        CVC_TRY(cvc_top2_final(d.top2_part, nblk_v, rows, d.unk_idx, d.words + (size_t)(t + 1) * rows, 1,
                                d.logprob ? d.logprob + (size_t)t * rows : nullptr, nullptr, 0, nullptr, 0, st));
     }
+    if (fused)
+        CVC_TRY(cvc_keys_finalize(d.tail_keys, key_unk0, d.tail_ms, nblk_v, d.T, rows, d.unk_idx, d.words + rows, d.logprob, st));
     p->launches = n;
     return 0;
 }
@@ -295,6 +314,9 @@ int validate(const cvc_decode_desc& d) {
             (!d.xa0_init && !d.emb_gate))
             return CVC_E_BADARG;
         if (d.emb_gate != nullptr && d.gsk_nwg > 0) return CVC_E_BADARG;
+        if (d.tail != 0 && (d.tail != 1 || !d.emb_gate || d.lang_ksx || !d.tail_keys || ((uintptr_t)d.tail_keys & 15) || !d.tail_ms || d.unk_idx < 0 ||
+                            cvc_gemm_packed_split(-1) != 2))
+            return CVC_E_BADARG;
         if (d.lang_ksx && (!d.ksx_slab || !d.ksx_flags || d.R != 2048 || d.T < 2 || d.gsk_nwg > 0)) return CVC_E_BADARG;
         if (d.gsk_nwg < 0 || (d.gsk_nwg > 0 && ((d.R & 63) || !d.slab_att || !d.slab_lang || !d.slab_q || !d.slab_o))) return CVC_E_BADARG;
     } else if (d.path == 1) {

@@ -3,6 +3,7 @@
 #include "gemm_split.h"
 #include "gsk.h"
 #include "dropout_rng.h"
+#include "sel_keys.h"
 
 // ==========================================================================================
 // Packed path for the decode engine: both MFMA operands are stored fragment-native in HBM, so a
@@ -81,6 +82,12 @@ struct PackedArgs {
     DropSpec h3_drop;         // training form: h_rm3 receives nn.Dropout(h') with the counter-based mask of element m * R + j
     long long wstride;        // elements (floats; WB16: bf16) between consecutive 32-row blocks of wp (0: dense, nquad * 128)
     GskSegs early;            // SLAB form (cvc_packed_lstm_late_fwd): partial tiles of the K range a stream-K launch already covered
+    // KEYS forms (sel_keys.h).  Linear (cvc_packed_linear_keys_fwd): the epilogue posts this step's candidates to keys / key_unk and
+    // writes the block's (max, sum-exp) to ms_part [nblk][64][2]; sel_unk = UNK's index.  LSTM (cvc_packed_lstm_embgate_keys_fwd):
+    // the word of the embedding-gate gather is decoded from the PREVIOUS step's keys / key_unk instead of read from `word`
+    unsigned long long* keys;       // [KEY_SLOTS][64]
+    unsigned long long* key_unk;    // [64]
+    float* ms_part;
 };
 
 #ifdef CVC_TS
@@ -150,8 +157,11 @@ __device__ __forceinline__ SelState sel_merge(SelState s, float u1, int k1, floa
 // ninth partial.
 // WC: the LSTM gate weights keep the default cache policy instead of streaming non-temporally (experiment: cvc_packed_lstm_cached_weights)
 // WB16: bf16-stored weights (see the head of the file); differs in the K loop's fragment, load, multiply and issue pattern only
-template <int MT, bool LSTM, int DEPTH, bool SPLIT, int NW, bool GRU = false, int NB = 1, bool SLAB = false, bool WC = false, bool WB16 = false>
+// KEYS: the fused greedy tail (PackedArgs::keys): linear form = candidates posted from the epilogue, LSTM form = word decoded from them
+template <int MT, bool LSTM, int DEPTH, bool SPLIT, int NW, bool GRU = false, int NB = 1, bool SLAB = false, bool WC = false, bool WB16 = false,
+          bool KEYS = false>
 __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs a) {
+    static_assert(!KEYS || (SPLIT && NW == 8 && !GRU && NB == 1 && !SLAB && !WB16), "keys forms: 8-wave split-product form, fp32 weights");
     static_assert(!WB16 || (SPLIT && NW == 8 && !GRU && NB == 1 && !SLAB), "bf16-stored weights: 8-wave split-product form only");
     using Frag = std::conditional_t<WB16, BFrag<MT>, PFrag<MT>>;
     using WT = std::conditional_t<WB16, uint16_t, float>;      // element type of the weight pack
@@ -259,7 +269,21 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
     if constexpr (LSTM && !GRU) {
         if (a.emb_gate != nullptr && tid < NB * 2 * 64) {
             const int em0 = tid & 63;
-            const long long eword = a.word[em0 < a.M ? em0 : a.M - 1];
+            long long eword;
+            if constexpr (KEYS) {
+                // the candidate keys + UNK's key of this row, requested together; their integer max is the previous step's word
+                const int er = em0 < a.M ? em0 : a.M - 1;
+                unsigned long long kq[KEY_SLOTS];
+#pragma unroll
+                for (int s = 0; s < KEY_SLOTS; ++s) kq[s] = a.keys[s * KEY_ROWS + er];
+                const unsigned long long ku = a.key_unk[er];
+                unsigned long long kb = 0ull;
+#pragma unroll
+                for (int s = 0; s < KEY_SLOTS; ++s) kb = kq[s] > kb ? kq[s] : kb;
+                eword = sel_key_word(kb, ku, a.sel_unk);
+            } else {
+                eword = a.word[em0 < a.M ? em0 : a.M - 1];
+            }
             // table in checkpoint order [V][4R]: gate g of hidden unit u at g * R + u
             const float* trow = a.emb_gate + (size_t)eword * 4 * a.R + (size_t)((int)blockIdx.x * NB + (tid >> 7)) * 8 + ((tid >> 6) & 1) * 4;
 #pragma unroll
@@ -461,7 +485,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
 #pragma unroll
     for (int c = 0; c < ECPW; ++c) {
         const int n = (int)blockIdx.x * 32 + wave * ECPW + c;
-        ebias[c] = (!LSTM && a.top2_part != nullptr && a.bias != nullptr) ? a.bias[n < a.Nout ? n : a.Nout - 1] : 0.f;
+        ebias[c] = (!LSTM && (KEYS || a.top2_part != nullptr) && a.bias != nullptr) ? a.bias[n < a.Nout ? n : a.Nout - 1] : 0.f;
     }
 
     // ---- ordered cross-wave reduction (same scheme as combine_and_store)
@@ -574,7 +598,52 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_packed_kernel(PackedArgs 
                 y[(size_t)m * a.ldy + n] = v;
             }
         }
-        if (a.top2_part != nullptr) {
+        if constexpr (KEYS) {
+            // ---- word choice without a selection launch (sel_keys.h): every wave scans its columns for the best non-UNK candidate
+            // as ONE integer key, UNK's own key, and the running (max, sum-exp) exactly as the record form below keeps them; the lane
+            // that owns a batch row merges the 8 waves and posts the block's best with one 64-bit integer max at device scope -- no
+            // return value, order-independent, so the word is deterministic whatever order the workgroups arrive in
+            float* scratch = red + NW * 32 * LDM;
+            unsigned long long kb = 0ull, ku = 0ull;
+            float mx = -__builtin_inff(), se = 0.f;
+            const int m = lane < MT * 32 ? lane : MT * 32 - 1;
+            constexpr int CPW = 32 / NW;
+#pragma unroll
+            for (int c = 0; c < CPW; ++c) {
+                const int nl = wave * CPW + c, n = n0 + nl;
+                if (n >= a.Nout) break;
+                const float v = sum_partials<NW>(red, nl, LDM, m) + ebias[c];
+                const unsigned long long k = sel_key(v, n);
+                if (n == a.sel_unk) ku = k;
+                else kb = k > kb ? k : kb;
+                const float nm = fmaxf(mx, v);
+                se = se * __expf(mx - nm) + __expf(v - nm);
+                mx = nm;
+            }
+            float* r4 = scratch + ((size_t)wave * 64 + lane) * 6;
+            r4[0] = __uint_as_float((uint32_t)kb); r4[1] = __uint_as_float((uint32_t)(kb >> 32));
+            r4[2] = __uint_as_float((uint32_t)ku); r4[3] = __uint_as_float((uint32_t)(ku >> 32));
+            r4[4] = mx; r4[5] = se;
+            __syncthreads();
+            if (wave == 0 && lane < M) {
+                for (int w = 1; w < NW; ++w) {
+                    const float* q4 = scratch + ((size_t)w * 64 + lane) * 6;
+                    const unsigned long long k1 = ((unsigned long long)__float_as_uint(q4[1]) << 32) | __float_as_uint(q4[0]);
+                    const unsigned long long k2 = ((unsigned long long)__float_as_uint(q4[3]) << 32) | __float_as_uint(q4[2]);
+                    kb = k1 > kb ? k1 : kb;
+                    ku = k2 > ku ? k2 : ku;
+                    const float nm = fmaxf(mx, q4[4]);
+                    se = (nm == -__builtin_inff()) ? 0.f : se * __expf(mx - nm) + q4[5] * __expf(q4[4] - nm);
+                    mx = nm;
+                }
+                float* ms = a.ms_part + ((size_t)blockIdx.x * 64 + lane) * 2;
+                ms[0] = mx; ms[1] = se;
+                if (kb != 0ull)
+                    (void)__hip_atomic_fetch_max(a.keys + (blockIdx.x & (KEY_SLOTS - 1)) * KEY_ROWS + lane, kb, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+                if (ku != 0ull) a.key_unk[lane] = ku;                  // (one block holds UNK's column: a plain store)
+            }
+        } else if (a.top2_part != nullptr) {
             float* scratch = red + NW * 32 * LDM;
             float v1 = -__builtin_inff(), v2 = -__builtin_inff(), mx = -__builtin_inff(), se = 0.f;
             int i1 = 0x7fffffff, i2 = 0x7fffffff;
@@ -1080,6 +1149,51 @@ extern "C" int cvc_packed_linear_fwd(const float* wp, const float* xq, int K, co
     a.wp = wp; a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = Nout; a.R = 0;
     a.bias = bias; a.y = y; a.ldy = ldy; a.ksplit = ksplit; a.split_stride = (long long)M * ldy; a.top2_part = top2_part;
     return launch_packed<false>(a, (Nout + 31) / 32, (hipStream_t)stream);
+}
+
+// ---- the fused greedy tail (DecodeEngine(tail="fused"), include/cvc_hip_blocks.h): the 8-wave split-product form only
+extern "C" int cvc_packed_linear_keys_fwd(const float* wp, const float* xq, int K, const float* bias, int M, int Nout, int unk_idx,
+                                          unsigned long long* keys, unsigned long long* key_unk, float* ms_part, cvc_stream_t stream) {
+    if (!wp || !xq || (K & 31) || K < 32 || Nout < 1 || M < 1 || M > 64 || !keys || !key_unk || !ms_part || unk_idx < 0) return CVC_E_BADARG;
+    if (((uintptr_t)keys & 15) || ((uintptr_t)key_unk & 7)) return CVC_E_BADARG;
+    if (cvc_gemm_split_mode != 2) return CVC_E_BADARG;
+    PackedArgs a{};
+    a.wp = wp; a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = Nout; a.R = 0; a.wstride = (long long)a.nquad * 128;
+    a.bias = bias; a.ksplit = 1; a.sel_unk = unk_idx; a.keys = keys; a.key_unk = key_unk; a.ms_part = ms_part;
+    const dim3 grid((Nout + 31) / 32);
+    hipStream_t st = (hipStream_t)stream;
+    if (M <= 32) hipLaunchKernelGGL((skinny_gemm_packed_kernel<1, false, CVC_PACKED_DEPTH8, true, 8, false, 1, false, false, false, true>), grid, dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((skinny_gemm_packed_kernel<2, false, CVC_PACKED_DEPTH8, true, 8, false, 1, false, false, false, true>), grid, dim3(512), 0, st, a);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_packed_lstm_embgate_keys_fwd(const float* wp, long long w_blk_stride, const float* xq, int K, const float* b_ih,
+                                                const float* b_hh, const float* gate_bias, const float* emb_gate,
+                                                const unsigned long long* keys, const unsigned long long* key_unk, int unk_idx,
+                                                const float* c_prev_q, int M, int R, float* h_dst1_q, float* h_dst2_q, float* c_out_q,
+                                                int w_cached, cvc_stream_t stream) {
+    if (!wp || !xq || !c_prev_q || !c_out_q || !emb_gate || !keys || !key_unk || (K & 31) || K < 32 || R < 8 || (R & 7) || M < 1 || M > 64 ||
+        unk_idx < 0)
+        return CVC_E_BADARG;
+    if (w_blk_stride != 0 && (w_blk_stride < (long long)(K / 4) * 128 || (w_blk_stride & 3))) return CVC_E_BADARG;
+    if (((uintptr_t)keys & 15) || ((uintptr_t)key_unk & 7)) return CVC_E_BADARG;
+    if (cvc_gemm_split_mode != 2) return CVC_E_BADARG;
+    PackedArgs a{};
+    a.wp = wp; a.xq = xq; a.nquad = K / 4; a.M = M; a.Nout = 4 * R; a.R = R; a.wstride = w_blk_stride ? w_blk_stride : (long long)a.nquad * 128;
+    a.bias = b_ih; a.bias2 = b_hh; a.gate_bias = gate_bias; a.c_prev_q = c_prev_q; a.c_out_q = c_out_q;
+    a.h_dst1_q = h_dst1_q; a.h_dst2_q = h_dst2_q; a.ksplit = 1; a.emb_gate = emb_gate; a.w_cached = w_cached ? 1 : 0;
+    a.keys = const_cast<unsigned long long*>(keys); a.key_unk = const_cast<unsigned long long*>(key_unk); a.sel_unk = unk_idx;
+    const dim3 grid(R / 8);
+    hipStream_t st = (hipStream_t)stream;
+    // (the same choice of forms as launch_packed<true> makes for the word form in split mode 2)
+    if (a.w_cached) {
+        if (M > 32) hipLaunchKernelGGL((skinny_gemm_packed_kernel<2, true, CVC_PACKED_DEPTH8, true, 8, false, 1, false, true, false, true>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((skinny_gemm_packed_kernel<1, true, CVC_PACKED_DEPTH8, true, 8, false, 1, false, true, false, true>), grid, dim3(512), 0, st, a);
+    } else {
+        if (M > 32) hipLaunchKernelGGL((skinny_gemm_packed_kernel<2, true, CVC_PACKED_DEPTH8, true, 8, false, 1, false, false, false, true>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((skinny_gemm_packed_kernel<1, true, CVC_PACKED_DEPTH8, true, 8, false, 1, false, false, false, true>), grid, dim3(512), 0, st, a);
+    }
+    return cvc_launch_status();
 }
 
 extern "C" int cvc_packed_linear_bf16w_fwd(const uint16_t* wp, const float* xq, int K, const float* bias, int M, int Nout,

@@ -6,6 +6,7 @@
 // point is to keep it on the device and inside the captured decode graph.
 // (the beam blocks: csrc/beam.hip; the training step's pointwise backward and small reductions: csrc/lstm_pointwise_bwd.hip)
 #include "row_block.h"
+#include "sel_keys.h"
 #include "gsk.h"
 #include "dropout_rng.h"
 #include <math.h>
@@ -235,6 +236,35 @@ __global__ __launch_bounds__(WG) void top2_final_kernel(const float* part, int n
             v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
             if (emb_ld > 0) st4(emb_out + (size_t)row * emb_ld + e, v);
             else st4(emb_out + ((size_t)(e >> 2) * 64 + row) * 4, v);       // emb_ld == 0: quad layout [E/4][64][4]
+        }
+    }
+}
+
+// The fused greedy tail's only selection work outside the critical path (sel_keys.h): one workgroup per (step, row) decodes the
+// word from the step's keys and sums the step's per-block (max, sum-exp) records for the log-prob exactly as top2_final_kernel sums
+// its records (same strides, same reductions: the same bits); one launch per decode.
+__global__ __launch_bounds__(WG) void keys_finalize_kernel(const unsigned long long* keys, const unsigned long long* key_unk, const float* ms_part,
+                                                           int nblocks, int T, int rows, int unk, int64_t* words, float* logprob) {
+    __shared__ float red[4];
+    const int item = blockIdx.x;
+    const int t = item / rows, row = item - t * rows;
+    const float* ms = ms_part + ((size_t)t * nblocks * 64 + row) * 2;
+    float mx = -INFINITY;
+    for (int b = threadIdx.x; b < nblocks; b += WG) mx = fmaxf(mx, ms[(size_t)b * 128]);
+    mx = block_max(mx, red);
+    float se = 0.f;
+    for (int b = threadIdx.x; b < nblocks; b += WG) se += ms[(size_t)b * 128 + 1] * expf(ms[(size_t)b * 128] - mx);
+    se = block_sum(se, red);
+    if (threadIdx.x == 0) {
+        const unsigned long long* kp = keys + (size_t)t * KEY_SLOTS * KEY_ROWS + row;
+        unsigned long long kb = 0ull;
+#pragma unroll
+        for (int s = 0; s < KEY_SLOTS; ++s) kb = kp[s * KEY_ROWS] > kb ? kp[s * KEY_ROWS] : kb;
+        const unsigned long long ku = key_unk[(size_t)t * KEY_ROWS + row];
+        words[item] = sel_key_word(kb, ku, unk);
+        if (logprob != nullptr) {
+            const float v = kb != 0ull ? sel_key_value(kb) : (ku != 0ull ? sel_key_value(ku) : -INFINITY);
+            logprob[item] = v - (mx + logf(se));
         }
     }
 }
@@ -545,6 +575,14 @@ extern "C" int cvc_top2_final(const float* part, int nblocks, int M, int unk_idx
     if (emb_out != nullptr && (!table || E < 4 || (E & 3) || (emb_ld & 3) || (emb_ld != 0 && emb_ld < E))) return CVC_E_BADARG;
     hipLaunchKernelGGL(top2_final_kernel, dim3(M), dim3(WG), 0, (hipStream_t)stream, part, nblocks, unk_idx, word, word_stride,
                        logprob, table, E, emb_out, emb_ld);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_keys_finalize(const unsigned long long* keys, const unsigned long long* key_unk, const float* ms_part, int nblocks, int T,
+                                 int rows, int unk_idx, int64_t* words, float* logprob, cvc_stream_t stream) {
+    if (!keys || !key_unk || !ms_part || !words || nblocks < 1 || T < 1 || rows < 1 || rows > KEY_ROWS || unk_idx < 0) return CVC_E_BADARG;
+    hipLaunchKernelGGL(keys_finalize_kernel, dim3(T * rows), dim3(WG), 0, (hipStream_t)stream, keys, key_unk, ms_part, nblocks, T, rows,
+                       unk_idx, words, logprob);
     return cvc_launch_status();
 }
 

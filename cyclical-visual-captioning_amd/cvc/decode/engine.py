@@ -67,7 +67,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
                  min_len: int = 0, ban_words=None, bad_endings=None, beam_groups: int = 1, diversity: float = 0.0,
-                 length_penalty: float = 0.0, force_n: int = 0, beam_history: bool = False):
+                 length_penalty: float = 0.0, force_n: int = 0, tail: Optional[str] = None, beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -148,7 +148,13 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         [B, beam] int32) and cvc_beam_backtrack_from(order[:, 0]), both inside a captured graph: run() returns the best-normed
         hypothesis among those that met the most forced words, hypotheses(ranked=True) returns (seq, score, norm, nmet) in that
         order, and self.nmet [T, rows] int32 holds the count of every row entering step t.  Needs beam_history=True, beam > 1 and
-        beam % (force_n + 1) == 0; refused with beam_groups > 1."""
+        beam % (force_n + 1) == 0; refused with beam_groups > 1.
+        tail: plain greedy decode on the packed embedding-gate schedule (beam = 1, <= 64 rows, fp32 weights, no sampling / forced /
+        constrained mode, no gsk / gate_ksplit / lang_ksx, split-product arithmetic) -- "fused": the vocabulary head posts every
+        block's best candidate as a 64-bit key (an integer max over the workgroups: csrc/sel_keys.h), the next step's attention cell
+        decodes its word from the keys, and one launch after the loop writes words and log-probs: six launches per step instead of
+        seven.  "launch": cvc_top2_final after every head, as every other mode runs.  None = TAIL_DEFAULT where the fused tail
+        applies, "launch" elsewhere; an explicit "fused" where it does not apply is refused."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -414,6 +420,23 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self._alloc_packed()
         elif self.tile:
             self._alloc_tile()
+        fused_ok = (self.packed and self.embgate and not self.given and not self.bf16w and not self.gsk and not self.gate_ksplit and
+                    not self.lang_ksx and self.beam == 1 and self.unk >= 0 and hip.gemm_packed_split(-1) == 2)
+        if tail is None:
+            tail = TAIL_DEFAULT if fused_ok else "launch"
+        if tail not in TAILS:
+            raise RuntimeError(f"DecodeEngine: tail must be one of {TAILS} (or None), got {tail!r}")
+        if tail == "fused" and not fused_ok:
+            raise RuntimeError('DecodeEngine: tail="fused" covers plain greedy decode on the packed embedding-gate schedule only (beam = 1, '
+                               "<= 64 rows, fp32 weights, no sampling / forced / constrained mode, no gsk / gate_ksplit / lang_ksx, "
+                               "cvc_gemm_packed_split(2))")
+        self.tail = tail
+        self.fused_tail = tail == "fused"
+        if self.fused_tail:
+            # [T][4][64] candidate keys, then [T][64] UNK keys (64-bit words; cleared at the start of every decode), and the
+            # per-step (max, sum-exp) records of the head's blocks
+            self.tail_keys = torch.zeros(self.T * 64 * 5, dtype=torch.int64, device=dev)
+            self.tail_ms = z(self.T, (V + 31) // 32, 64, 2)
         self._launches = self._build_launches()
         if driver and not self.given and not self.bf16w and not self.beam_hist and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
@@ -453,6 +476,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 d.att_w_cached = int(self.att_w_cached)
             if self.lang_ksx:
                 d.lang_ksx, d.ksx_slab, d.ksx_flags = 1, ptr(self.ksx_slab), ptr(self.ksx_flags)
+            if self.fused_tail:
+                d.tail, d.tail_keys, d.tail_ms = 1, ptr(self.tail_keys), ptr(self.tail_ms)
             if self.gsk:
                 d.gsk_nwg = self.gsk_nwg
                 d.slab_att, d.slab_lang, d.slab_q, d.slab_o = (ptr(self.slab_att), ptr(self.slab_lang), ptr(self.slab_q),
@@ -505,6 +530,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.cA[0].zero_()
             self.cL[0].zero_()
             self.words[0].zero_()
+            if self.fused_tail:
+                self.tail_keys.zero_()
             return
         for bufs in (self.h_att, self.c_att, self.h_lang, self.c_lang):
             bufs[0].zero_()
@@ -743,7 +770,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
         key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist, self.grouped, self.ranked, self.forcing)
+               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode

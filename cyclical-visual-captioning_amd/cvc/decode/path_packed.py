@@ -1,6 +1,7 @@
 """Greedy decode with at most 64 rows: both operands of every GEMM MFMA-fragment-native (csrc/gemm_packed.hip), 7 launches per
 step; buffers + the eager launch list of the default schedule and of the embedding-gate schedule (the C driver csrc/decode_driver.hip
-enqueues the same list from a bound descriptor).  Mixin of cvc.decode.engine.DecodeEngine."""
+enqueues the same list from a bound descriptor); with the fused tail (tail="fused": plain greedy on the embedding-gate schedule) 6
+launches per step and one finishing launch per decode.  Mixin of cvc.decode.engine.DecodeEngine."""
 from __future__ import annotations
 
 import ctypes as C
@@ -151,16 +152,26 @@ class PackedPath:
         else:
             att_fn, linear_fn = L.cvc_packed_lstm_embgate_ex_fwd, L.cvc_packed_linear_fwd
             w_att, att_stride, embgate, w_h, w_o = W.p_att2, (2 * R // 4) * 128, W.t_embgate, W.p_h, W.p_o
+        # fused tail (tail="fused"): keys of step t at key_at(t), its UNK keys at unk_at(t), behind all T steps' candidate keys
+        fused = self.fused_tail
+        if fused:
+            key_at = lambda t: self.tail_keys.data_ptr() + t * 64 * 4 * 8
+            unk_at = lambda t: self.tail_keys.data_ptr() + (self.T * 64 * 4 + t * 64) * 8
         for t in range(self.T):
             rd, wr = t & 1, (t + 1) & 1
             XA_r, XA_w, XL_r, XL_w = self.XA[rd], self.XA[wr], self.XL[rd], self.XL[wr]
             # step 0 multiplies the all-zero initial state (an exact zero times a finite weight adds nothing): one chunk of the
             # attention cell's K, the language cell without its h_lang columns (see run_packed_eg)
             first = t == 0 and (self.bf16w or hip.gemm_packed_split(-1) == 2)
-            out.append(("att_lstm", att_fn, (ptr(w_att), att_stride, ptr(XA_r), 32 if first else 2 * R, None, None,
-                                             ptr(self.gate_fc), ptr(embgate), ptr(self.words[t]), ptr(self.cA[rd]),
-                                             rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
-                                             1 if self.att_w_cached else 0)))
+            if fused and t > 0:       # the word is decoded from the previous step's keys (step 0: BOS from words[0])
+                out.append(("att_lstm", L.cvc_packed_lstm_embgate_keys_fwd, (
+                    ptr(w_att), att_stride, ptr(XA_r), 2 * R, None, None, ptr(self.gate_fc), ptr(embgate), key_at(t - 1), unk_at(t - 1),
+                    self.unk, ptr(self.cA[rd]), rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]), 1 if self.att_w_cached else 0)))
+            else:
+                out.append(("att_lstm", att_fn, (ptr(w_att), att_stride, ptr(XA_r), 32 if first else 2 * R, None, None,
+                                                 ptr(self.gate_fc), ptr(embgate), ptr(self.words[t]), ptr(self.cA[rd]),
+                                                 rows, R, qoff(XL_r, R), qoff(XA_w, R), ptr(self.cA[wr]),
+                                                 1 if self.att_w_cached else 0)))
             out.append(("h2attn", linear_fn, (ptr(w_h), qoff(XL_r, R), R, None, rows, A, self.QSPLIT, ptr(self.q_parts), A, None)))
             sets = (hip.AttnSet * 2)()
             sets[0] = self._region_set(t)
@@ -190,9 +201,15 @@ class PackedPath:
                 # row-major logits, then the sampling / forced block (the attention cell of step t + 1 reads the word from words[t + 1])
                 out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, ptr(self.logits), V, None)))
                 out.append(self._word_select_sampled(t, ptr(self.logits), 1, 0, None))
+            elif fused:             # no word_select launch: the head posts its candidates, the next attention cell reads them
+                out.append(("logits", L.cvc_packed_linear_keys_fwd, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, self.unk, key_at(t),
+                                                                     unk_at(t), ptr(self.tail_ms[t]))))
             else:
                 out.append(("logits", linear_fn, (ptr(w_o), ptr(XA_w), R, ptr(W.b_o), rows, V, 1, None, V, ptr(self.top2_part))))
                 out.append(("word_select", L.cvc_top2_final, (ptr(self.top2_part), nblk_v, rows, self.unk, ptr(self.words[t + 1]), 1,
                                                               ptr(self.logprob[t]), None, 0, None, 0)))
             self._keep.append(sets)
+        if fused:                   # words[1 .. T] and the log-probs of all steps: one launch per decode
+            out.append(("tail_finalize", L.cvc_keys_finalize, (key_at(0), unk_at(0), ptr(self.tail_ms), nblk_v, self.T, rows, self.unk,
+                                                               ptr(self.words[1]), ptr(self.logprob))))
         return out

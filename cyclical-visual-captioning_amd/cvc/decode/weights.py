@@ -239,6 +239,13 @@ CACHE_BUDGET = int(os.environ.get("CVC_CACHE_BUDGET_MB", "208")) << 20
 # steps/s without it, 326.1 / 323.5 k with it on one box: the 16.8 MB of partial tiles pass through the L2 / Infinity Cache that
 # holds the attention cell's weights, whose launch slows down by 1.5 us).  CVC_LANG_KSX=1 or lang_ksx=True switches it on.
 LANG_KSX_DEFAULT = os.environ.get("CVC_LANG_KSX", "0") == "1"
+# Plain greedy decode on the packed embedding-gate schedule: "fused" = the vocabulary head posts its candidates as 64-bit keys and the
+# next attention cell decodes its word from them (no word-selection launch; csrc/sel_keys.h), "launch" = cvc_top2_final after every
+# head.  DecodeEngine(tail=None) takes this where the fused tail applies; CVC_DECODE_TAIL overrides it (A/B).  DESIGN section 4.
+TAILS = ("launch", "fused")
+TAIL_DEFAULT = os.environ.get("CVC_DECODE_TAIL", "fused")
+if TAIL_DEFAULT not in TAILS:          # (an A/B override that names no tail changes nothing)
+    TAIL_DEFAULT = "fused"
 # is the language cell's gate matrix a candidate of the cache plan where the caller offers it (bf16 mode: 101 MB at cfg2)?  (A/B: CVC_LANG_W_CACHED=0)
 CACHE_LANG_GATE_WEIGHTS = os.environ.get("CVC_LANG_W_CACHED", "1") != "0"
 CACHE_GATE_WEIGHTS = os.environ.get("CVC_ATT_W_CACHED", "1") != "0"       # False: gate weights always stream (A/B)

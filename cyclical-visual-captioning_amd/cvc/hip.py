@@ -79,7 +79,8 @@ class DecodeDesc(C.Structure):
         [(n, C.c_void_p) for n in ("h_att", "c_att", "h_lang", "c_lang", "c_att_prev", "c_lang_prev", "zero_state")] +
         [("beam_ws", C.c_void_p)] +
         [("gsk_nwg", C.c_int)] + [(n, C.c_void_p) for n in ("slab_att", "slab_lang", "slab_q", "slab_o", "emb_gate", "sel_counter")] +
-        [("att_w_cached", C.c_int), ("lang_ksx", C.c_int), ("ksx_slab", C.c_void_p), ("ksx_flags", C.c_void_p)])
+        [("att_w_cached", C.c_int), ("lang_ksx", C.c_int), ("ksx_slab", C.c_void_p), ("ksx_flags", C.c_void_p)] +
+        [("tail", C.c_int), ("tail_keys", C.c_void_p), ("tail_ms", C.c_void_p)])
 
 class GradSrc(C.Structure):
     """cvc_grad_src: a gradient given as the sum of K-slice planes"""
@@ -258,6 +259,10 @@ SIGNATURES = {
     # packed GEMMs with bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip; building blocks)
     "cvc_packed_lstm_bf16w_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P],
     "cvc_packed_linear_bf16w_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P],
+    # greedy word choice without a selection launch (csrc/sel_keys.h; building blocks)
+    "cvc_packed_linear_keys_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    "cvc_packed_lstm_embgate_keys_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P],
+    "cvc_keys_finalize": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -300,7 +305,8 @@ BLOCKS = {
     "cvc_tile_gemm_loaders", "cvc_gru_persistent_waves8", "cvc_relu_dropout_fwd", "cvc_relu_dropout_bwd", "cvc_bn_workspace",
     "cvc_bn_relu_train_fwd", "cvc_bn_relu_train_bwd", "cvc_class_softmax_bwd", "cvc_layernorm_cat_bwd", "cvc_stable_order", "cvc_col_sum", "cvc_col_sum_ws", "cvc_attn_weighted_rows",
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
-    "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd"}
+    "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
+    "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",

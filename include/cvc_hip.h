@@ -615,6 +615,14 @@ typedef struct cvc_decode_desc {
     int lang_ksx;
     float* ksx_slab;
     unsigned* ksx_flags;
+    /* packed path, embedding-gate schedule, split mode 2, no lang_ksx: tail = 1 drops the word-selection launch of every step
+     * (cvc_hip_blocks.h, "greedy word choice without a selection launch"): the vocabulary head posts its candidates as 64-bit keys,
+     * the next step's attention cell decodes its word from them, and ONE launch after the loop writes words[1..T] and logprob.
+     * tail_keys: T * 64 * 5 64-bit words, 16-byte aligned ([T][4][64] candidate keys, then [T][64] UNK keys; cleared by the
+     * driver at the start of every decode); tail_ms: T * ceil(V/32) * 64 * 2 floats.  tail = 0: cvc_top2_final after every head. */
+    int tail;
+    unsigned long long* tail_keys;
+    float* tail_ms;
 } cvc_decode_desc;
 typedef struct cvc_decode_plan cvc_decode_plan;
 CVC_API int cvc_decode_plan_create(const cvc_decode_desc* desc, cvc_decode_plan** plan);   /* validates, copies the descriptor       */

@@ -447,6 +447,32 @@ int cvc_packed_lstm_bf16w_fwd(const uint16_t* wp, long long w_blk_stride, const 
 int cvc_packed_linear_bf16w_fwd(const uint16_t* wp, const float* xq, int K, const float* bias, int M, int Nout, int ksplit,
                                 float* y, int ldy, float* top2_part, cvc_stream_t stream);
 
+/* ---- greedy word choice without a selection launch (csrc/sel_keys.h; DecodeEngine(tail="fused"), cvc_decode_desc.tail_keys).
+ * A candidate (logit v, word n) is one 64-bit key, (ordered(v) << 32) | (0x7fffffff - n): its unsigned order is "value
+ * descending, index ascending", -0 is encoded as +0, a NaN or -inf is never a candidate (as in the records of cvc_packed_linear_fwd), 0 = none.  Buffers of one step: keys
+ * [4][64] (slot-major, 16-byte aligned) and key_unk [64] 64-bit words, both ZERO before the step's head runs; ms_part [ceil(V/32)][64][2] floats.
+ *   cvc_packed_linear_keys_fwd: the vocabulary head y = x W^T + bias of cvc_packed_linear_fwd (same sums, bit for bit) whose
+ *     epilogue posts, per 32-row block b and batch row m < M, the best candidate among the block's columns other than unk_idx to
+ *     keys[b % 4][m] with one 64-bit integer max at device scope (no return value), unk_idx's own key to key_unk[m], and writes
+ *     {max, sum exp(y - max)} over the block's columns to ms_part[b][m] -- the (mx, se) of cvc_packed_linear_fwd's records.
+ *     No y, no records.
+ *   cvc_packed_lstm_embgate_keys_fwd: cvc_packed_lstm_embgate_ex_fwd whose word of row m is decoded from keys / key_unk of the
+ *     PREVIOUS step: k = max over keys[0..3][m]; k != 0: word 0x7fffffff - low32(k) (the best word other than UNK:
+ *     captioner.py:415-422, best or second best if the best is UNK); else key_unk[m] != 0: unk_idx; else 0.
+ *   cvc_keys_finalize: words [T][rows] int64 by that rule and logprob [T][rows] (nullable) = the chosen word's logit - (mx +
+ *     log se) over the step's ms_part records, for all T steps in one launch; keys [T][4][64], key_unk [T][64], ms_part
+ *     [T][nblocks][64][2].
+ * Split mode 2 (cvc_gemm_packed_split) only, K % 32 == 0, 1 <= M (rows) <= 64, unk_idx >= 0: else CVC_E_BADARG, before any launch. */
+int cvc_packed_linear_keys_fwd(const float* wp, const float* xq, int K, const float* bias, int M, int Nout, int unk_idx,
+                               unsigned long long* keys, unsigned long long* key_unk, float* ms_part, cvc_stream_t stream);
+int cvc_packed_lstm_embgate_keys_fwd(const float* wp, long long w_blk_stride, const float* xq, int K, const float* b_ih,
+                                     const float* b_hh, const float* gate_bias, const float* emb_gate,
+                                     const unsigned long long* keys, const unsigned long long* key_unk, int unk_idx,
+                                     const float* c_prev_q, int M, int R, float* h_dst1_q, float* h_dst2_q, float* c_out_q,
+                                     int w_cached, cvc_stream_t stream);
+int cvc_keys_finalize(const unsigned long long* keys, const unsigned long long* key_unk, const float* ms_part, int nblocks, int T,
+                      int rows, int unk_idx, int64_t* words, float* logprob, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,7 +141,10 @@ def roles_for(mode, beam, T, B=64):
         "logits": (r"skinny_gemm_packed_kernelILi\dELb0E", 2, {1}),
         "attn_scores": (r"attn_scores_kernel", 1, {0}),
         "attn_wsum": (r"attn_wsum_kernel", 1, {0}),
+        # (plain greedy with the fused tail, DecodeEngine's default: no word_select launch, one tail_finalize per decode; the att_lstm /
+        # logits patterns match the keys forms of the same kernel template too.  CVC_DECODE_TAIL=launch collects the select launch.)
         "word_select": (r"top2_final_kernel", 1, {0}),
+        "tail_finalize": (r"keys_finalize_kernel", 1, {0}),
     }
 
 
@@ -222,6 +225,8 @@ def main():
         # a role is one kernel launch or, as a list, several launches whose bytes add up (an entry point made of several kernels)
         parts = [part_bytes(role, fetch, write, pat, period, positions, a.skip) for pat, period, positions in (spec if isinstance(spec, list) else [spec])]
         if any(p is None for p in parts):
+            print(f"collect_traffic: role {role}: no launches of its kernel in both traces, left out (a role of a schedule that did not run)",
+                  file=sys.stderr)
             continue
         fk, wk = sum(p[2] for p in parts), sum(p[3] for p in parts)
         sym = " + ".join(p[0] for p in parts)
