@@ -81,6 +81,8 @@ const Entry table[] = {
     CVC_B(cvc_packed_linear_keys_fwd),
     CVC_B(cvc_packed_lstm_embgate_keys_fwd),
     CVC_B(cvc_keys_finalize),
+    CVC_B(cvc_cider_d),
+    CVC_B(cvc_scst_weights),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

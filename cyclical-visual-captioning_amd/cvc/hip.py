@@ -263,6 +263,9 @@ SIGNATURES = {
     "cvc_packed_linear_keys_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
     "cvc_packed_lstm_embgate_keys_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P],
     "cvc_keys_finalize": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    # self-critical training: CIDEr-D reward and per-token loss weights (csrc/cider.hip; building blocks)
+    "cvc_cider_d": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P],
+    "cvc_scst_weights": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -306,7 +309,8 @@ BLOCKS = {
     "cvc_bn_relu_train_fwd", "cvc_bn_relu_train_bwd", "cvc_class_softmax_bwd", "cvc_layernorm_cat_bwd", "cvc_stable_order", "cvc_col_sum", "cvc_col_sum_ws", "cvc_attn_weighted_rows",
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
-    "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize"}
+    "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
+    "cvc_cider_d", "cvc_scst_weights"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1108,6 +1112,39 @@ def attn_nll_bwd(x0, x1, tg, ws, g0, g1, want0: bool, want1: bool):
                                   0 if x1 is None else x1.stride(0), 0 if x1 is None else x1.stride(1), _dev(tg, torch.uint8), B, T, N,
                                   _dev(ws), _dev(g0), _dev(g1), _dev(d0), _dev(d1), _stream()), "cvc_attn_nll_bwd")
     return d0, d1
+
+
+# --------------------------------------------------------------------------- self-critical training (csrc/cider.hip)
+def cider_d(cand: torch.Tensor, refs: torch.Tensor, nref: torch.Tensor, keys: torch.Tensor, idf: torch.Tensor, idf_unseen: float,
+            sigma: float = 6.0, want_orders: bool = False):
+    """cand [rows, T] int64; refs [clips, Rmax, T] int64 (rows % clips == 0: rows / clips samples per clip); nref [clips] int32; keys [G]
+    int64 holding the table's unsigned 64-bit keys, idf [G].  -> reward [rows] (, per_order [rows, 4])."""
+    if cand.dim() != 2 or refs.dim() != 3 or refs.shape[2] != cand.shape[1] or refs.shape[0] < 1 or cand.shape[0] % refs.shape[0] != 0 \
+            or nref.numel() != refs.shape[0] or idf.numel() != keys.numel():
+        raise RuntimeError(f"cvc.hip.cider_d: cand {tuple(cand.shape)}, refs {tuple(refs.shape)}, nref {tuple(nref.shape)}, keys "
+                           f"{tuple(keys.shape)}, idf {tuple(idf.shape)} do not fit")
+    rows, T = cand.shape
+    clips, Rmax = refs.shape[0], refs.shape[1]
+    G = int(keys.numel())
+    reward = torch.empty(rows, device=cand.device, dtype=torch.float32)
+    orders = torch.empty(rows, 4, device=cand.device, dtype=torch.float32) if want_orders else None
+    _check(lib().cvc_cider_d(_dev(cand, torch.int64, "cand"), _dev(refs, torch.int64, "refs"), _dev(nref, torch.int32, "nref"), rows, T,
+                             rows // clips, Rmax, _dev(keys, torch.int64, "keys") if G else None, _dev(idf, name="idf") if G else None, G,
+                             float(idf_unseen), float(sigma), _dev(reward), _dev(orders), _stream()), "cvc_cider_d")
+    return (reward, orders) if want_orders else reward
+
+
+def scst_weights(reward: torch.Tensor, base: Optional[torch.Tensor], per_clip: int, cand: torch.Tensor, t_major: bool = False):
+    """reward [rows], base [rows / per_clip] (per_clip == 1) or None, cand [rows, T] int64 -> adv [rows], w [rows, T] (t_major: [T, rows])"""
+    rows, T = cand.shape
+    if reward.numel() != rows or rows % int(per_clip) != 0 or (base is not None and base.numel() != rows // int(per_clip)):
+        raise RuntimeError(f"cvc.hip.scst_weights: reward {tuple(reward.shape)}, base {None if base is None else tuple(base.shape)}, "
+                           f"per_clip {per_clip}, cand {tuple(cand.shape)} do not fit")
+    adv = torch.empty(rows, device=cand.device, dtype=torch.float32)
+    w = torch.empty((T, rows) if t_major else (rows, T), device=cand.device, dtype=torch.float32)
+    _check(lib().cvc_scst_weights(_dev(reward, name="reward"), _dev(base, name="base"), rows, int(per_clip), _dev(cand, torch.int64, "cand"),
+                                  T, 1 if t_major else 0, _dev(adv), _dev(w), _stream()), "cvc_scst_weights")
+    return adv, w
 
 
 # --------------------------------------------------------------------------- tile path (rows > 64), csrc/gemm_tile.hip

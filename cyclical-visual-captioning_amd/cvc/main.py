@@ -31,11 +31,8 @@ from .trainer import Trainer, build_optimizer
 LAST_TRAINER = None
 
 
-def main(argv=None, sample=None, score=None):
-    """sample: (n, temperature, seed) or (n, temperature, seed, top_k, top_p) -- set up as for evaluation (checkpoint loading included), then write the validation split's
-    sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
-    score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
-    (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
+def build_parser():
+    """the reference's option surface (cvc.opts) plus the flags of this entry point"""
     parser = cvc_opts.build_parser()
     parser.add_argument("--synthetic_clips", type=int, default=128)
     parser.add_argument("--decode_weights", choices=("fp32", "bf16"), default="fp32",
@@ -61,6 +58,24 @@ def main(argv=None, sample=None, score=None):
     parser.add_argument("--synthetic_raw", action="store_true",
                         help="feed raw frame / region features through the once-per-clip encoder (model/backbone.py) "
                              "instead of pre-extracted features")
+    # self-critical training (Trainer.scst_step): sampled rollouts, CIDEr-D reward on the device
+    parser.add_argument("--scst_after", type=int, default=-1,
+                        help="take self-critical steps (CIDEr-D reward of sampled captions) from this epoch on; -1 = never")
+    parser.add_argument("--scst_samples", type=int, default=5,
+                        help="sampled captions per clip; > 1: leave-one-out baseline over the clip's samples, 1: greedy baseline")
+    parser.add_argument("--scst_temperature", type=float, default=1.0, help="temperature of the rollouts")
+    parser.add_argument("--scst_seed", type=int, default=1, help="seed of the rollouts' noise")
+    parser.add_argument("--scst_dropout", action="store_true",
+                        help="keep the training dropout on in the self-critical gradient pass (default: off, the policy that was sampled)")
+    return parser
+
+
+def main(argv=None, sample=None, score=None):
+    """sample: (n, temperature, seed) or (n, temperature, seed, top_k, top_p) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
+    score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
+    (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
+    parser = build_parser()
     opt = parser.parse_args(argv)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
@@ -113,6 +128,8 @@ def main(argv=None, sample=None, score=None):
         raise SystemExit("--no_repeat_ngram and --min_caption_len must be >= 0")
     if opt.group_size < 1 or opt.diversity_lambda < 0 or opt.length_penalty < 0:
         raise SystemExit("--group_size must be >= 1, --diversity_lambda and --length_penalty >= 0")
+    if opt.scst_samples < 1 or opt.scst_temperature <= 0:
+        raise SystemExit("--scst_samples must be >= 1 and --scst_temperature > 0")
     opt.force_word_ids = word_ids(opt.force_words, opt.wtoi, "--force_words")
     if len(opt.force_word_ids) > 3 or not 0 <= opt.force_detected <= 3 or (opt.force_word_ids and opt.force_detected):
         raise SystemExit("--force_words takes at most 3 words, --force_detected lies in 0 .. 3, and only one of them is given")
@@ -200,7 +217,7 @@ def main(argv=None, sample=None, score=None):
             infos = {"iter": (epoch + 1) * max(len(loader) - 1, 0), "epoch": epoch, "best_val_score": best, "vocab": full.itow,
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
-                         "ss_prob_history": {}}
+                         "ss_prob_history": {}, "reward_history": dict(trainer.reward_history)}
             with open(os.path.join(save_dir, "infos_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(infos, f)
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:

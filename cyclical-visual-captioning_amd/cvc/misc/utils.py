@@ -73,10 +73,14 @@ def _masked_nll_mean(txt_input, target):
     return (total / count).reshape(())
 
 
-def _masked_nll_mean_from_logits(logits, target, t_major=False):
+def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None):
     """Same value as _masked_nll_mean(log_softmax(logits), target), plus the per-row argmax, from one fused pass.
-    t_major: the rows of `logits` are ordered t * B + b (the C-driven training loops' outputs) instead of b * T + t."""
+    t_major: the rows of `logits` are ordered t * B + b (the C-driven training loops' outputs) instead of b * T + t.
+    row_weight: see _masked_nll_mean_from_head."""
     w = _text_mask(target).to(torch.float32)
+    if row_weight is not None:
+        total, argmax = F_.vocab_nll(logits, (target.t() if t_major else target).reshape(-1), row_weight.reshape(-1))
+        return (total / w.sum()).reshape(()), (argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
     if t_major:
         total, argmax = F_.vocab_nll(logits, target.t().reshape(-1), w.t().reshape(-1))
         return (total / w.sum()).reshape(()), argmax.view(target.shape[1], target.shape[0]).t()
@@ -84,11 +88,13 @@ def _masked_nll_mean_from_logits(logits, target, t_major=False):
     return (total / w.sum()).reshape(()), argmax.view(target.shape)
 
 
-def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False):
+def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False, row_weight=None):
     """_masked_nll_mean_from_logits(x W^T + b, target) with the criterion folded into the vocabulary head's GEMM finish: the logits
-    are never materialised (cvc.functional.vocab_head_nll); falls back to the two-step form for shapes that kernel does not take."""
+    are never materialised (cvc.functional.vocab_head_nll); falls back to the two-step form for shapes that kernel does not take.
+    row_weight: a real weight per row of x (in x's row order, any sign, 0 where the loss mask is 0) in place of the 0 / 1 loss mask:
+    -sum_r row_weight[r] log p(target[r]) / sum(mask) -- the self-critical loss, row_weight = advantage x mask.  None: the mask."""
     if not F_.vocab_head_nll_ok(x, weight):
-        return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major)
+        return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major, row_weight=row_weight)
     # the loss mask, its count and the t-major copies depend on the target alone: both heads of a cyclical pass (decode,
     # reconstruction) score against the same target tensor, so they are formed once and kept on it
     pre = getattr(target, "_cvc_nll_pre", None)
@@ -98,6 +104,8 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
         pre = ((target._version, t_major), tf.contiguous(), wf.contiguous(), w.sum())
         target._cvc_nll_pre = pre
     _, tf, wf, count = pre
+    if row_weight is not None:
+        wf = row_weight.reshape(-1).contiguous()
     if compute_only:       # -> (opaque result for a later call with done=, the argmax words)
         done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf)
         argmax = done[1]
@@ -129,13 +137,13 @@ class LMCriterion(nn.Module):
         loss, argmax = _masked_nll_mean_from_logits(logits, target, t_major)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
-    def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None):
+    def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None, row_weight=None):
         """from_logits() fed the vocabulary head's INPUT x [rows, R] and the head module (nn.Linear): the head's GEMM and the
         criterion run as one op, no logits tensor.  done: head_words()'s first result for the same x (the arithmetic then is not
         repeated)."""
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
-        loss, argmax = _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done)
+        loss, argmax = _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done, row_weight=row_weight)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
     @staticmethod
@@ -171,8 +179,8 @@ class LanguageCriterion(nn.Module):
     def from_logits(self, logits, target, t_major=False):
         return _masked_nll_mean_from_logits(logits, target, t_major)[0]
 
-    def from_head(self, x, head, target, t_major=False):
-        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major)[0]
+    def from_head(self, x, head, target, t_major=False, row_weight=None):
+        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, row_weight=row_weight)[0]
 
 
 def bbox_overlaps(rois, gt_box, frm_mask):

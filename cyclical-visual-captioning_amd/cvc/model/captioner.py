@@ -203,6 +203,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         return overlaps, self.roi_feat_extractor(segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, overlaps,
                                                  sample_idx)
 
+    def encode_clips(self, segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask):
+        """what a decode reads of the once-per-clip encoder: (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask)"""
+        _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
+            segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
+        return fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask
+
     def _forward_3_loops(self, segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats,
                          frm_mask, sample_idx, pnt_mask):
         """reference :196-382"""
@@ -440,6 +446,71 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         return (torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1),
                 None if fms[0] is None else torch.cat(fms, 1))
 
+    # ------------------------------------------------------------------ self-critical training: the gradient pass
+    def scst_loss(self, encoded, words, reward, base=None, per_clip: int = 1):
+        """The self-critical loss of sampled captions: loop A (reference :242-270) teacher-forced on the SAMPLED words, the vocabulary
+        head and its criterion with the advantage as row weight:  -sum_{r,t} w[r, t] log p(words[r, t]) / sum(mask),
+        w = advantage x mask (cvc_scst_weights; mask = LMCriterion's: the steps up to and including the first 0).
+        encoded: the once-per-clip encoder's (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask) of the B clips
+        (constants here: the decoder's parameters -- decoder_core, embed, logit -- are what this loss reaches);
+        words [B * per_clip, T] int64, row b * per_clip + j = sample j of clip b; reward [B * per_clip]; base [B] (per_clip == 1:
+        the greedy caption's reward) or None (per_clip > 1: leave-one-out mean of the clip's other samples).
+        Dropout follows the module's mode: eval() = the policy that was sampled.  More than 64 rows run loop A as groups of <= 64.
+        -> (loss (), adv [B * per_clip])"""
+        from .. import train_loops
+        fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
+        T, R, S = self.seq_length, self.rnn_size, int(per_clip)
+        rows = words.size(0)
+        if words.dim() != 2 or words.size(1) != T or words.dtype != torch.int64 or rows != fc_feats.size(0) * S:
+            raise RuntimeError(f"scst_loss: words must be int64 [B * per_clip, T] = [{fc_feats.size(0)} * {S}, {T}], got {words.dtype} "
+                               f"{tuple(words.shape)}")
+        F_.new_step()
+        if self.training and dropout.in_kernel(self.logit.weight):
+            dropout.advance(self.device)
+        rep = (lambda x: x.detach().contiguous()) if S == 1 else (lambda x: x.detach().repeat_interleave(S, 0))
+        fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats = (rep(x) for x in (fc_feats, conv_feats, p_conv_feats, pool_feats,
+                                                                                           p_pool_feats))
+        region_mask = rep(pnt_mask[:, 1:])
+        words = words.contiguous()
+        # a rollout goes on sampling behind its end mark (no early exit, reference :384-443): in the TARGET those words are zeroed, so
+        # that LMCriterion's mask of it (and its count) is "the steps up to and including the first 0", the mask of w; the inputs stay
+        # the rollout's own words, so every step's log-probs are the engine's (the recurrence is causal: no step that counts sees them)
+        target = words.masked_fill((words == 0).cumsum(1) > 0, 0)
+        inputs = torch.cat((words.new_zeros(rows, 1), words[:, :T - 1]), 1)                 # BOS = 0, then the sampled words
+        emb_all = self._embed(inputs, "emb_a")                                             # [rows, T, E]
+        dc = self.decoder_core
+        fc_in = fc_feats if self.opts.global_img_in_attn_lstm else None
+        plan = self._loop_plan(min(rows, 64), fc_feats)
+        if plan is not None:
+            attn_kind, inv_temp, drop_a, _ = plan
+            groups = train_loops.clip_groups(rows)
+            cut = lambda x, b0, b1: None if x is None else (x if len(groups) == 1 else x[b0:b1])
+            outs = []
+            for g, (b0, b1) in enumerate(groups):
+                arena = train_loops.LoopArena(1, T, b1 - b0, R, emb_all.shape[2], emb_all.device)
+                arena.sole = len(groups) == 1
+                drop = None if drop_a is None else (drop_a[0], drop_a[1] + 64 * g, drop_a[2])
+                outs.append(train_loops.decode_loop(arena, cut(emb_all, b0, b1), cut(fc_in, b0, b1),
+                                                    tuple(cut(f, b0, b1) for f in (pool_feats, p_pool_feats, conv_feats, p_conv_feats)),
+                                                    cut(region_mask, b0, b1), None, dc.att_lstm, dc.lang_lstm, dc.soft_attn, attn_kind,
+                                                    inv_temp, drop)[0])
+            out = (outs[0] if len(outs) == 1 else torch.cat(outs, 1)).view(T * rows, R)      # t-major rows
+            t_major = True
+        else:
+            state = self._init_step_state(rows)
+            steps = []
+            for t, emb in enumerate(emb_all.unbind(1)):
+                output, state, _roi, _fm, _wp = dc.step(emb, fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, region_mask,
+                                                        state, drop_site="out_a.%d" % t)
+                steps.append(output)
+            out = torch.stack(steps, 1).view(rows * T, R)
+            t_major = False
+        adv, w = hip.scst_weights(reward, base, S, words, t_major=t_major)
+        if self.debug_collect is not None:
+            self.debug_collect.update(scst_out=out, scst_t_major=t_major, scst_w=w)
+        loss = self.xe_criterion.from_head(out, self.logit, target, t_major=t_major, row_weight=w)
+        return loss.reshape(()), adv
+
     def _vis_embed(self, xt_clamp):
         """roi_feat_extractor.vis_embed (Embedding -> ReLU -> Dropout, backbone.py:55-57) on the grounder's class indices"""
         ve = self.roi_feat_extractor.vis_embed
@@ -480,7 +551,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
                 no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
                 beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None,
-                force_words=None):
+                force_words=None, encoded=None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -501,9 +572,14 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         force_words (argument, else the model's attributes, read from opts.force_word_ids / opts.force_detected): words the captions
         should contain, DecodeEngine's force_n -- a [B, C] integer tensor (-1 = unused) or a list of C ids applied to every clip,
         C <= 3; the engine is built with beam_history=True and force_n = C, the words are loaded into it for every batch, and seq is
-        the best-normed hypothesis among those that met the most forced words."""
-        _ov, (fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, _g, pnt_mask, _o, _c, _l) = self._encode(
-            segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
+        the best-normed hypothesis among those that met the most forced words.
+        encoded: encode_clips()'s result for this batch -- the encoder is then not run again (Trainer.scst_step: its rollouts, its
+        greedy baseline and its gradient pass read the same encoder outputs)."""
+        if encoded is not None:
+            fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
+        else:
+            fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = self.encode_clips(
+                segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
                      pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
         beam = self.beam_size if beam_size is None else int(beam_size)

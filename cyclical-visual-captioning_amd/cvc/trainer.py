@@ -99,6 +99,12 @@ class Trainer:
         self._side = None
         self._graph_broken = False
         self.graph_stats = dict(eager=0, replayed=0, captured=0)
+        # ---- self-critical training (scst_step): from epoch opts.scst_after on, -1 = never
+        self.scst_after = int(getattr(opts, "scst_after", -1))
+        self._cider = None            # cvc.cider.CiderD over the training captions, built at the first self-critical step
+        self._scst_steps = 0
+        self.last_scst = None
+        self.reward_history = {}      # epoch -> the mean reward of every display interval
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -205,6 +211,64 @@ class Trainer:
         else:
             from . import hip
             hip.bump_weights_generation()
+
+    # ------------------------------------------------------------------ self-critical training step
+    def cider(self):
+        """the CIDEr-D table of the training captions (cvc.cider.CiderD.from_dataset), built on first use"""
+        if self._cider is None:
+            from .cider import CiderD
+            self._cider = CiderD.from_dataset(self.dataset, self.device)
+        return self._cider
+
+    def scst_step(self, batch):
+        return self.scst_step_prepared(self._prepare(batch, True))
+
+    def scst_step_prepared(self, b):
+        """One self-critical optimisation step (SCST, Rennie et al. 2017) on a prepared batch: S = opts.scst_samples captions per clip
+        sampled from the model at opts.scst_temperature (the cached decode binding, DecodeEngine's sampling mode), scored against the
+        clip's ground-truth captions with CIDEr-D on the device (cvc.cider), and the REINFORCE gradient of
+        -sum adv * log p(sampled word) / sum(mask) through loop A and the vocabulary head (model.scst_loss).  Baseline: the mean
+        reward of the clip's other samples (S > 1), or the reward of the greedy caption (S = 1).  The encoder runs once, without
+        autograd and in eval mode; the decoder's parameters (decoder_core, embed, logit) are what the loss reaches.  Dropout is off in
+        the gradient pass unless opts.scst_dropout.  No host read-back between the rollout and optimizer.step().
+        The sampler leaves UNK out while log p is taken over the full vocabulary, as in the sampling engine.  Runs eagerly.
+        -> (loss, mean reward, mean baseline, mean |advantage|) as device scalars; the step's samples, rewards and advantages stay
+        in self.last_scst."""
+        model = getattr(self.model, "module", self.model)
+        o = self.opts
+        S, tau = int(getattr(o, "scst_samples", 5)), float(getattr(o, "scst_temperature", 1.0))
+        seed = int(getattr(o, "scst_seed", 1)) + self._scst_steps          # a sampling engine is seeded when it is built: once per step
+        cider = self.cider()
+        T = model.seq_length
+        plain = dict(beam_size=1, top_k=0, top_p=1.0, no_repeat_ngram=0, no_immediate_repeat=False, min_len=0, ban_words=(), bad_endings=(),
+                     beam_groups=1, diversity_lambda=0.0, length_penalty=0.0)
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                enc = model.encode_clips(b["segs_feat"], b["ppls"], b["num"], b["mask_bboxs"], b["ppls_feat"], b["gt_bboxs"], b["mask_frms"],
+                                         b["sample_idx"], b["pnt_mask"])
+                args = (b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"], b["gt_bboxs"], b["ppls_feat"],
+                        b["mask_frms"], b["sample_idx"], b["pnt_mask"])
+                seq, _, logprob = model._sample(*args, sample_max=0, temperature=tau, sample_n=S, seed=seed, encoded=enc, **plain)
+                seq = seq.contiguous()
+                refs = b["gt_seqs"][:, :, :T].contiguous()
+                nref = b["num"][:, 0].to(torch.int32)
+                reward = cider.score(seq, refs, nref)
+                base = greedy = None
+                if S == 1:
+                    greedy = model._sample(*args, sample_max=1, encoded=enc, **plain)[0].contiguous()
+                    base = cider.score(greedy, refs, nref)
+            if bool(getattr(o, "scst_dropout", False)):
+                model.train()
+            loss, adv = model.scst_loss(enc, seq, reward, base, S)
+        finally:
+            model.train(was_training)
+        self._backward_and_update(loss)
+        self._weights_changed()
+        self._scst_steps += 1
+        self.last_scst = dict(seq=seq, logprob=logprob, reward=reward, base=base, greedy=greedy, adv=adv, seed=seed)
+        return loss.detach(), reward.mean(), (reward - adv).mean(), adv.abs().mean()
 
     # ------------------------------------------------------------------ HIP-graph training step
     def _core_step(self, b):
@@ -418,11 +482,12 @@ class Trainer:
 
     # ------------------------------------------------------------------ epoch loops
     def train(self, epoch, tb_logger=None):
-        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon")}
+        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward")}
         self.model.train()
         end = time.time()
         n_steps = len(self.train_loader) - 1                 # the reference drops the last batch (:55)
-        graphed = self.graph_capable()
+        scst = self.scst_after >= 0 and epoch >= self.scst_after     # self-critical epochs: eager steps (scst_step_prepared)
+        graphed = self.graph_capable() and not scst
         self._active_buckets = self.shape_buckets if graphed else 0       # (read by _prepare, which the prefetcher calls)
         # batch k+1 is staged into HBM on a side stream while step k runs
         batches = DevicePrefetcher(self.train_loader, lambda raw: self._prepare(raw, True), self.device, limit=n_steps)
@@ -455,6 +520,10 @@ class Trainer:
                 kept.clear()
             else:
                 sums, cur = torch.stack([acc, last]).tolist()
+            if scst:                                  # (a sixth element: the step's mean reward)
+                meters["reward"].update(sums[5] / pending, n * pending)
+                meters["reward"].val = cur[5]
+                self.reward_history.setdefault(epoch, []).append(sums[5] / pending)
             for name, i in (("lm", 1), ("attn", 2), ("cls", 3), ("recon", 4)):
                 meters[name].update(sums[i] / pending, n * pending)
                 meters[name].val = cur[i]
@@ -467,7 +536,12 @@ class Trainer:
                 void_flags = torch.zeros(KEEP_MAX, device=self.device)
             for step, b in enumerate(batches):
                 meters["data"].update(time.time() - end)
-                if graphed:
+                if scst:
+                    # the meters' "LM Loss" is the self-critical loss; the attention / class / reconstruction terms take no part
+                    s_loss, s_reward, _s_base, _s_adv = self.scst_step_prepared(b)
+                    zero = torch.zeros((), device=s_loss.device)
+                    res = torch.stack([s_loss, s_loss, zero, zero, zero, s_reward.to(s_loss.dtype)])
+                elif graphed:
                     res = self.train_step_bucketed(b)
                 else:
                     res = torch.stack([x.reshape(()) for x in self.train_step_prepared(b)])
@@ -483,7 +557,8 @@ class Trainer:
                           'LM Loss {l.val:.4f} ({l.avg:.4f})\tAttn Loss {a.val:.4f} ({a.avg:.4f})\t'
                           'Cls Loss {c.val:.4f} ({c.avg:.4f})\tRecon Loss {r.val:.4f} ({r.avg:.4f})'.format(
                               epoch, step, n_steps, b=meters["batch"], d=meters["data"], l=meters["lm"], a=meters["attn"],
-                              c=meters["cls"], r=meters["recon"]))
+                              c=meters["cls"], r=meters["recon"]) +
+                          ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else ''))
                 else:
                     if deferred and pending >= KEEP_MAX:
                         flush()
@@ -496,6 +571,8 @@ class Trainer:
             tb_logger.add_scalar('train/attn_loss', meters["attn"].avg, epoch)
             tb_logger.add_scalar('train/cls_loss', meters["cls"].avg, epoch)
             tb_logger.add_scalar('train/lm_recon_loss', meters["recon"].avg, epoch)
+            if scst:
+                tb_logger.add_scalar('train/scst_reward', meters["reward"].avg, epoch)
 
     def _segment_timestamps(self):
         """{video: {segment: [start, end]}} of the validation segments: the reference reads them from the ANet-Entities

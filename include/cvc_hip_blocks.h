@@ -473,6 +473,30 @@ int cvc_packed_lstm_embgate_keys_fwd(const float* wp, long long w_blk_stride, co
 int cvc_keys_finalize(const unsigned long long* keys, const unsigned long long* key_unk, const float* ms_part, int nblocks, int T,
                       int rows, int unk_idx, int64_t* words, float* logprob, cvc_stream_t stream);
 
+/* ---- self-critical training: the CIDEr-D reward of sampled captions (csrc/cider.hip; cvc.cider.CiderD, Trainer.scst_step).
+ * A caption's words are its ids up to and including the first 0 (L words; all T without a 0).  An n-gram (n = 1..4) is an exact
+ * 64-bit key: 16 bits per word holding id + 1, the first word in the highest bits, unused positions 0.
+ *   cand [rows, T] int64: row c * per_clip + j = sample j of clip c;  refs [rows / per_clip, Rmax, T] int64, of which the first
+ *   nref[clip] (int32, clamped to [0, Rmax]) count;  keys [G] ascending as unsigned values with idf [G] = ln N_doc - ln max(1, df)
+ *   (computed in fp64 on the host), idf_unseen = ln N_doc for an n-gram that is not in the table (G = 0: keys / idf may be null).
+ *   v_n[g] = count * idf[g];  s_n = sum_g min(v_n^c[g], v_n^r[g]) v_n^r[g] / (|v_n^c| |v_n^r|), 0 if a norm is 0, times
+ *   exp(-(L_c - L_r)^2 / (2 sigma^2));  per_order [rows, 4] (nullable) = 10 * mean_r s_n;  reward [rows] = mean_n per_order,
+ *   0 for a clip without references.
+ * One wave per row, no atomics, fixed summation order: a row's result is bit-reproducible and independent of the other rows.
+ * Null pointers, rows < 1, T < 1 or T > 63, rows % per_clip != 0, Rmax < 1, G < 0, sigma <= 0: CVC_E_BADARG, before any launch. */
+int cvc_cider_d(const int64_t* cand, const int64_t* refs, const int32_t* nref, int rows, int T, int per_clip, int Rmax,
+                const unsigned long long* keys, const float* idf, int G, float idf_unseen, float sigma, float* reward,
+                float* per_order, cvc_stream_t stream);
+
+/* ---- self-critical training: rewards -> per-token loss weights, one launch (csrc/cider.hip).
+ *   per_clip = S > 1: adv[j] = reward[j] - (sum of the clip's other S - 1 rewards, ascending k) / (S - 1); base must be null.
+ *   per_clip = 1:     adv[row] = reward[row] - base[row]; base (the greedy caption's reward) must be given.
+ *   w[row, t] = adv[row] for the steps up to and including the first 0 of cand [rows, T], 0 after it (the mask of LMCriterion);
+ *   w is row-major (row * T + t), or t-major (t * rows + row) with t_major != 0 -- the row order of the C-driven training loops.
+ * Null pointers (but base), rows < 1, T < 1, rows % per_clip != 0, base given with S > 1 or missing with S = 1: CVC_E_BADARG. */
+int cvc_scst_weights(const float* reward, const float* base, int rows, int per_clip, const int64_t* cand, int T, int t_major,
+                     float* adv, float* w, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
