@@ -72,7 +72,10 @@ def up_to_date() -> bool:
 # compiler bump cannot regress this silently; the 128-row-vs-64-row bit-equality test in the default GPU suite is the other guard.
 # (gemm_packed.hip: no inline assembly, but register rings of up to 214-232 VGPRs at 64 rows in the bf16-weight mode -- a spill
 # there is a silent 2x; the entry covers every instantiation of the kernel template, fp32 forms included)
-NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",)}
+# (mix.hip: the mixed selection block keeps a row's logits in registers, up to 32 per thread, next to the draw's and the given word's
+# bookkeeping -- a spill there is silent and slow)
+NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",),
+                      "mix.hip": ("sample_select_kernel",)}
 
 
 def check_no_scratch(src: str, remarks: str):

@@ -43,6 +43,7 @@ const Entry table[] = {
     CVC_B(cvc_sample_select_parts),
     CVC_B(cvc_sample_select_trunc_parts),
     CVC_B(cvc_sample_advance),
+    CVC_B(cvc_mixed_select_parts),
     CVC_B(cvc_forced_select_parts),
     CVC_B(cvc_constrained_select_parts),
     CVC_B(cvc_beam_select_hist_parts),

@@ -1,6 +1,7 @@
 // The selection kernel of sampled decoding and the one function behind its entry points, shared by csrc/sample.hip
 // (cvc_sample_select_parts / cvc_sample_select_trunc_parts: contract in that file's header comment) and csrc/constrain.hip
-// (cvc_constrained_select_parts: the CONS flag of the same kernel, contract in that file).  One definition of the hash counters, the
+// (cvc_constrained_select_parts: the CONS flag of the same kernel, contract in that file) and csrc/mix.hip (cvc_mixed_select_parts:
+// the MIX flag, scheduled sampling's drawn-or-given word, contract in that file).  One definition of the hash counters, the
 // noise, the candidate mask, the truncation search and the log-prob: every form rounds alike.  The row loader, the shared argument
 // checks and the NC / NP / VEC dispatch are those of every selection block (csrc/select_row.h).
 #pragma once
@@ -21,6 +22,13 @@ template <> struct trunc_args<true> { using type = TruncArgs; };
 
 // what the constrained form takes on top (csrc/constrain.hip): ConsArgs of csrc/ban_set.h, the row's history and the rules
 
+// what the mixed form takes on top (csrc/mix.hip): the given word per row, the probability of taking the drawn one (device memory),
+// the coin's hash site and the nullable outputs
+struct NoMix {};
+struct MixArgs { const int64_t* given; int given_stride; const float* mix_prob; uint32_t site; int64_t* drawn; uint8_t* took; float* given_logprob; };
+template <bool MIX> struct mix_args { using type = NoMix; };
+template <> struct mix_args<true> { using type = MixArgs; };
+
 // the float of an order-preserving key: key(a) < key(b) <=> a < b over the non-NaN floats (-0 below +0; keys above key(+inf) and
 // below KEY_NEG_INF are NaNs)
 __device__ __forceinline__ float unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
@@ -35,13 +43,17 @@ __device__ __forceinline__ float gumbel(uint32_t h) {
 // `banned` mask: UNK, and with CONS the row's whole ban set (a V-bit map in LDS, built from the history and the lists: csrc/ban_set.h).
 // TRUNC: the cutoff search of the header comment in front of the Gumbel-max; the noise is then drawn for the kept words only.
 // CONS: inv_tau == 0 is the arg-max mode (s = z, no noise, state unread).
-template <int NC, int NP, bool VEC, bool TRUNC, bool CONS>
+// MIX: the plain form's draw, then a per-row coin decides whether the drawn or the given word is written (contract: csrc/mix.hip);
+// the given word's logit is published by its owner during the scan and scored against the row's own max / sum-exp.
+template <int NC, int NP, bool VEC, bool TRUNC, bool CONS, bool MIX = false>
 __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, int nparts, long long part_stride, const float* bias,
                                                            int V, int unk, float inv_tau, const uint32_t* state, uint32_t site,
                                                            int64_t* word, int wstride, float* logprob,
                                                            typename trunc_args<TRUNC>::type ta,
-                                                           typename cons_args<CONS>::type ca) {
+                                                           typename cons_args<CONS>::type ca,
+                                                           typename mix_args<MIX>::type ma) {
 #pragma clang fp contract(off)
+    static_assert(!MIX || (!TRUNC && !CONS), "the mixed form draws from the plain distribution");
     __shared__ float red_m[4], red_s[4], red_v[4], red_z[4];
     __shared__ int red_i[4];
     [[maybe_unused]] __shared__ int red_b[4];
@@ -52,6 +64,12 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
     float z[NC];
     load_logit_row<NC, NP, VEC>(parts + (size_t)row * V, nparts, part_stride, bias, V, tid, z);
     auto col = [&](int u) { return ::col<VEC>(tid, u); };
+    [[maybe_unused]] __shared__ float zg_pub;              // MIX: the given word's logit, read by thread 0 after the barriers below
+    [[maybe_unused]] int g = -1;                           // MIX: the given word, -1 outside [0, V) (uniform over the workgroup)
+    if constexpr (MIX) {
+        const int64_t g64 = ma.given[(size_t)row * ma.given_stride];
+        g = (g64 >= 0 && g64 < (int64_t)V) ? (int)g64 : -1;
+    }
     // bit u of `banned` = the word of register slot u is not a candidate: UNK, with CONS any word of the row's ban set
     static_assert(NC <= 32, "one ban bit per register slot");
     uint32_t banned = 0;
@@ -156,6 +174,7 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
         const int v = col(u);
         if (v < V) {
             if constexpr (!TRUNC) m = fmaxf(m, z[u]);
+            if constexpr (MIX) { if (v == g) zg_pub = z[u]; }
             bool cand = !((banned >> u) & 1u);
             if constexpr (TRUNC) cand = z[u] >= theta && cand;          // this order: one branch per slot (profiles/select_blocks_merge.md)
             if (cand) {
@@ -202,7 +221,18 @@ __global__ __launch_bounds__(WG) void sample_select_kernel(const float* parts, i
         const float S = (red_s[0] + red_s[1]) + (red_s[2] + red_s[3]);
         int w = bi;
         if (w < 0 || w >= V) w = 0;        // every score NaN: nothing compared better; the word is a gather index next step
-        word[(size_t)row * wstride] = w;
+        if constexpr (MIX) {
+            // the coin: its own site, the row as counter; u is exact in fp32 and strictly inside (0, 1): p = 0 never takes, p = 1 always
+            const uint32_t hc = cvc_drop_hash(seed_lo, seed_hi, call, ma.site, (uint32_t)row);
+            const bool took = ((float)(hc >> 9) + 0.5f) * 0x1p-23f < *ma.mix_prob;
+            if (ma.drawn != nullptr) ma.drawn[row] = w;
+            if (ma.took != nullptr) ma.took[row] = took ? 1 : 0;
+            // the forced block's definition and bits (csrc/forced.hip): same m, same S; a given word outside [0, V) scores NaN
+            if (ma.given_logprob != nullptr) ma.given_logprob[row] = g >= 0 ? zg_pub - (m + logf(S)) : __builtin_nanf("");
+            word[(size_t)row * wstride] = took ? w : (g >= 0 ? g : 0);
+        } else {
+            word[(size_t)row * wstride] = w;
+        }
         if (logprob != nullptr) logprob[row] = bz - (m + logf(S));
         if constexpr (CONS) {
             if (ca.nbanned != nullptr) ca.nbanned[row] = (red_b[0] + red_b[1]) + (red_b[2] + red_b[3]);
@@ -241,7 +271,7 @@ static int select_run(const float* parts, int nparts, long long part_stride, con
             hipLaunchKernelGGL((sample_select_kernel<decltype(nc)::value, decltype(np)::value, decltype(vec)::value,
                                                      decltype(trunc_)::value, CONS>),
                                dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, bias, V, unk_idx, inv_tau, rng_state,
-                               site, word, word_stride, logprob, ta, ca);
+                               site, word, word_stride, logprob, ta, ca, NoMix{});
         });
     };
     if (trunc || cutoff != nullptr || kept != nullptr) launch(std::true_type{}, TruncArgs{top_k, top_p, cutoff, kept});

@@ -67,7 +67,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  sample_n: int = 1, temperature: Optional[float] = None, seed: Optional[int] = None, weights_dtype: str = "fp32",
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
                  min_len: int = 0, ban_words=None, bad_endings=None, beam_groups: int = 1, diversity: float = 0.0,
-                 length_penalty: float = 0.0, force_n: int = 0, tail: Optional[str] = None, beam_history: bool = False):
+                 length_penalty: float = 0.0, force_n: int = 0, tail: Optional[str] = None, mix: bool = False,
+                 beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -154,7 +155,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         block's best candidate as a 64-bit key (an integer max over the workgroups: csrc/sel_keys.h), the next step's attention cell
         decodes its word from the keys, and one launch after the loop writes words and log-probs: six launches per step instead of
         seven.  "launch": cvc_top2_final after every head, as every other mode runs.  None = TAIL_DEFAULT where the fused tail
-        applies, "launch" elsewhere; an explicit "fused" where it does not apply is refused."""
+        applies, "launch" elsewhere; an explicit "fused" where it does not apply is refused.
+        mix: scheduled sampling -- a sampling engine (temperature, seed, sample_n) that also holds given words
+        (load_captions(); self.given_words [T, rows]) and a probability in device memory (set_mix_prob(); self.mix_prob, one float,
+        0 until set).  Step t's word_select is cvc_mixed_select_parts: it draws the sampler's word, flips a per-row coin and writes
+        the drawn word (probability p) or the given word of that position as words[t + 1], the next step's input; the probability is
+        read by the kernel, so a captured graph serves a changing one.  The sampling paths' launch lists (packed, tile, ring), no C
+        driver, capture() works.  run() returns (inputs_next [rows, T] = the words that were fed on, att2_weights, logprob of the
+        DRAWN words); self.drawn [T, rows] int64, self.took [T, rows] uint8 and self.given_logprob [T, rows] (the given word's
+        log-prob, the forced block's bits) stay on the engine.  Refused: no temperature, beam > 1, forced_n, any constraint, top_k /
+        top_p, weights_dtype="bf16"."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -174,6 +184,25 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             gate_ksplit, lang_ksx = False, False
         self.cons = _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings)
         self.constrained = bool(self.cons[0] or self.cons[1] or self.cons[2] or self.cons[3] or self.cons[4])
+        if not isinstance(mix, (bool, np.bool_)):
+            raise RuntimeError(f"DecodeEngine: mix must be a bool, got {mix!r}")
+        self.mix = bool(mix)
+        if self.mix:
+            why = None
+            if temperature is None:
+                why = "it draws from the sampling engine: it needs a temperature"
+            elif self.beam != 1:
+                why = "beam search (beam > 1) chooses its own words"
+            elif self.forced:
+                why = "the forced mode (forced_n) follows given words only"
+            elif self.constrained:
+                why = "constrained decoding is not part of it"
+            elif (not isinstance(top_k, bool) and isinstance(top_k, (int, np.integer)) and top_k != 0) or top_p != 1.0:
+                why = "top_k / top_p truncation is not part of it"
+            elif self.bf16w:
+                why = 'weights_dtype="bf16" is not part of it'
+            if why is not None:
+                raise RuntimeError(f"DecodeEngine: the mixed mode (mix=True) is refused: {why}")
         if not isinstance(beam_history, (bool, np.bool_)):
             raise RuntimeError(f"DecodeEngine: beam_history must be a bool, got {beam_history!r}")
         self.beam_hist = bool(beam_history)
@@ -334,6 +363,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.sampling:
             self.rng = torch.zeros(4, device=dev, dtype=torch.int32)          # {seed_lo, seed_hi, call, 0} (uint32 bit patterns)
             self.seed(0 if seed is None else seed)
+        if self.mix:
+            self.given_words = torch.zeros(self.T, rows, dtype=torch.int64, device=dev)   # the given word of every position (load_captions)
+            self.mix_prob = z(1)                                                          # P(the drawn word is fed on); set_mix_prob
+            self.drawn = torch.zeros(self.T, rows, dtype=torch.int64, device=dev)
+            self.took = torch.zeros(self.T, rows, dtype=torch.uint8, device=dev)
+            self.given_logprob = z(self.T, rows)
         if self.forced:
             self.rank = torch.zeros(self.T, rows, dtype=torch.int32, device=dev)      # rank of the given word among the row's logits
             self.fmask = self.fm_steps = None                                          # bound by load_captions(frame_mask=...)
@@ -579,11 +614,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         copied into the engine-owned mask; from the first such call on the region attention of step t also writes fm_steps[t], its
         pre-softmax scores with the fill value at the masked proposals.  The mask changes the launch list, so it has to be bound
         before capture(); None on an engine that has one clears it (fm_steps = the unmasked scores)."""
-        if not self.forced:
+        if not self.forced and not self.mix:
             raise RuntimeError("DecodeEngine.load_captions: this engine is not in the forced mode (forced_n = 0)")
         if tuple(words.shape) != (self.rows, self.T) or words.dtype != torch.int64:
             raise RuntimeError(f"DecodeEngine.load_captions: words must be int64 [{self.rows}, {self.T}], got {words.dtype} "
                                f"{tuple(words.shape)}")
+        if self.mix:                     # the mixed mode: the given word of every position, the same stream-ordered copy
+            if frame_mask is not None:
+                raise RuntimeError("DecodeEngine.load_captions: the mixed mode takes no frame mask")
+            self.given_words.copy_(words.t())
+            return self
         if frame_mask is not None:
             if tuple(frame_mask.shape) != (self.T, self.rows, self.N):
                 raise RuntimeError(f"DecodeEngine.load_captions: frame_mask has shape {tuple(frame_mask.shape)}, expected "
@@ -600,6 +640,27 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         elif self.fmask is not None:
             self.fmask.zero_()
         self.words[1:].copy_(words.t())
+        return self
+
+    def weights_refreshed(self):
+        """After DecodeWeights.refresh(): the one engine-owned operand that was computed from a weight when the engine was bound --
+        the embedded BOS word in the packed path's initial activations without the embedding-gate schedule -- is recomputed in
+        place.  Everything else the launch list reads is the weights object's own storage."""
+        if self.packed and not self.embgate:
+            W = self.W
+            bos = torch.relu(W.embed[0]).view(1, W.E).expand(self.rows, W.E).contiguous()
+            self.XA0_init[W.R // 4:(W.R + W.E) // 4] = to_quad(bos)
+        return self
+
+    def set_mix_prob(self, p: float):
+        """Mixed mode: the probability that a step feeds its DRAWN word on (0 = teacher forcing, 1 = the sampling engine), filled
+        into the engine-owned device float (stream-ordered: a captured graph reads the new value at its next replay)."""
+        if not self.mix:
+            raise RuntimeError("DecodeEngine.set_mix_prob: this engine is not in the mixed mode (mix=False)")
+        p = float(p)
+        if not (0.0 <= p <= 1.0):
+            raise RuntimeError(f"DecodeEngine.set_mix_prob: the probability must lie in [0, 1], got {p!r}")
+        self.mix_prob.fill_(p)
         return self
 
     def load_force_words(self, words):
@@ -676,6 +737,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self.logprob[t].data_ptr(), opt(getattr(self, "cutoff", None)), opt(getattr(self, "kept", None)),
                 self.words[1].data_ptr(), rows, self._cons_desc, self.nbanned[t].data_ptr()))
         tail = (self.rng.data_ptr(), t, self.words[t + 1].data_ptr(), 1, self.logprob[t].data_ptr())
+        if self.mix:
+            return ("word_select", L.cvc_mixed_select_parts, head + tail + (
+                self.given_words[t].data_ptr(), 1, self.mix_prob.data_ptr(), self.drawn[t].data_ptr(), self.took[t].data_ptr(),
+                self.given_logprob[t].data_ptr()))
         if not self.trunc:
             return ("word_select", L.cvc_sample_select_parts, head + tail)
         return ("word_select", L.cvc_sample_select_trunc_parts, head + (self.top_k, self.top_p) + tail +
@@ -770,7 +835,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
         key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail)
+               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail, self.mix)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
@@ -804,7 +869,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         temperature (constrained beam search: what a beam engine returns, (seq, att2_weights, final beam scores [B, beam])).  A beam
         engine's seq is the rank-0 hypothesis; with beam_groups > 1 or a length_penalty it is the best hypothesis by norm = score /
         len^alpha (self.order[:, 0]), with its attention rows, and the scores stay in slot order.  Forced mode: (seq = the given words, att2_weights, logprob,
-        rank [B*n, T] int32), row b * n + j = caption j of clip b."""
+        rank [B*n, T] int32), row b * n + j = caption j of clip b.  Mixed mode: the sampling engine's tuple with seq = the words
+        that were fed on (drawn or given) and logprob = the DRAWN words' (self.drawn)."""
         if self.graph is not None:
             self.graph.replay()
         else:

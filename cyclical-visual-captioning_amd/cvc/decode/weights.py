@@ -52,6 +52,50 @@ class DecodeWeights:
         for t in vars(self).values():
             if isinstance(t, torch.Tensor) and (not t.is_cuda or t.dtype != torch.float32):
                 raise RuntimeError("DecodeWeights: parameters must be fp32 tensors on the GPU (no CPU fallback)")
+        # flat views that do NOT alias their checkpoint tensor (it was not contiguous): refresh() copies these
+        flat = (("w_ih_att", "decoder_core.att_lstm.weight_ih"), ("w_hh_att", "decoder_core.att_lstm.weight_hh"),
+                ("b_ih_att", "decoder_core.att_lstm.bias_ih"), ("b_hh_att", "decoder_core.att_lstm.bias_hh"),
+                ("w_ih_lang", "decoder_core.lang_lstm.weight_ih"), ("w_hh_lang", "decoder_core.lang_lstm.weight_hh"),
+                ("b_ih_lang", "decoder_core.lang_lstm.bias_ih"), ("b_hh_lang", "decoder_core.lang_lstm.bias_hh"),
+                ("w_h", "decoder_core.soft_attn.h2attn.weight"), ("b_h", "decoder_core.soft_attn.h2attn.bias"),
+                ("w_a", "decoder_core.soft_attn.alpha_net.weight"), ("b_a", "decoder_core.soft_attn.alpha_net.bias"),
+                ("embed", "embed.0.weight"), ("w_o", "logit.weight"), ("b_o", "logit.bias"))
+        self._copies = [(getattr(self, a), sd[k].detach()) for a, k in flat
+                        if getattr(self, a) is not None and getattr(self, a).data_ptr() != sd[k].data_ptr()]
+
+    def refresh(self):
+        """The checkpoint tensors were updated IN PLACE (an optimizer step): every derived operand that exists on this object --
+        the packed path's p_* (and p_*_ks), the tile path's t_*, the embedding-gate table, the bf16 mode's packs and rounded views --
+        is recomputed into its existing storage, so engines bound to this object, their launch lists and their captured graphs stay
+        valid.  The flat views alias the parameters (a view that had to be a copy is copied again).  Stream-ordered, no host
+        read-back.  Returns self."""
+        for dst, src in self._copies:
+            dst.copy_(src.reshape(dst.shape))
+        R, E = self.R, self.E
+        att3 = lambda: torch.cat([self.w_ih_att[:, 0:R], self.w_ih_att[:, 2 * R:2 * R + E], self.w_hh_att], 1)   # K = 2R + E
+        att2 = lambda: torch.cat([self.w_ih_att[:, 0:R], self.w_hh_att], 1)                                      # K = 2R
+        lang = lambda: torch.cat([self.w_ih_lang, self.w_hh_lang], 1)
+        pad = lambda name, k: getattr(self, name).shape[1] - k // 4               # the stagger of a K-split pack, from its shape
+        build = {
+            "p_att": lambda: pack_weights(att3(), R), "p_att2": lambda: pack_weights(att2(), R),
+            "p_lang": lambda: pack_weights(lang(), R), "p_h": lambda: pack_weights(self.w_h), "p_o": lambda: pack_weights(self.w_o),
+            "p_att_ks": lambda: pack_weights(att3(), R, pad("p_att_ks", 2 * R + E)),
+            "p_lang_ks": lambda: pack_weights(lang(), R, pad("p_lang_ks", 3 * R)),
+            "t_att": lambda: pack_weights_tile(att3(), R), "t_att2": lambda: pack_weights_tile(att2(), R),
+            "t_lang": lambda: pack_weights_tile(lang(), R), "t_h": lambda: pack_weights_tile(self.w_h),
+            "t_o": lambda: pack_weights_tile(self.w_o), "t_fc": lambda: pack_weights_tile(self.w_ih_att[:, R:2 * R].contiguous()),
+            "t_embgate": lambda: embgate_table(self),
+            # the bf16 mode (bind_bf16): everything derived from a rounded matrix is derived from the ROUNDED values
+            "pb_att2": lambda: pack_weights_bf16(att2(), R), "pb_lang": lambda: pack_weights_bf16(lang(), R),
+            "pb_h": lambda: pack_weights_bf16(self.w_h), "pb_o": lambda: pack_weights_bf16(self.w_o),
+            "r_w_fc": lambda: bf16_round(self.w_ih_att[:, R:2 * R]),
+            "r_embgate": lambda: hip.tile_mm(torch.relu(self.embed), bf16_round(self.w_ih_att[:, 2 * R:2 * R + E])),
+        }
+        for name, fn in build.items():
+            dst = getattr(self, name, None)
+            if dst is not None:
+                dst.copy_(fn())
+        return self
 
 
 def _segs(items):

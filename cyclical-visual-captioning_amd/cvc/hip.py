@@ -242,6 +242,8 @@ SIGNATURES = {
     "cvc_sample_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P],
     "cvc_sample_select_trunc_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P],
     "cvc_sample_advance": [_P, _P],
+    # scheduled sampling: draw, coin, drawn-or-given word (csrc/mix.hip; building block)
+    "cvc_mixed_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P],
     "cvc_forced_select_parts": [_P, _I, _LL, _P, _I, _I, _P, _I, _P, _P, _P],
     "cvc_constrained_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P, _LL, C.POINTER(Constraint),
                                      _P, _P],
@@ -310,7 +312,7 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights"}
+    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",

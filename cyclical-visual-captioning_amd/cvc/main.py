@@ -25,7 +25,7 @@ from .data_synth import SyntheticCaptionDataset, collate
 from .distributed import GradReducer, init_from_env, shard_range, exchange_comm, destroy_exchange_comm
 from .misc import utils
 from .model.create_model import build_model
-from .trainer import Trainer, build_optimizer
+from .trainer import Trainer, build_optimizer, ss_prob_at
 
 
 LAST_TRAINER = None
@@ -67,6 +67,14 @@ def build_parser():
     parser.add_argument("--scst_seed", type=int, default=1, help="seed of the rollouts' noise")
     parser.add_argument("--scst_dropout", action="store_true",
                         help="keep the training dropout on in the self-critical gradient pass (default: off, the policy that was sampled)")
+    # scheduled sampling (Trainer.train_step_prepared with model.ss_prob > 0): loop A fed the model's own sampled words
+    parser.add_argument("--scheduled_sampling_start", type=int, default=-1,
+                        help="from this epoch on a growing share of the decoder's training inputs are its own sampled words; -1 = never")
+    parser.add_argument("--scheduled_sampling_increase_every", type=int, default=5, help="raise the share every this many epochs")
+    parser.add_argument("--scheduled_sampling_increase_prob", type=float, default=0.05, help="by this much")
+    parser.add_argument("--scheduled_sampling_max_prob", type=float, default=0.25, help="up to this share")
+    parser.add_argument("--scheduled_sampling_temperature", type=float, default=1.0, help="temperature of the sampled words")
+    parser.add_argument("--scheduled_sampling_seed", type=int, default=1, help="seed of the sampled words' noise and of the coins")
     return parser
 
 
@@ -130,6 +138,11 @@ def main(argv=None, sample=None, score=None):
         raise SystemExit("--group_size must be >= 1, --diversity_lambda and --length_penalty >= 0")
     if opt.scst_samples < 1 or opt.scst_temperature <= 0:
         raise SystemExit("--scst_samples must be >= 1 and --scst_temperature > 0")
+    if (opt.scheduled_sampling_increase_every < 1 or opt.scheduled_sampling_temperature <= 0 or opt.scheduled_sampling_increase_prob < 0
+            or not 0 <= opt.scheduled_sampling_max_prob <= 1):
+        raise SystemExit("--scheduled_sampling_increase_every must be >= 1, --scheduled_sampling_temperature > 0, "
+                         "--scheduled_sampling_increase_prob >= 0 and --scheduled_sampling_max_prob in [0, 1]")
+    opt.ss_temperature, opt.ss_seed = opt.scheduled_sampling_temperature, opt.scheduled_sampling_seed     # (Trainer reads these)
     opt.force_word_ids = word_ids(opt.force_words, opt.wtoi, "--force_words")
     if len(opt.force_word_ids) > 3 or not 0 <= opt.force_detected <= 3 or (opt.force_word_ids and opt.force_detected):
         raise SystemExit("--force_words takes at most 3 words, --force_detected lies in 0 .. 3, and only one of them is given")
@@ -163,6 +176,7 @@ def main(argv=None, sample=None, score=None):
         start_epoch = infos.get("epoch", 0)
     val_result_history = histories.get("val_result_history", {})
     lr_history = histories.get("lr_history", {})
+    ss_prob_history = histories.get("ss_prob_history", {})
 
     optimizer = build_optimizer(model, opt)
     # flat gradient arenas; exchanges only when world > 1 -- on the package's own RCCL communicator (--dist_backend rccl, the
@@ -193,6 +207,11 @@ def main(argv=None, sample=None, score=None):
 
     for epoch in range(start_epoch, opt.max_epochs):
         if not opt.inference_only:
+            if opt.scheduled_sampling_start >= 0:               # the schedule is on: the epoch's share, set before the epoch and recorded
+                core = getattr(model, "module", model)
+                core.ss_prob = ss_prob_at(epoch, opt.scheduled_sampling_start, opt.scheduled_sampling_increase_every,
+                                          opt.scheduled_sampling_increase_prob, opt.scheduled_sampling_max_prob)
+                ss_prob_history[epoch] = core.ss_prob
             trainer.train(epoch, tb)
         if epoch % max(opt.val_every_epoch, 1) != 0:        # reference main.py:221: scheduler + checkpoints only with an eval
             continue
@@ -217,7 +236,7 @@ def main(argv=None, sample=None, score=None):
             infos = {"iter": (epoch + 1) * max(len(loader) - 1, 0), "epoch": epoch, "best_val_score": best, "vocab": full.itow,
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
-                         "ss_prob_history": {}, "reward_history": dict(trainer.reward_history)}
+                         "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history)}
             with open(os.path.join(save_dir, "infos_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(infos, f)
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:

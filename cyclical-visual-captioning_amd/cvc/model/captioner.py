@@ -72,6 +72,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.decoder_num_layers = 2
         self.localizer_num_layers = 1
         self.rnn_size = opts.rnn_size
+        # scheduled sampling (Bengio et al. 2015): the share of loop A's inputs that are the model's own sampled words instead of the
+        # ground truth; read by Trainer.train_step_prepared, set per epoch by cvc.main (cvc.trainer.ss_prob_at).  0 = teacher forcing
         self.ss_prob = 0.0
         self.iou_threshold = 0.5
 
@@ -186,12 +188,16 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask,
-                sample_idx, pnt_mask, lang_eval=False, teacher_forcing=False):
-        """reference :175-194"""
+                sample_idx, pnt_mask, lang_eval=False, teacher_forcing=False, ss_inputs=None):
+        """reference :175-194.  ss_inputs [B * seq_per_img, T] int64 (column 0 = BOS; ss_rollout's result): loop A embeds these words
+        instead of gt_caption[:, :T] -- scheduled sampling; targets, label glue, the grounder's class inputs and loops B / C are the
+        ground truth's.  None: teacher forcing, as always."""
         F_.new_step()
         if lang_eval is False or teacher_forcing:
             return self._forward_3_loops(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes,
-                                         region_feats, frm_mask, sample_idx, pnt_mask)
+                                         region_feats, frm_mask, sample_idx, pnt_mask, ss_inputs)
+        if ss_inputs is not None:
+            raise RuntimeError("forward: ss_inputs are the training pass's (lang_eval=False)")
         return self._sample(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats,
                             frm_mask, sample_idx, pnt_mask)
 
@@ -210,7 +216,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         return fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask
 
     def _forward_3_loops(self, segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats,
-                         frm_mask, sample_idx, pnt_mask):
+                         frm_mask, sample_idx, pnt_mask, ss_inputs=None):
         """reference :196-382"""
         batch_size = proposals.size(0)
         num_rois = proposals.size(1)
@@ -235,7 +241,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             # bbox_target (a clone nobody reads, misc/utils.py:363-371) is not reproduced
             roi_labels, frm_mask_output, step_fmask = hip.label_glue(overlaps, mask_boxes[:, 0, :, tgt_steps], frm_mask, pnt_mask)
             return self._forward_after_glue(gt_caption, input_seq, fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats,
-                                            g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss)
+                                            g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss, ss_inputs)
         bm = mask_boxes[:, :, :, tgt_steps]                                           # [B, seq_per_img, K, T]
         ov = overlaps.unsqueeze(1).masked_fill(bm[:, 0].permute(0, 2, 1).unsqueeze(2).expand(B, T, num_rois, -1), 0)
         roi_labels = ov.max(3)[0] > 0.5                                                # [B, T, N]   (utils.bbox_target)
@@ -249,20 +255,25 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         frm_mask_output = torch.cat((frm_on_prop.new_zeros(B, T, 1), frm_on_prop), dim=2) | pnt_mask.bool().unsqueeze(1)
         step_fmask = frm_mask_output[:, :, 1:].permute(1, 0, 2).contiguous()           # [T, B, N]
         return self._forward_after_glue(gt_caption, input_seq, fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats,
-                                        g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss)
+                                        g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss, ss_inputs)
 
     def _forward_after_glue(self, gt_caption, input_seq, fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, g_pool_feats,
-                            region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss):
-        """_forward_3_loops from loop A on (reference :242-382)"""
+                            region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss, ss_inputs=None):
+        """_forward_3_loops from loop A on (reference :242-382).  ss_inputs: loop A's input words (scheduled sampling); loop C
+        reconstructs from the ground truth's either way."""
         T = self.seq_length
         B = gt_caption.size(0)
         num_rois = pool_feats.size(1)
+        if ss_inputs is not None and (tuple(ss_inputs.shape) != (B, T) or ss_inputs.dtype != torch.int64):
+            raise RuntimeError(f"forward: ss_inputs must be int64 [B * seq_per_img, T] = [{B}, {T}], got {ss_inputs.dtype} "
+                               f"{tuple(ss_inputs.shape)}")
         # ---- Loop A: teacher-forced decode (sequential: LSTM recurrence)            reference :242-270
-        emb_all = self._embed(gt_caption[:, :T], "emb_a")                            # [B, T, E], one launch
+        emb_all = self._embed(gt_caption[:, :T] if ss_inputs is None else ss_inputs, "emb_a")      # [B, T, E], one launch
         loops = self._loop_plan(B, fc_feats)
         if loops is not None:
             return self._forward_loops_driven(loops, emb_all, gt_caption, input_seq, fc_feats, conv_feats, p_conv_feats, pool_feats,
-                                              p_pool_feats, g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss)
+                                              p_pool_feats, g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss,
+                                              mixed=ss_inputs is not None)
         state = self._init_step_state(B)
         outputs, masked_attn = [], []
         # one unbind per tensor instead of T selects: a select's backward is a zero-filled [B, T, E] tensor plus an
@@ -311,7 +322,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
 
         # ---- Loop C: reconstruct from the localized regions (sequential)             reference :348-362
         state = self._init_step_state(B)
-        emb_all_c = self._embed(gt_caption[:, :T], "emb_c") if self.training else emb_all      # fresh dropout mask in training
+        # fresh dropout mask in training; with scheduled-sampling inputs emb_all is not the ground truth's
+        emb_all_c = self._embed(gt_caption[:, :T], "emb_c") if (self.training or ss_inputs is not None) else emb_all
         rec_outputs = []
         emb_steps_c, pool_steps, conv_steps = emb_all_c.unbind(1), loc_pool.unbind(1), loc_conv.unbind(1)
         # loop C knows even more of its inputs beforehand: the localized context of every step (loop B's output)
@@ -355,9 +367,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         return (hip.ATTN_ADDITIVE if additive else hip.ATTN_DOT, 1.0 if additive else 1.0 / float(sa.temp), specs[0], specs[1])
 
     def _forward_loops_driven(self, plan, emb_all, gt_caption, input_seq, fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats,
-                              g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss):
+                              g_pool_feats, region_mask, step_fmask, frm_mask_output, roi_labels, cls_loss, mixed=False):
         """_forward_3_loops from loop A on (reference :242-382) with loops A and C as one autograd node each; rows of the loops'
-        outputs are t-major (t * B + b), so the vocabulary head and its criterion run on t-major rows too."""
+        outputs are t-major (t * B + b), so the vocabulary head and its criterion run on t-major rows too.  mixed: emb_all embeds
+        scheduled-sampling inputs, so loop C embeds the ground truth itself."""
+        emb_gt = None if mixed else emb_all
         from .. import train_loops
         attn_kind, inv_temp, drop_a, drop_c = plan
         B, T, R = emb_all.shape[0], self.seq_length, self.rnn_size
@@ -393,7 +407,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             # and C come FIRST, fed the argmax words of the head's arithmetic, and loop A's outputs pass through loop C's graph node
             # -- its backward then holds both loops' output gradients and runs their back-propagation as one pass (cvc.train_loops._Loop).
             done, output_seq = head
-            out_c, out_a, fm = self._loops_b_c(arenas, groups, output_seq, gt_caption, emb_all, fc_in, conv_feats, p_conv_feats, pool_feats,
+            out_c, out_a, fm = self._loops_b_c(arenas, groups, output_seq, gt_caption, emb_gt, fc_in, conv_feats, p_conv_feats, pool_feats,
                                                p_pool_feats, region_mask, attn_kind, drop_c, joint=[(p_[0], p_[1]) for p_ in parts])
         att2_weights = fm.transpose(0, 1)                                             # [B, T, N] pre-softmax (:273)
 
@@ -415,7 +429,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
         if out_c is None:
-            out_c = self._loops_b_c(arenas, groups, output_seq, gt_caption, emb_all, fc_in, conv_feats, p_conv_feats, pool_feats, p_pool_feats,
+            out_c = self._loops_b_c(arenas, groups, output_seq, gt_caption, emb_gt, fc_in, conv_feats, p_conv_feats, pool_feats, p_pool_feats,
                                     region_mask, attn_kind, drop_c)
         lm_recon_loss = self.xe_criterion.from_head(out_c.view(T * B, R), self.logit, target, t_major=True)
         return (lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1), lm_recon_loss.reshape(1))
@@ -425,12 +439,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         """the argmax cut, loop B (localize, all T in one attention call; reference :313-338) and loop C (reconstruct from the
         localized regions; reference :348-362).  Loop B and the embeddings are one call over the whole batch; loop C runs once per
         group of <= 64 clips (cvc.train_loops.clip_groups).  -> out_c [T, B, R], or (out_c, loop A's out, loop A's fm) with `joint`
-        (per group: loop A's (out, fm) of that group)"""
+        (per group: loop A's (out, fm) of that group).  emb_all: the embedded ground-truth inputs, reused in eval mode; None =
+        embed them here (loop A ran on other inputs)"""
         from .. import train_loops
         dc, T = self.decoder_core, self.seq_length
         loc_emb = self._embed(output_seq, "emb_b")                                   # [B, T, E]
         ctx_all = self.localizer_core.forward_all_steps_sum(loc_emb, conv_feats, p_conv_feats, pool_feats, p_pool_feats, region_mask)
-        emb_all_c = self._embed(gt_caption[:, :T], "emb_c") if self.training else emb_all      # fresh dropout mask in training
+        emb_all_c = self._embed(gt_caption[:, :T], "emb_c") if (self.training or emb_all is None) else emb_all   # fresh dropout mask in training
         one = len(groups) == 1
         outs = []
         for g, (b0, b1) in enumerate(groups):
@@ -542,7 +557,76 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self._decode_cache = None
         self._engine_cache = None
         self._score_cache = None
+        self._ss_cache = None
         hip.bump_weights_generation()            # the encoder's packed GRU / dense operands are keyed on it (cvc/gru.py, cvc/dense.py)
+
+    def refresh_decode_weights(self):
+        """After a parameter update IN PLACE (an optimizer step, a replayed training graph): keep the cached decode binding and the
+        cached engines -- launch lists, captured graphs -- and recompute the binding's derived operands into their storage
+        (DecodeWeights.refresh()) instead of dropping everything as invalidate_decode_cache() does.  A parameter whose storage moved
+        (load_state_dict into new tensors, .to()) cannot be refreshed: that falls back to invalidation.  Used by the
+        scheduled-sampling step, which decodes on every step; the encoder's packed operands follow the weights generation as ever."""
+        cached = getattr(self, "_decode_cache", None)
+        if cached is None:
+            return self.invalidate_decode_cache()
+        params = [p for _, p in sorted(self.state_dict(keep_vars=True).items())]
+        if tuple(p.data_ptr() for p in params) != tuple(k[0] for k in cached[0]):
+            return self.invalidate_decode_cache()
+        cached[1].refresh()
+        self._decode_cache = (tuple((p.data_ptr(), p._version) for p in params), cached[1])
+        for slot in ("_engine_cache", "_score_cache", "_ss_cache"):
+            ent = getattr(self, slot, None)
+            if ent is not None:
+                ent[1].weights_refreshed()
+        hip.bump_weights_generation()
+
+    # ------------------------------------------------------------------ scheduled sampling: the rollout
+    @torch.no_grad()
+    def ss_rollout(self, encoded, gt_caption, prob: float, temperature: float = 1.0, seed: int = 0):
+        """Loop A's inputs of a scheduled-sampling step: one decode of the cached MIXED engine (DecodeEngine mix=True, sample_n =
+        seq_per_img) over the batch's ground-truth captions -- at every position the word fed on is the model's own sample (drawn
+        from softmax(logits / temperature) without UNK, as the sampling engine draws) with probability `prob`, else the ground
+        truth's.  No autograd, eval() semantics (dropout off), no host read-back; the engine is re-seeded with `seed` (its first
+        decode after that draws with call = 1).
+        encoded: encode_clips()'s result; gt_caption: the batch's [B, n, >= T] (or [B * seq_per_img, T]) int64 captions.
+        -> ss_inputs [B * seq_per_img, T] int64 = cat(BOS, inputs_next[:, :T - 1]); the engine (ss_engine()) keeps took, drawn,
+        given_logprob of the decode."""
+        T, S = self.seq_length, self.seq_per_img
+        fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
+        if gt_caption.dim() == 3:
+            gt_caption = gt_caption[:, :S, :T].reshape(-1, T)
+        given = gt_caption[:, :T].contiguous()
+        was_training = self.training
+        self.eval()
+        try:
+            feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
+                         pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
+            temp = float(getattr(self.opts, "softmax_temp", 1.0))
+            weights = self.decode_weights()
+            key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), temp, T, self.use_hip_graph,
+                   float(temperature), S)
+            cached = getattr(self, "_ss_cache", None)
+            if cached is not None and cached[0] == key:
+                engine = cached[1]
+                engine.load_features(feats)
+            else:
+                engine = DecodeEngine(weights, feats, T, self.unk_idx, inv_temp=1.0 / temp, own_features=True, sample_n=S,
+                                      temperature=float(temperature), seed=seed, mix=True)
+                if self.use_hip_graph:
+                    engine.capture()
+                self._ss_cache = (key, engine)
+            engine.load_captions(given)
+            engine.set_mix_prob(prob)
+            engine.seed(seed)
+            inputs_next = engine.run()[0]
+            return torch.cat((inputs_next.new_zeros(inputs_next.size(0), 1), inputs_next[:, :T - 1]), 1)
+        finally:
+            self.train(was_training)
+
+    def ss_engine(self):
+        """the cached mixed engine of the last ss_rollout (None before the first, and after invalidate_decode_cache())"""
+        ent = getattr(self, "_ss_cache", None)
+        return None if ent is None else ent[1]
 
     @torch.no_grad()
     def _sample(self, segs_feat, seq, proposals, gt_caption, num, mask_boxes, gt_boxes, region_feats, frm_mask, sample_idx,

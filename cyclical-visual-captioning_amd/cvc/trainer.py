@@ -46,6 +46,14 @@ def bucket_len(n: int, full: int, buckets: int = SHAPE_BUCKETS) -> int:
     return min(full, -(-n // step) * step)
 
 
+def ss_prob_at(epoch: int, start: int, increase_every: int = 5, increase_prob: float = 0.05, max_prob: float = 0.25) -> float:
+    """The scheduled-sampling share of an epoch: 0 before epoch `start` (and always with start < 0), then
+    min(max_prob, increase_prob * ((epoch - start) // increase_every)) -- a staircase that starts at 0 and is capped."""
+    if start < 0 or epoch < start:
+        return 0.0
+    return float(min(max_prob, increase_prob * ((epoch - start) // max(int(increase_every), 1))))
+
+
 def _shape_key(b) -> tuple:
     out = []
     for k in sorted(b):
@@ -105,6 +113,11 @@ class Trainer:
         self._scst_steps = 0
         self.last_scst = None
         self.reward_history = {}      # epoch -> the mean reward of every display interval
+        # ---- scheduled sampling (train_step_prepared while model.ss_prob > 0): rollout temperature, seed of step k = ss_seed + k
+        self.ss_temperature = float(getattr(opts, "ss_temperature", 1.0))
+        self.ss_seed = int(getattr(opts, "ss_seed", 1))
+        self._ss_steps = 0
+        self.last_ss = None
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -136,9 +149,9 @@ class Trainer:
                     gt_bboxs=to(bboxs), mask_bboxs=to(box_mask), ppls_feat=to(region_feat), mask_frms=to(frm_mask),
                     sample_idx=to(sample_idx).type_as(to(iseq)), pnt_mask=pnt_mask, seg_id=seg_id)
 
-    def _call(self, b, lang_eval=False):
+    def _call(self, b, lang_eval=False, **kw):
         return self.model(b["segs_feat"], b["input_seqs"], b["gt_seqs"], b["num"], b["ppls"], b["gt_bboxs"], b["mask_bboxs"],
-                          b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"], lang_eval)
+                          b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"], lang_eval, **kw)
 
     def loss_mix(self, out):
         """trainer.py:92-109"""
@@ -167,10 +180,45 @@ class Trainer:
         """One optimisation step on a batch that already is on the device (see cvc.prefetch.DevicePrefetcher)."""
         if self.opts.att_model != 'cyclical':
             raise ValueError('Unknown att_model: {}'.format(self.opts.att_model))
+        if float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0:
+            return self._ss_step_prepared(b)
         out = self._call(b)
         loss, lm, att2, cls, rec = self.loss_mix(out)
         self._backward_and_update(loss)
         self._weights_changed()
+        return loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach()
+
+    def _ss_step_prepared(self, b):
+        """The scheduled-sampling step (Bengio et al. 2015; model.ss_prob > 0): the encoder once in eval mode without autograd, one
+        decode of the cached mixed engine over the ground-truth captions (model.ss_rollout, seed ss_seed + step: every position feeds
+        on the model's own sample with probability ss_prob, else the ground truth's word), then the ordinary cyclical pass with those
+        words as loop A's inputs, the update, and model.refresh_decode_weights() -- the engine and its graph survive the update.
+        The rollout samples from the eval-mode policy without UNK, as the sampling engine does.  Runs eagerly; no host read-back
+        between the rollout and optimizer.step().  self.last_ss keeps the step's inputs, took, given_logprob, seed and the share of
+        sampled inputs (a device scalar)."""
+        model = getattr(self.model, "module", self.model)
+        seed = self.ss_seed + self._ss_steps
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                enc = model.encode_clips(b["segs_feat"], b["ppls"], b["num"], b["mask_bboxs"], b["ppls_feat"], b["gt_bboxs"], b["mask_frms"],
+                                         b["sample_idx"], b["pnt_mask"])
+                ss_inputs = model.ss_rollout(enc, b["gt_seqs"], float(model.ss_prob), self.ss_temperature, seed)
+                eng = model.ss_engine()
+                took = eng.took.t().clone()                               # [rows, T]; column t decided the input of step t + 1
+                given_logprob = eng.given_logprob.t().clone()
+        finally:
+            model.train(was_training)
+        out = self._call(b, ss_inputs=ss_inputs)
+        loss, lm, att2, cls, rec = self.loss_mix(out)
+        self._backward_and_update(loss)
+        model.refresh_decode_weights()
+        T = took.size(1)
+        share = took[:, :T - 1].float().mean() if T > 1 else took.new_zeros((), dtype=torch.float32)
+        self.last_ss = dict(inputs=ss_inputs, took=took, given_logprob=given_logprob, seed=seed, share=share,
+                            prob=float(model.ss_prob))
+        self._ss_steps += 1
         return loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach()
 
     def _backward_and_update(self, loss, set_to_none=True):
@@ -482,12 +530,14 @@ class Trainer:
 
     # ------------------------------------------------------------------ epoch loops
     def train(self, epoch, tb_logger=None):
-        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward")}
+        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled")}
         self.model.train()
         end = time.time()
         n_steps = len(self.train_loader) - 1                 # the reference drops the last batch (:55)
         scst = self.scst_after >= 0 and epoch >= self.scst_after     # self-critical epochs: eager steps (scst_step_prepared)
-        graphed = self.graph_capable() and not scst
+        # scheduled-sampling epochs (model.ss_prob > 0, set per epoch by cvc.main): eager steps with a rollout in front
+        ss = not scst and float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0
+        graphed = self.graph_capable() and not scst and not ss
         self._active_buckets = self.shape_buckets if graphed else 0       # (read by _prepare, which the prefetcher calls)
         # batch k+1 is staged into HBM on a side stream while step k runs
         batches = DevicePrefetcher(self.train_loader, lambda raw: self._prepare(raw, True), self.device, limit=n_steps)
@@ -524,6 +574,9 @@ class Trainer:
                 meters["reward"].update(sums[5] / pending, n * pending)
                 meters["reward"].val = cur[5]
                 self.reward_history.setdefault(epoch, []).append(sums[5] / pending)
+            if ss:                                    # (a sixth element: the share of loop A's inputs that were sampled words)
+                meters["sampled"].update(sums[5] / pending, n * pending)
+                meters["sampled"].val = cur[5]
             for name, i in (("lm", 1), ("attn", 2), ("cls", 3), ("recon", 4)):
                 meters[name].update(sums[i] / pending, n * pending)
                 meters[name].val = cur[i]
@@ -543,6 +596,8 @@ class Trainer:
                     res = torch.stack([s_loss, s_loss, zero, zero, zero, s_reward.to(s_loss.dtype)])
                 elif graphed:
                     res = self.train_step_bucketed(b)
+                elif ss:                          # (a sixth element: the step's share of sampled inputs)
+                    res = torch.stack([x.reshape(()) for x in self.train_step_prepared(b)] + [self.last_ss["share"].to(torch.float32)])
                 else:
                     res = torch.stack([x.reshape(()) for x in self.train_step_prepared(b)])
                 acc = res.clone() if acc is None else acc.add_(res)
@@ -558,7 +613,8 @@ class Trainer:
                           'Cls Loss {c.val:.4f} ({c.avg:.4f})\tRecon Loss {r.val:.4f} ({r.avg:.4f})'.format(
                               epoch, step, n_steps, b=meters["batch"], d=meters["data"], l=meters["lm"], a=meters["attn"],
                               c=meters["cls"], r=meters["recon"]) +
-                          ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else ''))
+                          ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else '') +
+                          ('\tSampled {s.val:.3f} ({s.avg:.3f})'.format(s=meters["sampled"]) if ss else ''))
                 else:
                     if deferred and pending >= KEEP_MAX:
                         flush()

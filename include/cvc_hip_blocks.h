@@ -157,6 +157,21 @@ int cvc_sample_select_parts(const float* parts, int nparts, long long part_strid
                             float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
                             cvc_stream_t stream);
 int cvc_sample_advance(uint32_t* rng_state, cvc_stream_t stream);
+/* Scheduled sampling (csrc/mix.hip; the MIX form of the kernel in csrc/sample_select.h): cvc_sample_select_parts, then a per-row
+ * coin decides whether the drawn or a GIVEN word is written as the next step's input.
+ *   drawn[r], logprob[r] = word and logprob of cvc_sample_select_parts from the same arguments, bit for bit
+ *   h       = cvc_drop_hash(seed_lo, seed_hi, call, CVC_MIX_SITE + t, r),  u = ((h >> 9) + 0.5) * 2^-23
+ *   took[r] = u < *mix_prob (exact in fp32; 0 never takes, 1 always takes); mix_prob: one float of device memory, read by the kernel
+ *   g       = given[r * given_stride] if that lies in [0, V), else 0;   word[r * word_stride] = took ? drawn : g
+ *   given_logprob[r] = z[r, g] - logsumexp_v z[r, v], the bits of cvc_forced_select_parts (a given word outside [0, V): NaN)
+ * drawn, took, given_logprob are nullable.  The checks of cvc_sample_select_parts; NULL given / mix_prob, given_stride < 1:
+ * CVC_E_BADARG.  CVC_MIX_SITE + t is disjoint from CVC_SAMPLE_SITE + t' and from the dropout sites (cvc/dropout.py) for t, t' < 64.
+ * Bitwise deterministic. */
+#define CVC_MIX_SITE 0x4D000000u
+int cvc_mixed_select_parts(const float* parts, int nparts, long long part_stride, const float* bias, int M, int V, int unk_idx,
+                           float inv_tau, const uint32_t* rng_state, int t, int64_t* word, int word_stride, float* logprob,
+                           const int64_t* given, int given_stride, const float* mix_prob, int64_t* drawn, uint8_t* took,
+                           float* given_logprob, cvc_stream_t stream);
 /* The same with top-k / nucleus (top-p) truncation: z, s, the noise, the hash counters and logprob are those of
  * cvc_sample_select_parts; the arg-max runs over a candidate set C2 only.
  *   C0 = { v < V, v != unk_idx }
