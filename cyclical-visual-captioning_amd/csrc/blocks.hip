@@ -84,6 +84,7 @@ const Entry table[] = {
     CVC_B(cvc_keys_finalize),
     CVC_B(cvc_cider_d),
     CVC_B(cvc_scst_weights),
+    CVC_B(cvc_caption_overlap),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

@@ -4,6 +4,7 @@
 // cvc_cider_d: ONE WAVE per candidate row, lane p owns the n-grams (n = 1..4) that start at position p -- hence T <= 63.
 //   A caption's words are its ids up to and including the first 0 (L words, 1 <= L <= T; all T without a 0).  An n-gram is one exact
 //   64-bit key: 16 bits per word holding id + 1, first word in the highest bits, unused positions 0 (the order is part of the key).
+//   (Loader and keys: csrc/caption_ngrams.h, with the end mark counted.)
 //   Words (as id + 1, 0 past the caption's end) and keys go to LDS; a key's count is the number of the caption's positions that
 //   hold it, and every distinct n-gram is counted once, by the lane of its first occurrence.  idf comes from a binary search of
 //   the sorted table (precomputed on the host in fp64: no logf here), an n-gram that is not in it has idf_unseen = ln N_doc.
@@ -14,42 +15,14 @@
 // cvc_scst_weights: the advantage of every row (leave-one-out mean of the clip's other samples, or a given baseline) spread over the
 //   caption's steps up to and including the first 0 (cvc.misc.utils._text_mask), one thread per row.
 #include "cvc_common.h"
+#include "caption_ngrams.h"
 #include <math.h>
 
 namespace {
 
-constexpr int MAXT = 63;
-
-// the caption's words into sw[0 .. 67] as id + 1 (0 from position L on) -> L
-__device__ __forceinline__ int load_caption(const int64_t* cap, int T, int lane, uint32_t* sw) {
-    const int64_t w = lane < T ? cap[lane] : 1;
-    const unsigned long long eos = __ballot(lane < T && w == 0);
-    const int L = eos != 0ull ? (int)__builtin_ctzll(eos) + 1 : T;
-    __syncthreads();                      // the previous caption's readers are done
-    sw[lane] = lane < L ? (uint32_t)((w + 1) & 0xffff) : 0u;
-    if (lane < 4) sw[64 + lane] = 0u;
-    __syncthreads();
-    return L;
-}
-
-__device__ __forceinline__ unsigned long long ngram_key(const uint32_t* sw, int lane, int n) {
-    unsigned long long k = 0ull;
-    for (int i = 0; i < n; ++i) k |= (unsigned long long)sw[lane + i] << (48 - 16 * i);
-    return k;
-}
-
-// how many of buf[0 .. npos) hold `key`; *first: none of them before `lane`
-__device__ __forceinline__ int count_key(const unsigned long long* buf, int npos, unsigned long long key, int lane, bool* first) {
-    int c = 0;
-    bool f = true;
-    for (int q = 0; q < npos; ++q) {
-        const bool same = buf[q] == key;
-        c += same ? 1 : 0;
-        f = f && !(same && q < lane);
-    }
-    *first = f;
-    return c;
-}
+using cvc_caption::MAXT;
+using cvc_caption::ngram_key;
+using cvc_caption::count_key;
 
 __device__ __forceinline__ float idf_of(const unsigned long long* keys, const float* idf, int G, float idf_unseen, unsigned long long key) {
     int lo = 0, hi = G;
@@ -69,7 +42,7 @@ __global__ __launch_bounds__(64) void cider_d_kernel(const int64_t* cand, const 
     __shared__ unsigned long long rk[64];          // the current reference's keys of the current order
     const int row = blockIdx.x, lane = threadIdx.x;
     const int clip = row / per_clip;
-    const int Lc = load_caption(cand + (size_t)row * T, T, lane, sw);
+    const int Lc = cvc_caption::load_caption<true>(cand + (size_t)row * T, T, lane, sw);
     float norm_c[4];
 #pragma unroll
     for (int n = 1; n <= 4; ++n) {
@@ -90,7 +63,7 @@ __global__ __launch_bounds__(64) void cider_d_kernel(const int64_t* cand, const 
     nr = nr < 0 ? 0 : (nr > Rmax ? Rmax : nr);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int r = 0; r < nr; ++r) {
-        const int Lr = load_caption(refs + ((size_t)clip * Rmax + r) * T, T, lane, sw);
+        const int Lr = cvc_caption::load_caption<true>(refs + ((size_t)clip * Rmax + r) * T, T, lane, sw);
         const float dl = (float)(Lc - Lr);
         const float gauss = expf(-(dl * dl) * inv_2s2);
 #pragma unroll

@@ -268,6 +268,8 @@ SIGNATURES = {
     # self-critical training: CIDEr-D reward and per-token loss weights (csrc/cider.hip; building blocks)
     "cvc_cider_d": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P],
     "cvc_scst_weights": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P],
+    # token-overlap caption metrics: BLEU statistics, sentence BLEU, ROUGE-L (csrc/overlap.hip; building block)
+    "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -312,7 +314,7 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts"}
+    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1147,6 +1149,28 @@ def scst_weights(reward: torch.Tensor, base: Optional[torch.Tensor], per_clip: i
     _check(lib().cvc_scst_weights(_dev(reward, name="reward"), _dev(base, name="base"), rows, int(per_clip), _dev(cand, torch.int64, "cand"),
                                   T, 1 if t_major else 0, _dev(adv), _dev(w), _stream()), "cvc_scst_weights")
     return adv, w
+
+
+# --------------------------------------------------------------------------- token-overlap caption metrics (csrc/overlap.hip)
+def caption_overlap(cand: torch.Tensor, refs: torch.Tensor, nref: torch.Tensor, per_clip: Optional[int] = None, want_lcs: bool = False):
+    """cand [rows, T] int64; refs [clips, Rmax, T] int64 (per_clip = rows / clips consecutive candidates per clip); nref [clips] int32.
+    -> stats [rows, 10] int32 (correct_1..4, guess_1..4, cand_len, ref_len), lcs [rows, Rmax] int32 or None, bleu [rows, 4], rouge [rows]"""
+    if cand.dim() != 2 or refs.dim() != 3 or refs.shape[2] != cand.shape[1] or refs.shape[0] < 1 or nref.numel() != refs.shape[0]:
+        raise RuntimeError(f"cvc.hip.caption_overlap: cand {tuple(cand.shape)}, refs {tuple(refs.shape)}, nref {tuple(nref.shape)} do not fit")
+    rows, T = cand.shape
+    clips, Rmax = refs.shape[0], refs.shape[1]
+    per_clip = rows // clips if per_clip is None else int(per_clip)
+    if per_clip < 1 or per_clip * clips != rows:
+        raise RuntimeError(f"cvc.hip.caption_overlap: {rows} candidate rows are not {per_clip} per clip of {clips} clips")
+    dev = cand.device
+    stats = torch.empty(rows, 10, device=dev, dtype=torch.int32)
+    lcs = torch.empty(rows, Rmax, device=dev, dtype=torch.int32) if want_lcs else None
+    bleu = torch.empty(rows, 4, device=dev, dtype=torch.float32)
+    rouge = torch.empty(rows, device=dev, dtype=torch.float32)
+    _check(lib().cvc_caption_overlap(_dev(cand, torch.int64, "cand"), _dev(refs, torch.int64, "refs"), _dev(nref, torch.int32, "nref"),
+                                     rows, T, per_clip, Rmax, _dev(stats, torch.int32), _dev(lcs, torch.int32), _dev(bleu), _dev(rouge),
+                                     _stream()), "cvc_caption_overlap")
+    return stats, lcs, bleu, rouge
 
 
 # --------------------------------------------------------------------------- tile path (rows > 64), csrc/gemm_tile.hip

@@ -67,6 +67,13 @@ def build_parser():
     parser.add_argument("--scst_seed", type=int, default=1, help="seed of the rollouts' noise")
     parser.add_argument("--scst_dropout", action="store_true",
                         help="keep the training dropout on in the self-critical gradient pass (default: off, the policy that was sampled)")
+    parser.add_argument("--scst_reward", type=str, default="cider:1",
+                        help="the self-critical reward as name:weight pairs over cider, bleu1..bleu4, rougel (cvc.metrics), e.g. "
+                             "cider:1,bleu4:0.5,rougel:0.5; the weights apply to the raw scales: CIDEr-D in [0, 10], the others in [0, 1]")
+    # validation scores without external toolkits (Trainer(device_metrics=True); cvc.metrics)
+    parser.add_argument("--val_metrics", choices=("none", "device"), default="none",
+                        help="device: BLEU-1..4, ROUGE-L and CIDEr-D of the validation captions by word id, scored on the GPU; they "
+                             "drive ReduceLROnPlateau and model-best.pth (not the toolkits' numbers: no PTB tokenizer)")
     # scheduled sampling (Trainer.train_step_prepared with model.ss_prob > 0): loop A fed the model's own sampled words
     parser.add_argument("--scheduled_sampling_start", type=int, default=-1,
                         help="from this epoch on a growing share of the decoder's training inputs are its own sampled words; -1 = never")
@@ -142,6 +149,8 @@ def main(argv=None, sample=None, score=None):
             or not 0 <= opt.scheduled_sampling_max_prob <= 1):
         raise SystemExit("--scheduled_sampling_increase_every must be >= 1, --scheduled_sampling_temperature > 0, "
                          "--scheduled_sampling_increase_prob >= 0 and --scheduled_sampling_max_prob in [0, 1]")
+    from .metrics import parse_reward_weights
+    opt.scst_reward_weights = parse_reward_weights(opt.scst_reward)                                       # (Trainer reads these)
     opt.ss_temperature, opt.ss_seed = opt.scheduled_sampling_temperature, opt.scheduled_sampling_seed     # (Trainer reads these)
     opt.force_word_ids = word_ids(opt.force_words, opt.wtoi, "--force_words")
     if len(opt.force_word_ids) > 3 or not 0 <= opt.force_detected <= 3 or (opt.force_word_ids and opt.force_detected):
@@ -183,7 +192,7 @@ def main(argv=None, sample=None, score=None):
     # default: torch.distributed on gloo is the control plane only), whose collectives are captured into the step's HIP graph
     comm = exchange_comm() if (world > 1 and opt.dist_backend == "rccl") else None
     reducer = GradReducer(model.named_parameters(), comm=comm)
-    trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer)
+    trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device")
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
@@ -218,7 +227,7 @@ def main(argv=None, sample=None, score=None):
         stats = trainer.eval(epoch, tb)
         if opt.inference_only:
             break
-        score = stats.get("CIDEr")                            # None without an external scorer
+        score = stats.get("CIDEr")                            # None without a scorer (--val_metrics device, or an external one)
         if world > 1:                                         # only rank 0 scores: every rank must step its LR schedule alike
             box = [score]
             torch.distributed.broadcast_object_list(box, src=0)

@@ -5,7 +5,8 @@ step.  Reference bugs are not copied: `next(it)` instead o
 reconstruction-loss meter is updated, grounding stats are only logged when they exist.
 
 Caption / grounding scoring lives in external toolkits the reference vendors as (empty)
-submodules; pass `scorer(predictions, grd_output, opts) -> dict` to get language stats.
+submodules; pass `scorer(predictions, grd_output, opts) -> dict` to get language stats, and / or
+`device_metrics=True` for BLEU, ROUGE-L and CIDEr-D by word id on the device (cvc.metrics).
 """
 from __future__ import annotations
 
@@ -78,7 +79,7 @@ def _copy_into(static, b):
 
 
 class Trainer:
-    def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None):
+    def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False):
         self.opts = opts
         self.dataset = dataset
         self.model = model
@@ -87,6 +88,10 @@ class Trainer:
         self.val_loader = val_loader
         self.scorer = scorer
         self.grad_reducer = grad_reducer
+        # eval(): BLEU-1..4, ROUGE-L and CIDEr-D of the decoded captions against the batches' own references, on the device
+        # (cvc.metrics.DeviceScorer); off: eval is what it was
+        self.device_metrics = bool(device_metrics)
+        self._val_cider = None        # cvc.cider.CiderD over the validation loader's captions, built at the first eval
         self.device = next(model.parameters()).device
         self._graph = None            # HIP-graph state of train_step_graphed
         # ---- train(): one captured graph per (bucketed) batch shape
@@ -112,6 +117,8 @@ class Trainer:
         self._cider = None            # cvc.cider.CiderD over the training captions, built at the first self-critical step
         self._scst_steps = 0
         self.last_scst = None
+        # the reward mix {name: weight} (cvc.metrics.REWARD_NAMES; cvc.main --scst_reward); None or cider alone at 1: CIDEr-D as ever
+        self.scst_reward_weights = getattr(opts, "scst_reward_weights", None)
         self.reward_history = {}      # epoch -> the mean reward of every display interval
         # ---- scheduled sampling (train_step_prepared while model.ss_prob > 0): rollout temperature, seed of step k = ss_seed + k
         self.ss_temperature = float(getattr(opts, "ss_temperature", 1.0))
@@ -274,16 +281,21 @@ class Trainer:
     def scst_step_prepared(self, b):
         """One self-critical optimisation step (SCST, Rennie et al. 2017) on a prepared batch: S = opts.scst_samples captions per clip
         sampled from the model at opts.scst_temperature (the cached decode binding, DecodeEngine's sampling mode), scored against the
-        clip's ground-truth captions with CIDEr-D on the device (cvc.cider), and the REINFORCE gradient of
+        clip's ground-truth captions with CIDEr-D on the device (cvc.cider) -- or, with opts.scst_reward_weights, with the mix
+        sum_k w_k metric_k of CIDEr-D, BLEU-1..4 and ROUGE-L (cvc.metrics.reward_mix: raw scales, CIDEr-D in [0, 10], the others in
+        [0, 1]; fixed order, fp32 on the device; the greedy baseline is scored with the same mix) -- and the REINFORCE gradient of
         -sum adv * log p(sampled word) / sum(mask) through loop A and the vocabulary head (model.scst_loss).  Baseline: the mean
         reward of the clip's other samples (S > 1), or the reward of the greedy caption (S = 1).  The encoder runs once, without
         autograd and in eval mode; the decoder's parameters (decoder_core, embed, logit) are what the loss reaches.  Dropout is off in
         the gradient pass unless opts.scst_dropout.  No host read-back between the rollout and optimizer.step().
         The sampler leaves UNK out while log p is taken over the full vocabulary, as in the sampling engine.  Runs eagerly.
         -> (loss, mean reward, mean baseline, mean |advantage|) as device scalars; the step's samples, rewards and advantages stay
-        in self.last_scst."""
+        in self.last_scst (with a mix also reward_parts: the metrics that were weighted, per row)."""
+        from . import metrics
         model = getattr(self.model, "module", self.model)
         o = self.opts
+        mix = None if metrics.is_cider_only(self.scst_reward_weights) else self.scst_reward_weights
+        parts = None
         S, tau = int(getattr(o, "scst_samples", 5)), float(getattr(o, "scst_temperature", 1.0))
         seed = int(getattr(o, "scst_seed", 1)) + self._scst_steps          # a sampling engine is seeded when it is built: once per step
         cider = self.cider()
@@ -302,11 +314,14 @@ class Trainer:
                 seq = seq.contiguous()
                 refs = b["gt_seqs"][:, :, :T].contiguous()
                 nref = b["num"][:, 0].to(torch.int32)
-                reward = cider.score(seq, refs, nref)
+                if mix is None:
+                    reward = cider.score(seq, refs, nref)
+                else:
+                    reward, parts = metrics.reward_mix(mix, cider, seq, refs, nref)
                 base = greedy = None
                 if S == 1:
                     greedy = model._sample(*args, sample_max=1, encoded=enc, **plain)[0].contiguous()
-                    base = cider.score(greedy, refs, nref)
+                    base = cider.score(greedy, refs, nref) if mix is None else metrics.reward_mix(mix, cider, greedy, refs, nref)[0]
             if bool(getattr(o, "scst_dropout", False)):
                 model.train()
             loss, adv = model.scst_loss(enc, seq, reward, base, S)
@@ -316,6 +331,8 @@ class Trainer:
         self._weights_changed()
         self._scst_steps += 1
         self.last_scst = dict(seq=seq, logprob=logprob, reward=reward, base=base, greedy=greedy, adv=adv, seed=seed)
+        if mix is not None:
+            self.last_scst["reward_parts"] = parts
         return loss.detach(), reward.mean(), (reward - adv).mean(), adv.abs().mean()
 
     # ------------------------------------------------------------------ HIP-graph training step
@@ -656,9 +673,13 @@ class Trainer:
         o = self.opts
         ds = self.dataset
         timestamps = self._segment_timestamps()
+        dev_scorer = self._device_scorer() if (self.device_metrics and o.val_split != 'hidden_test') else None
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
                 seq, att2_weights, _ = self._call(b, True)
+                if dev_scorer is not None:                  # the references scst_step_prepared scores against; no host read
+                    T = seq.size(1)
+                    dev_scorer.add(seq.contiguous(), b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32))
                 if getattr(o, "eval_obj_grounding", False):
                     assert o.beam_size == 1, 'only support beam_size is 1'
                     self._collect_grounding(b, seq, att2_weights, grd_output)
@@ -670,6 +691,8 @@ class Trainer:
         # every rank decoded its shard of the clips; merge host-side, rank 0 writes the files and scores
         predictions, grd_output = gather_eval_outputs(predictions, grd_output)
         lang_stats = {}
+        if dev_scorer is not None:                          # (every rank: its sums are merged like the predictions)
+            lang_stats = self._merged_device_metrics(dev_scorer)
         if getattr(o, "eval_obj_grounding_gt", False):        # (every rank: its shards are merged like the predictions)
             self._eval_ground_gt(epoch, tb_logger)
         self.submission_file = self.attn_file = None
@@ -681,12 +704,35 @@ class Trainer:
         if getattr(o, "eval_obj_grounding", False):
             self.attn_file = write_grounding_json(grd_output, o)
         if self.scorer is not None:
-            lang_stats = self.scorer(predictions, grd_output, o) or {}
-            if tb_logger:
-                for k, v in lang_stats.items():
-                    tb_logger.add_scalar('eval/' + k, v, epoch)
+            lang_stats = {**lang_stats, **(self.scorer(predictions, grd_output, o) or {})}      # an external scorer's keys win
+        if tb_logger:
+            for k, v in lang_stats.items():
+                tb_logger.add_scalar('eval/' + k, v, epoch)
         self.predictions = predictions
         return lang_stats
+
+    def _device_scorer(self):
+        """a fresh cvc.metrics.DeviceScorer over the CIDEr-D table of the validation loader's own captions (document frequencies
+        over the evaluated split, as the toolkits take them); the table is built once, at the first eval"""
+        from .cider import CiderD
+        from .metrics import DeviceScorer
+        if self._val_cider is None:
+            self._val_cider = CiderD.from_dataset(self.val_loader.dataset, self.device)
+        return DeviceScorer(self._val_cider)
+
+    @staticmethod
+    def _merged_device_metrics(dev_scorer):
+        """one host read of this rank's sums; with several ranks the sums are exchanged host-side, next to gather_eval_outputs, and
+        added in rank order on every rank (more than one rank: untested)"""
+        import torch.distributed as dist
+        from .metrics import result_from_sums
+        mine = dev_scorer.sums()
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return result_from_sums(*mine)
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        stats = [sum(p[0][i] for p in parts) for i in range(10)]
+        return result_from_sums(stats, *(sum(p[j] for p in parts) for j in (1, 2, 3)))
 
     def _eval_ground_gt(self, epoch, tb_logger):
         """eval's --eval_obj_grounding_gt part: grounding on the GT sentences, kept as self.grounding_gt_stats and logged under

@@ -512,6 +512,22 @@ int cvc_cider_d(const int64_t* cand, const int64_t* refs, const int32_t* nref, i
 int cvc_scst_weights(const float* reward, const float* base, int rows, int per_clip, const int64_t* cand, int T, int t_major,
                      float* adv, float* w, cvc_stream_t stream);
 
+/* ---- token-overlap caption metrics: BLEU statistics, sentence BLEU-1..4 and ROUGE-L, one launch (csrc/overlap.hip; cvc.metrics).
+ * cand / refs / nref / per_clip / Rmax as cvc_cider_d, on the same n-gram keys -- but a caption's words here are the ids BEFORE its
+ * first 0 (the end mark is no word, what stands behind it is ignored; all T ids without a 0; L = 0 is possible).
+ *   stats [rows, 10] int32, exact: correct_1..4 (sum over the candidate's distinct n-grams of min(count_c, max_r count_r)),
+ *     guess_1..4 (max(0, Lc - n + 1)), cand_len Lc, ref_len (the counted reference length closest to Lc, the shorter on a tie; 0
+ *     without a reference).
+ *   lcs [rows, Rmax] int32 (nullable), exact: the longest-common-subsequence length against reference r; -1 in slots >= nref.
+ *   bleu [rows, 4] fp32: p_n = (correct_n + 1e-15) / (guess_n + 1e-9), BLEU_k = bp exp((sum_{n<=k} log p_n) / k), bp = 1 if
+ *     Lc >= ref_len else exp(1 - ref_len / Lc); 0 if Lc = 0 or the clip has no reference.
+ *   rouge [rows] fp32: p = max_r lcs_r / Lc, q = max_r lcs_r / Lr (Lr = 0: 0), (1 + b^2) p q / (q + b^2 p) with b = 1.2; 0 if
+ *     Lc = 0, no reference, or p q = 0.
+ * One wave per row, no atomics: a row's result is bit-reproducible and independent of the other rows.
+ * Null pointers (but lcs), rows < 1, T < 1 or T > 63, rows % per_clip != 0, Rmax < 1: CVC_E_BADARG, before any launch. */
+int cvc_caption_overlap(const int64_t* cand, const int64_t* refs, const int32_t* nref, int rows, int T, int per_clip, int Rmax,
+                        int32_t* stats, int32_t* lcs, float* bleu, float* rouge, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
