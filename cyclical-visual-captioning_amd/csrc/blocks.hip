@@ -85,6 +85,7 @@ const Entry table[] = {
     CVC_B(cvc_cider_d),
     CVC_B(cvc_scst_weights),
     CVC_B(cvc_caption_overlap),
+    CVC_B(cvc_consensus_cider),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

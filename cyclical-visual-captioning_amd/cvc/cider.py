@@ -26,6 +26,7 @@ import torch
 
 MAX_ID = 65534          # ids are stored as id + 1 in 16 bits
 MAX_T = 63              # one wave per caption, lane p owns the n-grams starting at p
+MAX_PER_CLIP = 32       # consensus selection: a clip's candidates share one workgroup's LDS
 SIGMA = 6.0
 
 
@@ -132,3 +133,18 @@ class CiderD:
             raise RuntimeError(f"CiderD.score: T = {cand.shape[1]}; the scorer takes at most T = {MAX_T}")
         return hip.cider_d(cand.contiguous(), refs.contiguous(), nref.to(torch.int32).contiguous(), self.keys, self.idf, self.idf_unseen,
                            self.sigma, want_orders=per_order)
+
+    def consensus(self, cand: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None):
+        """Consensus (minimum-Bayes-risk) selection under CIDEr-D.  cand [rows, T] int64 on the device, per_clip consecutive candidates
+        per clip; live [rows] (nullable: every row counts): rows that are neither candidates nor references.
+        -> utility [rows] fp32: the CIDEr-D of a row against the clip's other live rows as its references, with uniform weights;
+        pick [clips] int32: the first live row with the largest utility; best [clips, T] int64: that row."""
+        from . import hip
+        if self.keys is None or self.keys.device != cand.device:
+            self.to(cand.device)
+        if cand.shape[1] > MAX_T:
+            raise RuntimeError(f"CiderD.consensus: T = {cand.shape[1]}; the scorer takes at most T = {MAX_T}")
+        if int(per_clip) > MAX_PER_CLIP:
+            raise RuntimeError(f"CiderD.consensus: {int(per_clip)} candidates per clip; the selection takes at most per_clip = {MAX_PER_CLIP}")
+        return hip.consensus_cider(cand.contiguous(), int(per_clip), self.keys, self.idf, self.idf_unseen, self.sigma,
+                                   live=None if live is None else live.to(torch.int32).contiguous())

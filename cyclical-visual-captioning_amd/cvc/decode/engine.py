@@ -784,6 +784,39 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         return (seq.gather(1, o.unsqueeze(2).expand(B, beam, T)), score.gather(1, o), self.norm.gather(1, o),
                 self.final_nmet.gather(1, o) if self.forcing else o // (beam // self.groups))
 
+    def consensus(self, table):
+        """Consensus (minimum-Bayes-risk) selection among the candidates of the last run() ("Consensus
+        selection"): per clip the candidate with the highest mean CIDEr-D against the clip's other candidates as stand-in
+        references, over `table` (a cvc.cider.CiderD; csrc/consensus.hip).  A sampling engine with sample_n > 1: the n samples of
+        a clip.  A beam engine with beam_history=True: its hypotheses(), live where the score is finite.
+        -> (seq [B, T], att2_weights [B, T, N], logprob [B, T] or None for a beam, pick [B] int32 -- the index of the kept sample /
+        the kept slot --, utility [B * n] fp32), new tensors, everything selected on the device with pick (a beam's attention rows
+        by cvc_beam_backtrack_from the picked slot); no host read-back."""
+        if self.forced:
+            raise RuntimeError("DecodeEngine.consensus: a forced engine scores given words, it has no candidates to choose among")
+        if self.mix:
+            raise RuntimeError("DecodeEngine.consensus: a mix engine's rows follow given captions (scheduled sampling), they are no "
+                               "candidates of one clip")
+        if self.beam > 1 and not self.beam_hist:
+            raise RuntimeError("DecodeEngine.consensus: a beam engine needs beam_history=True (the candidates are hypotheses())")
+        if self.nq < 2:
+            raise RuntimeError("DecodeEngine.consensus: one candidate per clip -- it needs sample_n > 1 or beam > 1")
+        B, T, N, n = self.B, self.T, self.N, self.nq
+        if self.sampling:
+            cand = self.words[1:].t().contiguous()
+            utility, pick, best = table.consensus(cand, n)
+            at = torch.arange(B, device=cand.device) * n + pick
+            return (best, self.att_steps.permute(1, 0, 2).index_select(0, at), self.logprob.t().index_select(0, at), pick, utility)
+        seq, score = self.hypotheses()
+        utility, pick, _ = table.consensus(seq.reshape(B * n, T), n, live=torch.isfinite(score).reshape(-1))
+        start = pick.to(torch.int64)
+        bt_seq = torch.empty(B, T, dtype=torch.int64, device=start.device)
+        bt_att = torch.empty(B, T, N, dtype=torch.float32, device=start.device)
+        hip._check(hip.lib().cvc_beam_backtrack_from(self.words[1:].data_ptr(), self.parent.data_ptr(), self.att_steps.data_ptr(), B, n,
+                                                     T, N, start.data_ptr(), 1, bt_seq.data_ptr(), bt_att.data_ptr(), hip._stream()),
+                   "cvc_beam_backtrack_from")
+        return bt_seq, bt_att, None, pick, utility
+
     def _python_launches(self):
         if self._launches is None:
             self._keep = []

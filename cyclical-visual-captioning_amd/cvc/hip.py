@@ -270,6 +270,8 @@ SIGNATURES = {
     "cvc_scst_weights": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P],
     # token-overlap caption metrics: BLEU statistics, sentence BLEU, ROUGE-L (csrc/overlap.hip; building block)
     "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    # consensus caption selection: pairwise CIDEr-D among a clip's candidates, pick and picked row (csrc/consensus.hip; building block)
+    "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -314,7 +316,7 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap"}
+    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1171,6 +1173,30 @@ def caption_overlap(cand: torch.Tensor, refs: torch.Tensor, nref: torch.Tensor, 
                                      rows, T, per_clip, Rmax, _dev(stats, torch.int32), _dev(lcs, torch.int32), _dev(bleu), _dev(rouge),
                                      _stream()), "cvc_caption_overlap")
     return stats, lcs, bleu, rouge
+
+
+# --------------------------------------------------------------------------- consensus caption selection (csrc/consensus.hip)
+def consensus_cider(cand: torch.Tensor, per_clip: int, keys: torch.Tensor, idf: torch.Tensor, idf_unseen: float, sigma: float = 6.0,
+                    live: Optional[torch.Tensor] = None):
+    """cand [rows, T] int64, per_clip consecutive candidates per clip; keys [G] int64 holding the table's unsigned 64-bit keys, idf [G];
+    live [rows] int32 or None (every row is live).  -> utility [rows] fp32 (CIDEr-D of the row against the clip's other live rows),
+    pick [clips] int32 (the first live row with the largest utility), best [clips, T] int64 (that row)."""
+    per_clip = int(per_clip)
+    if cand.dim() != 2 or per_clip < 1 or cand.shape[0] < 1 or cand.shape[0] % per_clip != 0 or idf.numel() != keys.numel() \
+            or (live is not None and live.numel() != cand.shape[0]):
+        raise RuntimeError(f"cvc.hip.consensus_cider: cand {tuple(cand.shape)}, per_clip {per_clip}, live "
+                           f"{None if live is None else tuple(live.shape)}, keys {tuple(keys.shape)}, idf {tuple(idf.shape)} do not fit")
+    rows, T = cand.shape
+    clips = rows // per_clip
+    G = int(keys.numel())
+    utility = torch.empty(rows, device=cand.device, dtype=torch.float32)
+    pick = torch.empty(clips, device=cand.device, dtype=torch.int32)
+    best = torch.empty(clips, T, device=cand.device, dtype=torch.int64)
+    _check(lib().cvc_consensus_cider(_dev(cand, torch.int64, "cand"), _dev(live, torch.int32, "live"), rows, T, per_clip,
+                                     _dev(keys, torch.int64, "keys") if G else None, _dev(idf, name="idf") if G else None, G,
+                                     float(idf_unseen), float(sigma), _dev(utility), _dev(pick, torch.int32), _dev(best, torch.int64),
+                                     _stream()), "cvc_consensus_cider")
+    return utility, pick, best
 
 
 # --------------------------------------------------------------------------- tile path (rows > 64), csrc/gemm_tile.hip

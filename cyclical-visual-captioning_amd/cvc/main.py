@@ -82,11 +82,19 @@ def build_parser():
     parser.add_argument("--scheduled_sampling_max_prob", type=float, default=0.25, help="up to this share")
     parser.add_argument("--scheduled_sampling_temperature", type=float, default=1.0, help="temperature of the sampled words")
     parser.add_argument("--scheduled_sampling_seed", type=int, default=1, help="seed of the sampled words' noise and of the coins")
+    # consensus (minimum-Bayes-risk) caption selection at evaluation (model._sample(consensus=...); DecodeEngine.consensus)
+    parser.add_argument("--consensus", choices=("off", "samples", "beam"), default="off",
+                        help="keep per clip the candidate with the highest mean CIDEr-D against the clip's other candidates (training "
+                             "captions' table): samples = --consensus_samples sampled captions (with --top_k / --top_p and the "
+                             "constraints as they are set), beam = the --beam_size hypotheses of beam search")
+    parser.add_argument("--consensus_samples", type=int, default=16, help="sampled candidates per clip (2 .. 32)")
+    parser.add_argument("--consensus_temperature", type=float, default=1.0, help="temperature of the sampled candidates")
+    parser.add_argument("--consensus_seed", type=int, default=1, help="seed of the sampled candidates' noise")
     return parser
 
 
 def main(argv=None, sample=None, score=None):
-    """sample: (n, temperature, seed) or (n, temperature, seed, top_k, top_p) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p) or (n, temperature, seed, top_k, top_p, consensus) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
     score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
     (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
@@ -149,6 +157,10 @@ def main(argv=None, sample=None, score=None):
             or not 0 <= opt.scheduled_sampling_max_prob <= 1):
         raise SystemExit("--scheduled_sampling_increase_every must be >= 1, --scheduled_sampling_temperature > 0, "
                          "--scheduled_sampling_increase_prob >= 0 and --scheduled_sampling_max_prob in [0, 1]")
+    if not 2 <= opt.consensus_samples <= 32 or opt.consensus_temperature <= 0:
+        raise SystemExit("--consensus_samples lies in 2 .. 32 and --consensus_temperature must be > 0")
+    if opt.consensus == "beam" and opt.beam_size < 2:
+        raise SystemExit("--consensus beam chooses among the hypotheses of beam search: it needs --beam_size > 1")
     from .metrics import parse_reward_weights
     opt.scst_reward_weights = parse_reward_weights(opt.scst_reward)                                       # (Trainer reads these)
     opt.ss_temperature, opt.ss_seed = opt.scheduled_sampling_temperature, opt.scheduled_sampling_seed     # (Trainer reads these)
@@ -196,7 +208,7 @@ def main(argv=None, sample=None, score=None):
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
-        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p"), sample[3:])))
+        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
         if comm is not None:

@@ -116,6 +116,15 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # its force_detected best-scored detection classes (cvc.misc.utils.detected_force_words)
         self.force_words = tuple(getattr(opts, "force_word_ids", None) or ())
         self.force_detected = int(getattr(opts, "force_detected", 0))
+        # consensus (minimum-Bayes-risk) selection among a clip's candidates (DecodeEngine.consensus): "off", "samples" (every decode
+        # of _sample draws consensus_samples captions per clip and keeps the consensus one) or "beam" (the hypotheses of beam search);
+        # consensus_table is the cvc.cider.CiderD the utilities are taken over (Trainer sets the training captions' table)
+        self.consensus = str(getattr(opts, "consensus", "off") or "off")
+        self.consensus_samples = int(getattr(opts, "consensus_samples", 16))
+        self.consensus_temperature = float(getattr(opts, "consensus_temperature", 1.0))
+        self.consensus_seed = int(getattr(opts, "consensus_seed", 1))
+        self.consensus_table = None
+        self.last_consensus: Optional[dict] = None
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
         self.decode_weights_dtype = getattr(opts, "decode_weights", "fp32")
         # test hook: set to a dict to receive the training pass's intermediate tensors (ground_weights, att2_weights,
@@ -635,7 +644,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
                 no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
                 beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None,
-                force_words=None, encoded=None):
+                force_words=None, encoded=None, consensus=None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -658,7 +667,24 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         C <= 3; the engine is built with beam_history=True and force_n = C, the words are loaded into it for every batch, and seq is
         the best-normed hypothesis among those that met the most forced words.
         encoded: encode_clips()'s result for this batch -- the encoder is then not run again (Trainer.scst_step: its rollouts, its
-        greedy baseline and its gradient pass read the same encoder outputs)."""
+        greedy baseline and its gradient pass read the same encoder outputs).
+        consensus (argument, else the model's attribute, read from opts.consensus; off by default): consensus (minimum-Bayes-risk)
+        selection among the clip's candidates under CIDEr-D over self.consensus_table (DecodeEngine.consensus; without a table the
+        call raises).  True: the candidates are what this call decodes -- with sample_max = 0 and sample_n > 1 the n samples of a
+        clip, the result is the picked sample per clip (seq [B, T], att2_weights [B, T, N], logprob [B, T]); with beam_size > 1 the
+        hypotheses of the beam (the engine is built with beam_history=True), the result is (seq, att2_weights, None) of the picked
+        one.  "samples": sampling whatever sample_max says, with the model's consensus_samples / consensus_temperature /
+        consensus_seed where sample_n / temperature / seed are not given, beam_size 1.  "beam": as True, beam_size > 1 required.
+        The candidates are exactly what the same call returns with consensus=False and the same seed; self.last_consensus =
+        dict(candidates, pick, utility) keeps them (seq [B * n, T] / hypotheses [B, beam, T]) with the picks [B] and the utilities
+        [B * n], device tensors."""
+        mode = self.consensus if consensus is None else consensus
+        mode = "on" if mode is True else (None if (not mode or mode == "off") else mode)
+        if mode not in (None, "on", "samples", "beam"):
+            raise RuntimeError(f"_sample: consensus must be a bool, 'off', 'samples' or 'beam', got {mode!r}")
+        if mode is not None and self.consensus_table is None:
+            raise RuntimeError("_sample: consensus selection needs model.consensus_table, a cvc.cider.CiderD (Trainer sets the "
+                               "training captions' table); there is none")
         if encoded is not None:
             fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
         else:
@@ -668,10 +694,18 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                      pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
         beam = self.beam_size if beam_size is None else int(beam_size)
         temp = float(getattr(self.opts, "softmax_temp", 1.0))
-        sampling = (self.sample_max if sample_max is None else int(sample_max)) == 0
-        tau = (self.sample_temperature if temperature is None else float(temperature)) if sampling else None
-        n = (self.sample_n if sample_n is None else int(sample_n)) if sampling else 1
-        s_seed = (self.sample_seed if seed is None else int(seed)) if sampling else None
+        sampling = mode == "samples" or (self.sample_max if sample_max is None else int(sample_max)) == 0
+        d_tau, d_n, d_seed = ((self.consensus_temperature, self.consensus_samples, self.consensus_seed) if mode == "samples" else
+                              (self.sample_temperature, self.sample_n, self.sample_seed))
+        tau = (d_tau if temperature is None else float(temperature)) if sampling else None
+        n = (d_n if sample_n is None else int(sample_n)) if sampling else 1
+        s_seed = (d_seed if seed is None else int(seed)) if sampling else None
+        if mode == "samples":
+            beam = 1
+        if mode is not None and not (n > 1 if (sampling and mode != "beam") else (not sampling and beam > 1)):
+            raise RuntimeError(f"_sample: consensus selection needs several candidates per clip -- sample_max = 0 with sample_n > 1, or "
+                               f"beam_size > 1 without sampling (got consensus = {mode!r}, sampling = {sampling}, sample_n = {n}, "
+                               f"beam_size = {beam})")
         k = (self.sample_top_k if top_k is None else int(top_k)) if sampling else 0
         p = (self.sample_top_p if top_p is None else float(top_p)) if sampling else 1.0
         wdtype = self.decode_weights_dtype if decode_weights is None else decode_weights
@@ -695,7 +729,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha)
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha) + (mode is not None,)
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -709,7 +743,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         else:
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
                                   sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
-                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0),
+                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0)
+                                  or (beam > 1 and mode is not None),      # (consensus chooses among hypotheses())
                                   beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n, **cons)
             if self.use_hip_graph:
                 engine.capture()
@@ -717,6 +752,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if force_n > 0:
             engine.load_force_words(force_words)
         res = engine.run()
+        if mode is not None:
+            seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table)
+            self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility)
+            return seq_c, att_c, logprob_c
         if sampling or (engine.constrained and beam == 1):
             return res[0].clone(), res[1].clone(), res[2].clone()
         return res[0].clone(), res[1].clone(), None

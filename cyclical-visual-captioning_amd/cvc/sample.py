@@ -5,7 +5,9 @@ temperature) without UNK, written to <results_dir>/densecap-<val_split>-<id>_sam
   python -m cvc.sample --temperature 0.7 --sample_n 5 --sample_seed 1 --path_opt cfgs/cyclical.yml --resume True --id my_run
   python -m cvc.sample --temperature 1.0 --top_k 40 --top_p 0.9 ...      (top-k, then nucleus truncation of the distribution)
 
---temperature / --sample_n / --sample_seed / --top_k / --top_p are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
+  python -m cvc.sample --sample_n 16 --consensus ...                     (also the consensus pick and the samples' utilities)
+
+--temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
 --resume with --load_best_score: the same checkpoint loading as an --inference_only evaluation).
 """
 from __future__ import annotations
@@ -24,7 +26,12 @@ def parse(argv=None):
     p.add_argument("--sample_seed", type=int, default=0, help="seed of the sampling noise")
     p.add_argument("--top_k", type=int, default=0, help="keep the k most likely words (and ties with the k-th); 0 = off")
     p.add_argument("--top_p", type=float, default=1.0, help="nucleus: keep the most likely words up to mass p in (0, 1]; 1 = off")
+    p.add_argument("--consensus", action="store_true",
+                   help="add to every segment the index of its consensus pick and the samples' utilities (CIDEr-D against the other "
+                        "samples, training captions' table); needs --sample_n > 1")
     own, rest = p.parse_known_args(argv)
+    if own.consensus and own.sample_n < 2:
+        raise SystemExit("--consensus needs --sample_n > 1")
     if not own.temperature > 0:
         raise SystemExit("--temperature must be > 0")
     if own.sample_n < 1:
@@ -40,7 +47,7 @@ def main(argv=None):
     own, rest = parse(argv)
     if "--inference_only" not in rest:
         rest = rest + ["--inference_only"]
-    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p))
+    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus))
 
 
 if __name__ == "__main__":

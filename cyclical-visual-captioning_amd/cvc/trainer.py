@@ -275,6 +275,11 @@ class Trainer:
             self._cider = CiderD.from_dataset(self.dataset, self.device)
         return self._cider
 
+    def _consensus_table(self, model):
+        """consensus selection (model._sample(consensus=...)) takes its utilities over the training captions' table: set on first use"""
+        if model.consensus_table is None:
+            model.consensus_table = self.cider()
+
     def scst_step(self, batch):
         return self.scst_step_prepared(self._prepare(batch, True))
 
@@ -301,7 +306,7 @@ class Trainer:
         cider = self.cider()
         T = model.seq_length
         plain = dict(beam_size=1, top_k=0, top_p=1.0, no_repeat_ngram=0, no_immediate_repeat=False, min_len=0, ban_words=(), bad_endings=(),
-                     beam_groups=1, diversity_lambda=0.0, length_penalty=0.0)
+                     beam_groups=1, diversity_lambda=0.0, length_penalty=0.0, consensus=False)
         was_training = model.training
         model.eval()
         try:
@@ -666,8 +671,14 @@ class Trainer:
 
     def eval(self, epoch, tb_logger=None):
         """Greedy (or beam) decode of the validation split -> predictions in the densecap JSON
-        layout (trainer.py:254-286: {'sentence', 'timestamp': [start, end]} per segment) -> optional external scorer."""
+        layout (trainer.py:254-286: {'sentence', 'timestamp': [start, end]} per segment) -> optional external scorer.
+        With the model's consensus switch on (opts.consensus = samples / beam) every clip's caption is the consensus pick among its
+        candidates (model._sample), with that candidate's attention rows: the densecap file, the device metrics and the grounding
+        all see the picked caption."""
         self.model.eval()
+        core = getattr(self.model, "module", self.model)
+        if getattr(core, "consensus", "off") != "off":
+            self._consensus_table(core)
         predictions = defaultdict(list)
         grd_output = defaultdict(dict)
         o = self.opts
@@ -844,7 +855,7 @@ class Trainer:
         return stats
 
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
-               constraints: dict = None):
+               constraints: dict = None, consensus: bool = False):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
         without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise);
         top_k / top_p truncate that distribution (0 / 1.0 = off; the log-probs stay the model's, over the full vocabulary).
@@ -853,6 +864,9 @@ class Trainer:
         Writes <results_dir>/<stem>_samples.json (rank 0, as eval does; stem defaults to densecap-<val_split>-<id>):
             {video: [{"segment": seg_idx, "timestamp": [start, end], "sentences": [n], "logprobs": [n]}]}
         logprobs[j]: the sum of the log-probs of sample j's words up to and including its first EOS (all T steps without one).
+        consensus=True (n > 1): every entry also holds "consensus": the index of the consensus pick among its n sentences, and
+        "utilities": [n], each sentence's CIDEr-D against the segment's other samples over the training captions' table
+        (cvc.cider.CiderD.consensus); the last batch's device tensors stay in model.last_consensus.
         Returns the path (None on the other ranks)."""
         model = getattr(self.model, "module", self.model)
         model.eval()
@@ -860,12 +874,20 @@ class Trainer:
         timestamps = self._segment_timestamps()
         samples = defaultdict(list)
         n = int(n)
+        if consensus:
+            if n < 2:
+                raise RuntimeError(f"Trainer.sample: consensus selection needs n > 1 samples per segment, got n = {n}")
+            self._consensus_table(model)
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
                 seq, _, logprob = model._sample(b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"],
                                                 b["gt_bboxs"], b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"],
                                                 sample_max=0, temperature=temperature, sample_n=n, seed=seed, top_k=top_k,
-                                                top_p=top_p, **(constraints or {}))
+                                                top_p=top_p, consensus=False, **(constraints or {}))
+                if consensus:
+                    utility, pick, _ = model.consensus_table.consensus(seq, n)
+                    model.last_consensus = dict(candidates=seq, pick=pick, utility=utility)
+                    picks, utils_ = pick.tolist(), utility.view(-1, n).tolist()
                 sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 # sequence log-prob: the steps up to and including the first EOS (word 0)
@@ -875,6 +897,8 @@ class Trainer:
                     vid_idx, entry = densecap_entry(sents[k * n], seg_id, timestamps)
                     samples[vid_idx].append({"segment": entry["segment"], "timestamp": entry["timestamp"],
                                              "sentences": sents[k * n:(k + 1) * n], "logprobs": seq_lp[k * n:(k + 1) * n]})
+                    if consensus:
+                        samples[vid_idx][-1].update(consensus=picks[k], utilities=utils_[k])
         samples, _ = gather_eval_outputs(samples, {})
         self.samples = samples
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:

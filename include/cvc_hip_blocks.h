@@ -528,6 +528,24 @@ int cvc_scst_weights(const float* reward, const float* base, int rows, int per_c
 int cvc_caption_overlap(const int64_t* cand, const int64_t* refs, const int32_t* nref, int rows, int T, int per_clip, int Rmax,
                         int32_t* stats, int32_t* lcs, float* bleu, float* rouge, cvc_stream_t stream);
 
+/* ---- consensus (minimum-Bayes-risk) caption selection: pairwise CIDEr-D among a clip's candidates, one launch
+ * (csrc/consensus.hip; cvc.cider.CiderD.consensus, cvc.decode.DecodeEngine.consensus).
+ *   cand [rows, T] int64: row c * per_clip + j = candidate j of clip c;  live [rows] int32 (nullable: every row is live), a row with
+ *   live == 0 is neither a candidate nor a reference;  keys / idf / G / idf_unseen / sigma and a caption's words as cvc_cider_d.
+ *   utility [rows] fp32: the CIDEr-D of the row as the candidate against the clip's other live rows as the references, in ascending
+ *     row order -- bit for bit what cvc_cider_d returns for that candidate and those references (per_clip = 1, nref = their number);
+ *     0 for a dead row and for a row without another live row in its clip.
+ *   pick [clips] int32: the index within the clip of the live row with the largest utility, the lowest index on a tie, 0 for a clip
+ *     without a live row;  best [clips, T] int64: that row, all T ids.
+ * One workgroup per clip; every caption's n-gram keys, counts, idf weights and norms are built once and kept in LDS for the pairs
+ * (one table search per distinct n-gram per launch).  No atomics, no workspace: a clip's outputs are bit-reproducible and
+ * independent of the other clips.  Launch only (no host read, no allocation): capturable in a HIP graph.
+ * Null pointers (but live; keys / idf with G = 0), rows < 1, rows % per_clip != 0, per_clip < 1 or > 32, T < 1 or > 63, G < 0,
+ * sigma <= 0: CVC_E_BADARG, before any launch. */
+int cvc_consensus_cider(const int64_t* cand, const int32_t* live, int rows, int T, int per_clip, const unsigned long long* keys,
+                        const float* idf, int G, float idf_unseen, float sigma, float* utility, int32_t* pick, int64_t* best,
+                        cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
