@@ -86,6 +86,7 @@ const Entry table[] = {
     CVC_B(cvc_scst_weights),
     CVC_B(cvc_caption_overlap),
     CVC_B(cvc_consensus_cider),
+    CVC_B(cvc_grounding_f1),
 #ifdef CVC_EXPERIMENTAL
     CVC_B(cvc_gsk_plan),
     CVC_B(cvc_gsk_gemm),

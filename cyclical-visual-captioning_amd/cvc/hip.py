@@ -272,6 +272,8 @@ SIGNATURES = {
     "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # consensus caption selection: pairwise CIDEr-D among a clip's candidates, pick and picked row (csrc/consensus.hip; building block)
     "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
+    # grounding F1 of generated captions: picks per object word and frame, per-class counters (csrc/grounding.hip; building block)
+    "cvc_grounding_f1": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -316,7 +318,8 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider"}
+    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
+    "cvc_grounding_f1"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1197,6 +1200,48 @@ def consensus_cider(cand: torch.Tensor, per_clip: int, keys: torch.Tensor, idf: 
                                      float(idf_unseen), float(sigma), _dev(utility), _dev(pick, torch.int32), _dev(best, torch.int64),
                                      _stream()), "cvc_consensus_cider")
     return utility, pick, best
+
+
+# --------------------------------------------------------------------------- grounding F1 of generated captions (csrc/grounding.hip)
+def grounding_f1(seq: torch.Tensor, att: torch.Tensor, ppls: torch.Tensor, gt_bboxs: torch.Tensor, nbox: torch.Tensor,
+                 word_cls: torch.Tensor, frames: int, table: torch.Tensor, per_clip: Optional[int] = None,
+                 props_per_frame: Optional[int] = None):
+    """seq [rows, T] int64; att [rows, T, P] fp32 over the clip's proposals (frame-major, P <= frames * props_per_frame: the trimmed
+    axis; props_per_frame None: P / frames);
+    ppls [clips, P, 7] fp32; gt_bboxs [clips, K, 6] fp32 (x1, y1, x2, y2, frame, class); nbox [clips] int32; word_cls [V] int32;
+    table [C + 1, 6] int32, added to (per_clip = rows / clips consecutive rows per clip).
+    -> pick [rows, T, frames] int32, counts [rows, 6] int32, f1 [rows] fp32"""
+    frames = int(frames)
+    if seq.dim() != 2 or att.dim() != 3 or ppls.dim() != 3 or gt_bboxs.dim() != 3 or word_cls.dim() != 1 or table.dim() != 2 \
+            or att.shape[:2] != seq.shape or ppls.shape[0] < 1 or ppls.shape[1] != att.shape[2] or ppls.shape[2] != 7 \
+            or gt_bboxs.shape[0] != ppls.shape[0] or gt_bboxs.shape[2] != 6 or nbox.numel() != ppls.shape[0] \
+            or table.shape[0] < 2 or table.shape[1] != 6 or frames < 1:
+        raise RuntimeError(f"cvc.hip.grounding_f1: seq {tuple(seq.shape)}, att {tuple(att.shape)}, ppls {tuple(ppls.shape)}, gt_bboxs "
+                           f"{tuple(gt_bboxs.shape)}, nbox {tuple(nbox.shape)}, word_cls {tuple(word_cls.shape)}, table "
+                           f"{tuple(table.shape)}, frames {frames} do not fit")
+    rows, T = seq.shape
+    clips, P, K = ppls.shape[0], ppls.shape[1], gt_bboxs.shape[1]
+    per_clip = rows // clips if per_clip is None else int(per_clip)
+    if per_clip < 1 or per_clip * clips != rows:
+        raise RuntimeError(f"cvc.hip.grounding_f1: {rows} caption rows are not {per_clip} per clip of {clips} clips")
+    if props_per_frame is None:   # an untrimmed axis: frames x Np slots exactly
+        if P % frames != 0:
+            raise RuntimeError(f"cvc.hip.grounding_f1: {P} proposal slots are not {frames} frames of equally many: a trimmed axis needs "
+                               "props_per_frame")
+        props_per_frame = P // frames
+    Np = int(props_per_frame)
+    if Np < 1 or P > frames * Np:
+        raise RuntimeError(f"cvc.hip.grounding_f1: {P} proposal slots do not fit {frames} frames of {Np}")
+    dev = seq.device
+    pick = torch.empty(rows, T, frames, device=dev, dtype=torch.int32)
+    counts = torch.empty(rows, 6, device=dev, dtype=torch.int32)
+    f1 = torch.empty(rows, device=dev, dtype=torch.float32)
+    _check(lib().cvc_grounding_f1(_dev(seq, torch.int64, "seq"), _dev(att, name="att"), _dev(ppls, name="ppls"),
+                                  _dev(gt_bboxs, name="gt_bboxs"), _dev(nbox, torch.int32, "nbox"), _dev(word_cls, torch.int32, "word_cls"),
+                                  rows, T, P, frames, Np, K, table.shape[0] - 1, int(word_cls.numel()), per_clip,
+                                  _dev(pick, torch.int32), _dev(counts, torch.int32), _dev(f1), _dev(table, torch.int32, "table"),
+                                  _stream()), "cvc_grounding_f1")
+    return pick, counts, f1
 
 
 # --------------------------------------------------------------------------- tile path (rows > 64), csrc/gemm_tile.hip

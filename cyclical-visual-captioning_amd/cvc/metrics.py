@@ -17,6 +17,9 @@ Definitions (what csrc/overlap.hip computes and tests/overlap_ref.py restates):
 
 These are NOT the toolkit's numbers: no PTB tokenizer is applied (the ids are the dataset's tokens, UNK is a word like any other),
 CIDEr-D counts the end mark, METEOR and SPICE are not attempted.
+
+Further down: the grounding scores of the generated captions (csrc/grounding.hip; grounding, grounding_result, GroundingScorer) --
+F1_all / F1_loc in the manner of ActivityNet-Entities, for Trainer.eval with the device metrics and --eval_obj_grounding both on.
 """
 from __future__ import annotations
 
@@ -167,3 +170,101 @@ def result_from_sums(stats_sum, rouge_sum, cider_sum, count) -> dict:
     n = max(float(count), 1.0)
     return {"Bleu_1": float(bleu[0]), "Bleu_2": float(bleu[1]), "Bleu_3": float(bleu[2]), "Bleu_4": float(bleu[3]),
             "ROUGE_L": float(rouge_sum) / n, "CIDEr": float(cider_sum) / n}
+
+
+# --------------------------------------------------------------------------- grounding F1 of generated captions (csrc/grounding.hip)
+# Definitions (what the kernel computes and tests/grounding_ref.py restates):
+# * an object word is a position before the caption's first 0 whose word id maps to a detection class >= 1 (word_cls); the row's
+#   predicted classes are the distinct such classes, each represented by its first object word.
+# * pick[r, t, f]: for an object word and a sampled frame the proposal slot f * Np + j with the largest attention weight, the lowest j
+#   among equal maxima (j = 0 for a frame without a weight > -inf); -1 elsewhere.  A trimmed proposal axis is padded with weight -inf
+#   and zero boxes.
+# * a class's box in frame f is the proposal its representative picks there; it hits an annotated box when the intersection has
+#   positive width and height and 2 * inter > union (IoU > 1/2, no +1 pixel, fp32).
+# * per class c, over the clip's annotated boxes of class c: gt, gt_pred (c is predicted), gt_hit (and the box's frame is a sampled
+#   frame whose box hits it); over the rows that predict c: pred, pred_in_gt (the clip has a box of c), pred_hit (one of them is hit).
+# * scores (grounding_result), over the classes S with gt > 0: Prec_all = mean pred_hit / pred (0 where pred = 0), Recall_all = mean
+#   gt_hit / gt, Prec_loc = mean over pred_in_gt > 0 of pred_hit / pred_in_gt, Recall_loc = mean over gt_pred > 0 of gt_hit / gt_pred
+#   (an empty mean: 0), F1 = 2 P R / (P + R) (0 when P + R = 0); the _micro scores: the same ratios on the column sums over all classes.
+# These follow ActivityNet-Entities' F1_all / F1_loc but are NOT the toolkit's numbers: the toolkit is not pinned against, a word's
+# class comes from the dataset's lemma table alone, and the boxes are the dataset's padded annotation rows.
+GROUNDING_COLUMNS = ("gt", "gt_pred", "gt_hit", "pred", "pred_in_gt", "pred_hit")
+GROUNDING_KEYS = ("F1_all", "F1_loc", "Prec_all", "Recall_all", "Prec_loc", "Recall_loc", "F1_all_micro", "F1_loc_micro")
+
+
+def grounding(seq: torch.Tensor, att: torch.Tensor, ppls: torch.Tensor, gt_bboxs: torch.Tensor, nbox: torch.Tensor, word_cls: torch.Tensor,
+              frames: int, per_clip: Optional[int] = None, table: Optional[torch.Tensor] = None,
+              props_per_frame: Optional[int] = None) -> dict:
+    """seq [rows, T] int64; att [rows, T, P] fp32; ppls [clips, P, 7]; gt_bboxs [clips, K, 6] (x1, y1, x2, y2, frame, class); nbox
+    [clips]: how many of a clip's K boxes count; word_cls [V] int32: word id -> detection class or 0; frames: sampled frames per clip
+    (P = frames * props_per_frame slots, frame-major; a trimmed axis, P smaller than that, needs props_per_frame); table [C + 1, 6]
+    int32 is added to (None: a fresh one sized by word_cls' largest class -- one host read; pass a table to have none).
+    -> dict(pick [rows, T, frames] int32, counts [rows, 6] int32, f1 [rows] fp32, table), all on the device."""
+    from . import hip
+    from .cider import MAX_T
+    if seq.dim() != 2 or seq.shape[1] > MAX_T:
+        raise RuntimeError(f"metrics.grounding: seq {tuple(seq.shape)}; the kernel takes rows of at most T = {MAX_T} words")
+    if table is None:
+        table = torch.zeros(max(int(word_cls.max()), 1) + 1, 6, dtype=torch.int32, device=seq.device)
+    elif table.dim() != 2 or table.shape[0] < 2 or table.shape[1] != 6 or table.dtype != torch.int32:
+        raise RuntimeError(f"metrics.grounding: the table must be [classes + 1, 6] int32, got {tuple(table.shape)} {table.dtype}")
+    pick, counts, f1 = hip.grounding_f1(seq.contiguous(), att.contiguous(), ppls.contiguous(), gt_bboxs.contiguous(),
+                                        nbox.to(torch.int32).contiguous(), word_cls.contiguous(), frames, table, per_clip, props_per_frame)
+    return dict(pick=pick, counts=counts, f1=f1, table=table)
+
+
+def grounding_result(table) -> dict:
+    """the per-class counters [C + 1, 6] (GROUNDING_COLUMNS) -> the scores of GROUNDING_KEYS, fp64 on the host"""
+    t = np.asarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.float64).reshape(-1, 6)
+    gt, gt_pred, gt_hit, pred, pred_in_gt, pred_hit = (t[:, i] for i in range(6))
+
+    def mean(num, den, keep):
+        return float(np.mean(num[keep] / den[keep])) if keep.any() else 0.0
+
+    def f1(p, r):
+        return 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+
+    def ratio(num, den):
+        return float(num / den) if den > 0 else 0.0
+    S = gt > 0
+    ratio_or_0 = np.divide(pred_hit, pred, out=np.zeros_like(pred), where=pred > 0)
+    prec_all = float(np.mean(ratio_or_0[S])) if S.any() else 0.0
+    rec_all = mean(gt_hit, gt, S)
+    prec_loc = mean(pred_hit, pred_in_gt, S & (pred_in_gt > 0))
+    rec_loc = mean(gt_hit, gt_pred, S & (gt_pred > 0))
+    s = t.sum(0)
+    return {"F1_all": f1(prec_all, rec_all), "F1_loc": f1(prec_loc, rec_loc), "Prec_all": prec_all, "Recall_all": rec_all,
+            "Prec_loc": prec_loc, "Recall_loc": rec_loc, "F1_all_micro": f1(ratio(s[5], s[3]), ratio(s[2], s[0])),
+            "F1_loc_micro": f1(ratio(s[5], s[4]), ratio(s[2], s[1]))}
+
+
+class GroundingScorer:
+    """Grounding scores of a validation pass without a host read per batch: add() runs the kernel on a batch, which adds to the
+    per-class int32 table on the device; sums() reads it once; add_sums() takes another rank's table; result() -> grounding_result."""
+
+    def __init__(self, word_cls: torch.Tensor, n_classes: int, frames: int, props_per_frame: Optional[int] = None):
+        self.word_cls = word_cls.to(torch.int32).contiguous()
+        self.n_classes, self.frames = int(n_classes), int(frames)
+        self.props_per_frame = None if props_per_frame is None else int(props_per_frame)
+        self.table = None              # [n_classes + 1, 6] int32 on the device
+        self.extra = np.zeros((self.n_classes + 1, 6), dtype=np.int64)         # other ranks' tables, on the host
+
+    def add(self, seq, att, ppls, gt_bboxs, nbox, per_clip: Optional[int] = None) -> dict:
+        """one launch, no host read -> grounding()'s dict (pick, counts, f1 of this batch; table: the running one)"""
+        if self.table is None:
+            self.table = torch.zeros(self.n_classes + 1, 6, dtype=torch.int32, device=seq.device)
+            self.word_cls = self.word_cls.to(seq.device)
+        return grounding(seq, att, ppls, gt_bboxs, nbox, self.word_cls, self.frames, per_clip, self.table, self.props_per_frame)
+
+    def add_sums(self, table):
+        """a precomputed table (another rank's, or a test's): [n_classes + 1, 6] integers"""
+        t = np.asarray(table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.int64)
+        self.extra += t.reshape(self.n_classes + 1, 6)
+
+    def sums(self) -> np.ndarray:
+        """-> the table [n_classes + 1, 6] int64 on the host: ONE read"""
+        mine = self.table.cpu().numpy().astype(np.int64) if self.table is not None else 0
+        return self.extra + mine
+
+    def result(self) -> dict:
+        return grounding_result(self.sums())

@@ -60,6 +60,20 @@ def detected_force_words(proposals, num, C, itod, wtoi, unk_idx):
     return out
 
 
+def word_class_table(opts):
+    """[vocab_size] int32 on the host: word id -> the detection class (an index of itod, >= 1) a generated word is grounded as, 0 for
+    every other id -- the rule Trainer._collect_grounding applies word by word: the word's lemma (wtol) is the lemma of a detection
+    class name (wtod).  Built once per trainer; the grounding kernel (cvc.metrics.grounding) reads it on the device."""
+    lemma_det = {opts.wtol[k]: i for k, i in opts.wtod.items() if k in opts.wtol}
+    table = torch.zeros(int(opts.vocab_size), dtype=torch.int32)
+    for ix, word in opts.itow.items():
+        ix = int(ix)
+        lemma = opts.wtol.get(word)
+        if 0 < ix < table.numel() and lemma in lemma_det:
+            table[ix] = int(lemma_det[lemma])
+    return table
+
+
 def _text_mask(target):
     m = target.gt(0)
     return torch.cat([torch.ones_like(m[:, :1]), m[:, :-1]], 1)   # includes the first EOS (:135-137)

@@ -6,7 +6,8 @@ reconstruction-loss meter is updated, grounding stats are only logged when they 
 
 Caption / grounding scoring lives in external toolkits the reference vendors as (empty)
 submodules; pass `scorer(predictions, grd_output, opts) -> dict` to get language stats, and / or
-`device_metrics=True` for BLEU, ROUGE-L and CIDEr-D by word id on the device (cvc.metrics).
+`device_metrics=True` for BLEU, ROUGE-L and CIDEr-D by word id on the device (cvc.metrics) -- and, with opts.eval_obj_grounding
+beside it, the grounding F1 of the generated captions (cvc.metrics.GroundingScorer).
 """
 from __future__ import annotations
 
@@ -92,6 +93,7 @@ class Trainer:
         # (cvc.metrics.DeviceScorer); off: eval is what it was
         self.device_metrics = bool(device_metrics)
         self._val_cider = None        # cvc.cider.CiderD over the validation loader's captions, built at the first eval
+        self._word_cls = None         # word id -> detection class (utils.word_class_table), built at the first eval that grounds
         self.device = next(model.parameters()).device
         self._graph = None            # HIP-graph state of train_step_graphed
         # ---- train(): one captured graph per (bucketed) batch shape
@@ -685,6 +687,9 @@ class Trainer:
         ds = self.dataset
         timestamps = self._segment_timestamps()
         dev_scorer = self._device_scorer() if (self.device_metrics and o.val_split != 'hidden_test') else None
+        # the grounding scores of the generated captions (cvc.metrics.GroundingScorer): only with the device metrics AND
+        # --eval_obj_grounding; the grounding file then is built from the kernel's picks
+        grd_scorer = self._grounding_scorer() if (dev_scorer is not None and getattr(o, "eval_obj_grounding", False)) else None
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
                 seq, att2_weights, _ = self._call(b, True)
@@ -693,7 +698,10 @@ class Trainer:
                     dev_scorer.add(seq.contiguous(), b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32))
                 if getattr(o, "eval_obj_grounding", False):
                     assert o.beam_size == 1, 'only support beam_size is 1'
-                    self._collect_grounding(b, seq, att2_weights, grd_output)
+                    if grd_scorer is not None:
+                        self._collect_grounding_device(b, seq, att2_weights, grd_scorer, grd_output)
+                    else:
+                        self._collect_grounding(b, seq, att2_weights, grd_output)
                 sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 for k, sent in enumerate(sents):
@@ -704,6 +712,8 @@ class Trainer:
         lang_stats = {}
         if dev_scorer is not None:                          # (every rank: its sums are merged like the predictions)
             lang_stats = self._merged_device_metrics(dev_scorer)
+        if grd_scorer is not None:
+            lang_stats = {**lang_stats, **self._merged_grounding(grd_scorer)}
         if getattr(o, "eval_obj_grounding_gt", False):        # (every rank: its shards are merged like the predictions)
             self._eval_ground_gt(epoch, tb_logger)
         self.submission_file = self.attn_file = None
@@ -744,6 +754,27 @@ class Trainer:
         dist.all_gather_object(parts, mine)
         stats = [sum(p[0][i] for p in parts) for i in range(10)]
         return result_from_sums(stats, *(sum(p[j] for p in parts) for j in (1, 2, 3)))
+
+    def _grounding_scorer(self):
+        """a fresh cvc.metrics.GroundingScorer; the word -> detection class table is built once, at the first eval"""
+        from .metrics import GroundingScorer
+        o = self.opts
+        if self._word_cls is None:
+            self._word_cls = utils.word_class_table(o).to(self.device)
+        return GroundingScorer(self._word_cls, len(o.itod), o.num_sampled_frm, o.num_prop_per_frm)
+
+    @staticmethod
+    def _merged_grounding(grd_scorer):
+        """one host read of this rank's per-class table; with several ranks the tables are exchanged host-side and added on every
+        rank, as _merged_device_metrics does with its sums (more than one rank: untested)"""
+        import torch.distributed as dist
+        from .metrics import grounding_result
+        mine = grd_scorer.sums()
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return grounding_result(mine)
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        return grounding_result(sum(parts[1:], parts[0]))
 
     def _eval_ground_gt(self, epoch, tb_logger):
         """eval's --eval_obj_grounding_gt part: grounding on the GT sentences, kept as self.grounding_gt_stats and logged under
@@ -923,7 +954,7 @@ class Trainer:
         """Per generated word, the most attended proposal of every sampled frame (trainer.py:217-248)."""
         o = self.opts
         B = seq.size(0)
-        boxes = self._frame_boxes(b["ppls"], att2_weights)
+        boxes = self._frame_boxes(*self._full_proposal_axis(b["ppls"], att2_weights))
         lemma_det = {o.wtol[k]: i for k, i in o.wtod.items() if k in o.wtol}
         words = seq.tolist()                                   # one device -> host copy each, not one per word
         boxes_l = boxes[..., :4].tolist()
@@ -939,6 +970,32 @@ class Trainer:
                     res['clss'].append(o.itod[lemma_det[lemma]])
                     res['idx_in_sent'].append(j)
             grd_output[vid_id][str(int(seg_idx))] = res
+
+    def _collect_grounding_device(self, b, seq, att2_weights, grd_scorer, grd_output):
+        """_collect_grounding on the grounding kernel (eval with the device metrics): one launch scores the batch into the scorer's
+        per-class table and returns every object word's proposal slot per sampled frame; the boxes of those words alone are
+        gathered and read in ONE device -> host copy (position, class and 4 x frames coordinates per object word)."""
+        o = self.opts
+        ppls = b["ppls"]
+        pick = grd_scorer.add(seq, att2_weights, ppls, b["gt_bboxs"], b["num"][:, 2])["pick"]          # [B, T, frames] int32
+        at = (pick[:, :, 0] >= 0).nonzero()                                                       # the object words: (row, position)
+        rows_i, pos = at[:, 0], at[:, 1]
+        slots = pick[rows_i, pos].long()                                                          # [n, frames]
+        clips = (rows_i // (seq.size(0) // ppls.size(0))).unsqueeze(1)
+        given = (slots < ppls.size(1)).unsqueeze(2)                                               # a trimmed slot: a zero box
+        boxes = torch.where(given, ppls[clips, slots.clamp(max=ppls.size(1) - 1), :4], ppls.new_zeros(()))
+        cls = grd_scorer.word_cls[seq[rows_i, pos]]
+        flat = torch.cat([torch.stack([rows_i, pos, cls.long()], 1).double(), boxes.double().flatten(1)], 1).tolist()
+        res = []
+        for seg_id in b["seg_id"]:
+            vid_id, seg_idx = seg_id.split('_segment_')
+            res.append({'clss': [], 'idx_in_sent': [], 'bbox_for_all_frames': []})
+            grd_output[vid_id][str(int(seg_idx))] = res[-1]
+        for rec in flat:
+            r = res[int(rec[0])]
+            r['bbox_for_all_frames'].append([rec[3 + 4 * f:7 + 4 * f] for f in range(pick.size(2))])
+            r['clss'].append(o.itod[int(rec[2])])
+            r['idx_in_sent'].append(int(rec[1]))
 
 
 def ground_picks(weights, frm_mask_output, roi_labels):

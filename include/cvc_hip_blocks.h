@@ -546,6 +546,30 @@ int cvc_consensus_cider(const int64_t* cand, const int32_t* live, int rows, int 
                         const float* idf, int G, float idf_unseen, float sigma, float* utility, int32_t* pick, int64_t* best,
                         cvc_stream_t stream);
 
+/* ---- grounding F1 of generated captions: per object word the most attended proposal of every sampled frame, tested against the
+ * clip's annotated boxes and counted per detection class, one launch (csrc/grounding.hip; cvc.metrics.grounding, Trainer.eval).
+ *   seq [rows, T] int64: row r belongs to clip r / per_clip; its words are the ids before the first 0 (all T without one).
+ *   att [rows, T, P] fp32: the weights over the clip's proposals; slot p belongs to frame p / Np, P <= F * Np is the trimmed axis (a
+ *     slot >= P has weight -inf and a zero box).  ppls [rows / per_clip, P, 7] fp32 (x1, y1, x2, y2 first).
+ *   gt_bboxs [rows / per_clip, K, 6] fp32 (x1, y1, x2, y2, frame, class), of which the first nbox[clip] (int32, clamped to [0, K])
+ *     count; a box whose class is outside [1, C] is not counted.
+ *   word_cls [V] int32: word id -> class in [1, C], anything else (and an id outside [0, V)): no object word.
+ *   pick [rows, T, F] int32: for an object word t and a frame f the slot f * Np + j with the largest weight, the lowest j among
+ *     equal maxima, j = 0 when no weight of the frame is > -inf or the first one is NaN; -1 everywhere else.
+ *   A class is represented by its first object word; its box in frame f is ppls[clip, pick, 0:4]; it hits an annotated box when
+ *   w = min(x2) - max(x1) > 0, h likewise, and 2 w h > area_a + area_g - w h (fp32, no +1 pixel, no contraction).
+ *   table [C + 1, 6] int32, ADDED TO, per class: gt, gt_pred, gt_hit (boxes of the class; of a predicted class; hit by the
+ *     representative's pick in the box's frame, which lies in [0, F)), pred, pred_in_gt, pred_hit (rows that predict the class; whose
+ *     clip has a box of it; at least one of them hit).  counts [rows, 6] int32: the row's own sums over the classes, same order.
+ *   f1 [rows] fp32: 2 p r / (p + r) with p = pred_hit / pred, r = gt_hit / gt of the row's counts; 0 when a denominator is 0.
+ * One workgroup per row; integer atomics into the table: every output is bit-reproducible.  Launch only (no host read, no
+ * allocation): capturable in a HIP graph.
+ * Null pointers, rows < 1, T < 1 or > 63, P, F, Np, K, C, V or per_clip < 1, rows % per_clip != 0, P > F * Np: CVC_E_BADARG;
+ * (T * F + 3 K) * 4 bytes > 48 KiB (the kernel's LDS): CVC_E_TOOBIG; both before any launch. */
+int cvc_grounding_f1(const int64_t* seq, const float* att, const float* ppls, const float* gt_bboxs, const int32_t* nbox,
+                     const int32_t* word_cls, int rows, int T, int P, int F, int Np, int K, int C, int V, int per_clip,
+                     int32_t* pick, int32_t* counts, float* f1, int32_t* table, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
