@@ -370,17 +370,24 @@ __global__ __launch_bounds__(WG) void nll_fwd_kernel(const float* logp, const in
 
 // Fused vocabulary criterion: one pass over a row of raw logits gives its log-sum-exp, its argmax (ties -> lowest
 // index, what torch.max over the log-probs returns) and the row's weighted NLL; no [M, V] log-prob matrix is written.
+// LS: label smoothing eps in [0, 1), the target distribution (1 - eps) onehot + eps / V (F.cross_entropy's label_smoothing):
+//     row_loss = w (lse - (1 - eps) x[t] - (eps / V) sum_v x[v]),   row_nll = w (lse - x[t]) (the unsmoothed value, nullable)
+// -- the row's sum is taken in the pass that looks for the maximum, one more fixed-order block reduction.  eps == 0 gives the
+// bits of the LS = false form.
+template <bool LS>
 __global__ __launch_bounds__(WG) void vocab_nll_fwd_kernel(const float* logits, const int64_t* target, const float* w, int V,
-                                                           float* lse_out, int64_t* argmax, float* row_loss) {
+                                                           float* lse_out, int64_t* argmax, float* row_loss, float eps, float* row_nll) {
     __shared__ float red[4];
     __shared__ int ired[4];
     const int row = blockIdx.x;
     const float* x = logits + (size_t)row * V;
     float m = -INFINITY;
     int mi = 0x7fffffff;
+    float zs = 0.f;
     for (int v = threadIdx.x; v < V; v += WG) {
         const float xv = x[v];
         if (xv > m) { m = xv; mi = v; }                       // ascending v per thread: first occurrence wins
+        if (LS) zs += xv;
     }
     const float bm = block_max(m, red);
     int cand = m == bm ? mi : 0x7fffffff;
@@ -393,12 +400,20 @@ __global__ __launch_bounds__(WG) void vocab_nll_fwd_kernel(const float* logits, 
     float s = 0.f;
     for (int v = threadIdx.x; v < V; v += WG) s += expf(x[v] - bm);
     s = block_sum(s, red);
+    if (LS) zs = block_sum(zs, red);
     if (threadIdx.x == 0) {
         const float lse = bm + logf(s);
         lse_out[row] = lse;
         if (argmax != nullptr) argmax[row] = best == 0x7fffffff ? 0 : best;      // all-NaN row: keep the index in range
         const float wm = w[row];
-        row_loss[row] = wm != 0.f ? wm * (lse - x[target[row]]) : 0.f;
+        const float xt = wm != 0.f ? x[target[row]] : 0.f;
+        const float nll = wm != 0.f ? wm * (lse - xt) : 0.f;
+        if (LS) {
+            row_loss[row] = eps == 0.f ? nll : wm != 0.f ? wm * (lse - (1.f - eps) * xt - (eps / (float)V) * zs) : 0.f;
+            if (row_nll != nullptr) row_nll[row] = nll;
+        } else {
+            row_loss[row] = nll;
+        }
     }
 }
 
@@ -411,14 +426,20 @@ __global__ __launch_bounds__(WG) void row_sum_kernel(const float* row_loss, int 
 }
 
 // d_logits[m, v] = g[0] * w[m] * (softmax(logits[m])[v] - [v == target[m]])
+// LS: ... - (1 - eps) [v == target[m]] - eps / V), the gradient of the smoothed row loss (eps == 0: the bits of LS = false)
+template <bool LS>
 __global__ __launch_bounds__(WG) void vocab_nll_bwd_kernel(const float* logits, const float* lse, const int64_t* target,
-                                                           const float* w, const float* g, int V, float* d_logits) {
+                                                           const float* w, const float* g, int V, float* d_logits, float eps) {
     const int m = blockIdx.y;
     const int v = blockIdx.x * WG + threadIdx.x;
     if (v >= V) return;
     const float gw = g[0] * w[m];
     const size_t o = (size_t)m * V + v;
-    d_logits[o] = gw == 0.f ? 0.f : gw * (expf(logits[o] - lse[m]) - (v == (int)target[m] ? 1.f : 0.f));
+    const bool hit = v == (int)target[m];
+    if (LS && eps != 0.f)
+        d_logits[o] = gw == 0.f ? 0.f : gw * (expf(logits[o] - lse[m]) - (hit ? 1.f - eps : 0.f) - eps / (float)V);
+    else
+        d_logits[o] = gw == 0.f ? 0.f : gw * (expf(logits[o] - lse[m]) - (hit ? 1.f : 0.f));
 }
 
 // Vocabulary head criterion folded into the GEMM's finishing pass (captioner.py:266, :313, :361 +
@@ -428,10 +449,16 @@ __global__ __launch_bounds__(WG) void vocab_nll_bwd_kernel(const float* logits, 
 // -- the gradient of the row's loss term with respect to the logits, which the backward scales by the upstream scalar.  The
 // [B*T, V] logits never exist as a tensor in training.  `pre` may alias slab 0 (every thread reads its columns of all slabs
 // before it writes).  V <= 256 * NLL_CACHE.
+// LS: label smoothing eps in [0, 1) (the target distribution (1 - eps) onehot + eps / V, F.cross_entropy's label_smoothing):
+//     row_loss = w (lse - (1 - eps) x[t] - (eps / V) sum_v x[v]),   pre[m, v] = w[m] (softmax[v] - (1 - eps) [v == t] - eps / V),
+//     row_nll  = w (lse - x[t])  (the unsmoothed value, for logging; nullable)
+// -- every thread adds its columns in ascending order while they are in registers, one more fixed-order block reduction gives the
+// row's sum.  eps == 0 takes the LS = false expressions: the same bits.
 constexpr int NLL_CACHE = 32;
+template <bool LS>
 __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
                                                             const int64_t* target, const float* w, int V, float* pre, int ld_pre,
-                                                            int64_t* argmax, float* row_loss) {
+                                                            int64_t* argmax, float* row_loss, float eps, float* row_nll) {
     __shared__ float red[4];
     __shared__ int ired[4];
     __shared__ float xt_s;
@@ -441,6 +468,7 @@ __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, 
     float vals[NLL_CACHE];
     float m = -INFINITY;
     int mi = 0x7fffffff;
+    float zs = 0.f;
 #pragma unroll
     for (int u = 0; u < NLL_CACHE; ++u) {
         const int v = threadIdx.x + u * WG;
@@ -451,6 +479,7 @@ __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, 
             if (bias != nullptr) xv += bias[v];
             if (xv > m) { m = xv; mi = v; }                   // ascending v per thread: first occurrence wins
             if (v == tgt) xt_s = xv;
+            if (LS) zs += xv;
         }
         vals[u] = xv;
     }
@@ -469,15 +498,28 @@ __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, 
     s = block_sum(s, red);
     const float lse = bm + logf(s);
     const float wm = w[row];
+    const bool smooth = LS && eps != 0.f;
+    if (LS) zs = block_sum(zs, red);
     if (threadIdx.x == 0) {
         if (argmax != nullptr) argmax[row] = best == 0x7fffffff ? 0 : best;
-        row_loss[row] = wm != 0.f ? wm * (lse - xt_s) : 0.f;
+        const float nll = wm != 0.f ? wm * (lse - xt_s) : 0.f;
+        if (LS) {
+            row_loss[row] = !smooth ? nll : wm != 0.f ? wm * (lse - (1.f - eps) * xt_s - (eps / (float)V) * zs) : 0.f;
+            if (row_nll != nullptr) row_nll[row] = nll;
+        } else {
+            row_loss[row] = nll;
+        }
     }
     float* out = pre + (size_t)row * ld_pre;
+    const float hit = smooth ? 1.f - eps : 1.f, all = smooth ? eps / (float)V : 0.f;
 #pragma unroll
     for (int u = 0; u < NLL_CACHE; ++u) {
         const int v = threadIdx.x + u * WG;
-        if (v < V) out[v] = wm == 0.f ? 0.f : wm * (expf(vals[u] - lse) - (v == tgt ? 1.f : 0.f));
+        if (!smooth) {
+            if (v < V) out[v] = wm == 0.f ? 0.f : wm * (expf(vals[u] - lse) - (v == tgt ? 1.f : 0.f));
+        } else {
+            if (v < V) out[v] = wm == 0.f ? 0.f : wm * (expf(vals[u] - lse) - (v == tgt ? hit : 0.f) - all);
+        }
     }
 }
 
@@ -616,9 +658,25 @@ extern "C" int cvc_nll_fwd(const float* logp, const int64_t* target, const float
 extern "C" int cvc_vocab_nll_fwd(const float* logits, const int64_t* target, const float* w, int M, int V, float* lse,
                                  int64_t* argmax, float* row_loss, float* loss_sum, cvc_stream_t stream) {
     if (!logits || !target || !w || !lse || !row_loss || !loss_sum || M < 1 || V < 1) return CVC_E_BADARG;
-    hipLaunchKernelGGL(vocab_nll_fwd_kernel, dim3(M), dim3(WG), 0, (hipStream_t)stream, logits, target, w, V, lse, argmax,
-                       row_loss);
+    hipLaunchKernelGGL(vocab_nll_fwd_kernel<false>, dim3(M), dim3(WG), 0, (hipStream_t)stream, logits, target, w, V, lse, argmax,
+                       row_loss, 0.f, (float*)nullptr);
     hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_loss, M, loss_sum);
+    return cvc_launch_status();
+}
+
+// eps in [0, 1) and finite (a NaN fails both comparisons' complement)
+static bool smoothing_ok(float eps) { return eps >= 0.f && eps < 1.f; }
+
+// cvc_vocab_nll_fwd with label smoothing; row_nll / nll_sum: the unsmoothed rows and their sum (both or neither)
+extern "C" int cvc_vocab_nll_ls_fwd(const float* logits, const int64_t* target, const float* w, int M, int V, float eps, float* lse,
+                                    int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll, float* nll_sum,
+                                    cvc_stream_t stream) {
+    if (!logits || !target || !w || !lse || !row_loss || !loss_sum || M < 1 || V < 1 || !smoothing_ok(eps) || !row_nll != !nll_sum)
+        return CVC_E_BADARG;
+    hipLaunchKernelGGL(vocab_nll_fwd_kernel<true>, dim3(M), dim3(WG), 0, (hipStream_t)stream, logits, target, w, V, lse, argmax,
+                       row_loss, eps, row_nll);
+    hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_loss, M, loss_sum);
+    if (row_nll) hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_nll, M, nll_sum);
     return cvc_launch_status();
 }
 
@@ -628,16 +686,39 @@ extern "C" int cvc_vocab_head_nll_fwd(const float* parts, int nparts, long long 
     if (!parts || nparts < 1 || !target || !w || !pre || !row_loss || !loss_sum || M < 1 || V < 1 || V > WG * NLL_CACHE || ld < V ||
         ld_pre < V)
         return CVC_E_BADARG;
-    hipLaunchKernelGGL(vocab_head_nll_kernel, dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, ld, bias, target, w, V,
-                       pre, ld_pre, argmax, row_loss);
+    hipLaunchKernelGGL(vocab_head_nll_kernel<false>, dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, ld, bias, target,
+                       w, V, pre, ld_pre, argmax, row_loss, 0.f, (float*)nullptr);
     hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_loss, M, loss_sum);
+    return cvc_launch_status();
+}
+
+// cvc_vocab_head_nll_fwd with label smoothing; row_nll / nll_sum: the unsmoothed rows and their sum (both or neither)
+extern "C" int cvc_vocab_head_nll_ls_fwd(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
+                                         const int64_t* target, const float* w, int M, int V, float eps, float* pre, int ld_pre,
+                                         int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll, float* nll_sum,
+                                         cvc_stream_t stream) {
+    if (!parts || nparts < 1 || !target || !w || !pre || !row_loss || !loss_sum || M < 1 || V < 1 || V > WG * NLL_CACHE || ld < V ||
+        ld_pre < V || !smoothing_ok(eps) || !row_nll != !nll_sum)
+        return CVC_E_BADARG;
+    hipLaunchKernelGGL(vocab_head_nll_kernel<true>, dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, ld, bias, target,
+                       w, V, pre, ld_pre, argmax, row_loss, eps, row_nll);
+    hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_loss, M, loss_sum);
+    if (row_nll) hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_nll, M, nll_sum);
     return cvc_launch_status();
 }
 
 extern "C" int cvc_vocab_nll_bwd(const float* logits, const float* lse, const int64_t* target, const float* w,
                                  const float* g, int M, int V, float* d_logits, cvc_stream_t stream) {
     if (!logits || !lse || !target || !w || !g || !d_logits || M < 1 || V < 1) return CVC_E_BADARG;
-    hipLaunchKernelGGL(vocab_nll_bwd_kernel, dim3((V + WG - 1) / WG, M), dim3(WG), 0, (hipStream_t)stream, logits, lse,
-                       target, w, g, V, d_logits);
+    hipLaunchKernelGGL(vocab_nll_bwd_kernel<false>, dim3((V + WG - 1) / WG, M), dim3(WG), 0, (hipStream_t)stream, logits, lse,
+                       target, w, g, V, d_logits, 0.f);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_vocab_nll_ls_bwd(const float* logits, const float* lse, const int64_t* target, const float* w,
+                                    const float* g, int M, int V, float eps, float* d_logits, cvc_stream_t stream) {
+    if (!logits || !lse || !target || !w || !g || !d_logits || M < 1 || V < 1 || !smoothing_ok(eps)) return CVC_E_BADARG;
+    hipLaunchKernelGGL(vocab_nll_bwd_kernel<true>, dim3((V + WG - 1) / WG, M), dim3(WG), 0, (hipStream_t)stream, logits, lse,
+                       target, w, g, V, d_logits, eps);
     return cvc_launch_status();
 }

@@ -204,44 +204,67 @@ class _VocabHeadNLL(torch.autograd.Function):
     backward is pre = w * (softmax - onehot), which the backward scales by the upstream scalar and feeds to nn.Linear's products."""
 
     @staticmethod
-    def compute(x, weight, bias, target, w):
-        """the forward's arithmetic: -> (loss [1], argmax [M], pre [M, V])"""
+    def compute(x, weight, bias, target, w, eps=0.0):
+        """the forward's arithmetic: -> (loss [1], argmax [M], pre [M, V]); with label smoothing eps > 0 the loss and pre are the
+        smoothed criterion's and the tuple goes on with (unsmoothed loss [1], eps)"""
         parts = hip.tile_mm(_rows(x), hip.weight_operand(weight), parts_only=True)
-        return hip.vocab_head_nll_fwd(parts, bias, target.contiguous(), w.contiguous())
+        if eps == 0.0:
+            return hip.vocab_head_nll_fwd(parts, bias, target.contiguous(), w.contiguous())
+        return (*hip.vocab_head_nll_ls_fwd(parts, bias, target.contiguous(), w.contiguous(), eps), eps)
 
     @staticmethod
-    def forward(ctx, x, weight, bias, target, w, done):
+    def forward(ctx, x, weight, bias, target, w, done, eps):
         # done: compute()'s result on the same x, formed earlier (the argmax was needed before x's final graph node existed:
         # cvc.train_loops._Loop, joint back-propagation) -- this node then only attaches the backward
         x = _rows(x)
-        loss, amax, pre = done if done is not None else _VocabHeadNLL.compute(x, weight, bias, target, w)
+        if done is not None and (done[4] if len(done) > 3 else 0.0) != eps:
+            raise RuntimeError(f"vocab_head_nll: `done` was computed with label_smoothing = {done[4] if len(done) > 3 else 0.0}, this "
+                               f"call asks for {eps}")
+        res = done if done is not None else _VocabHeadNLL.compute(x, weight, bias, target, w, eps)
+        loss, amax, pre = res[:3]
+        nll = res[3] if len(res) > 3 else None          # (the unsmoothed sum; without smoothing it is the loss itself)
         ctx.save_for_backward(weight, bias, x, pre)
         ctx.has_bias = bias is not None
         ctx.key = ("linear", weight.data_ptr())
         if weight.requires_grad:
             _BATCHER.note_use(ctx.key)
         ctx.mark_non_differentiable(amax)
-        return loss, amax
+        if nll is None:
+            return loss, amax
+        ctx.mark_non_differentiable(nll)
+        return loss, amax, nll
 
     @staticmethod
-    def backward(ctx, g, _g_amax):
+    def backward(ctx, g, _g_amax, _g_nll=None):
         weight, bias, x, pre = ctx.saved_tensors
         dy = hip.scale_by_scalar(pre, g.contiguous().reshape(1))
         ni = ctx.needs_input_grad
         d_w, d_b, d_x = _linear_backward(ctx, weight, bias, [x], dy, (ni[1], ni[2], ni[0]))
-        return d_x, d_w, d_b, None, None, None
+        return d_x, d_w, d_b, None, None, None, None
 
 
-def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, done=None) -> Tuple[Tensor, Tensor]:
+def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, done=None, label_smoothing: float = 0.0,
+                   return_nll: bool = False):
     """-> (sum_m w[m] * -log_softmax(x W^T + b)[m, target[m]] as a [1] tensor, argmax over V per row [M] int64); x [M, K]
-    done: vocab_head_nll_compute()'s result for the same x"""
-    return _VocabHeadNLL.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), done)
+    done: vocab_head_nll_compute()'s result for the same x (and the same label_smoothing: another one is refused)
+    label_smoothing = eps in [0, 1): the loss of the target distribution (1 - eps) onehot + eps / V, what
+    torch.nn.functional.cross_entropy(label_smoothing=eps) computes; 0 is the one-hot criterion on its own kernel, no other launch.
+    return_nll: a third result, the UNSMOOTHED sum as a [1] tensor without a graph (eps = 0: the loss, detached)"""
+    eps = hip.check_label_smoothing(label_smoothing)
+    if eps == 0.0:
+        loss, amax = _VocabHeadNLL.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), done, 0.0)
+        return (loss, amax, loss.detach()) if return_nll else (loss, amax)
+    loss, amax, nll = _VocabHeadNLL.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), done, eps)
+    return (loss, amax, nll) if return_nll else (loss, amax)
 
 
-def vocab_head_nll_compute(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor):
-    """the arithmetic of vocab_head_nll without its graph node (-> an opaque `done` for vocab_head_nll; done[1] is the argmax)"""
+def vocab_head_nll_compute(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, label_smoothing: float = 0.0):
+    """the arithmetic of vocab_head_nll without its graph node (-> an opaque `done` for vocab_head_nll; done[1] is the argmax).
+    `done` carries label_smoothing: vocab_head_nll refuses one computed with another value"""
+    eps = hip.check_label_smoothing(label_smoothing)
     with torch.no_grad():
-        return _VocabHeadNLL.compute(x.detach(), weight.detach(), None if bias is None else bias.detach(), target.reshape(-1), w.reshape(-1))
+        return _VocabHeadNLL.compute(x.detach(), weight.detach(), None if bias is None else bias.detach(), target.reshape(-1), w.reshape(-1),
+                                     eps)
 
 
 def vocab_head_nll_ok(x: Tensor, weight: Tensor) -> bool:
@@ -682,31 +705,56 @@ class _MaskedNLLSum(torch.autograd.Function):
         return hip.nll_bwd(target, w, g.contiguous().reshape(1), ctx.V), None, None
 
 
-def masked_nll_sum(logp: Tensor, target: Tensor, w: Tensor) -> Tensor:
-    return _MaskedNLLSum.apply(logp, target.reshape(-1), w.reshape(-1))
+def masked_nll_sum(logp: Tensor, target: Tensor, w: Tensor, label_smoothing: float = 0.0) -> Tensor:
+    """sum_m w[m] * -logp[m, target[m]]; with label_smoothing = eps in (0, 1) the smoothed target's
+    sum_m w[m] * (-(1 - eps) logp[m, target[m]] - (eps / V) sum_v logp[m, v]).  This log-prob form is not on the training pass's hot
+    path: the uniform term is the library's row reduction of the device tensor beside the NLL kernel."""
+    eps = hip.check_label_smoothing(label_smoothing)
+    total = _MaskedNLLSum.apply(logp, target.reshape(-1), w.reshape(-1))
+    if eps == 0.0:
+        return total
+    if not logp.is_cuda:
+        raise RuntimeError("cvc.functional.masked_nll_sum: logp must live on the GPU (no CPU fallback for the hot path)")
+    uniform = -(logp.sum(1) * w.reshape(-1)).sum().reshape(1)
+    return (1.0 - eps) * total + (eps / logp.shape[1]) * uniform
 
 
 class _VocabNLL(torch.autograd.Function):
     """Masked NLL sum + per-row argmax straight from raw logits: log_softmax, the NLL gather and the cycle's
-    argmax cut (captioner.py:266, :313; misc/utils.py:139-146) in one pass, no [M, V] log-prob matrix."""
+    argmax cut (captioner.py:266, :313; misc/utils.py:139-146) in one pass, no [M, V] log-prob matrix.
+    eps > 0: the label-smoothed criterion (cvc_vocab_nll_ls_fwd / _bwd), a third result: the unsmoothed sum."""
 
     @staticmethod
-    def forward(ctx, logits, target, w):
+    def forward(ctx, logits, target, w, eps):
         logits, target, w = logits.contiguous(), target.contiguous(), w.contiguous()
-        loss, lse, amax = hip.vocab_nll_fwd(logits, target, w)
+        ctx.eps = eps
+        if eps == 0.0:
+            loss, lse, amax = hip.vocab_nll_fwd(logits, target, w)
+            ctx.save_for_backward(logits, lse, target, w)
+            ctx.mark_non_differentiable(amax)
+            return loss, amax
+        loss, lse, amax, nll = hip.vocab_nll_ls_fwd(logits, target, w, eps)
         ctx.save_for_backward(logits, lse, target, w)
-        ctx.mark_non_differentiable(amax)
-        return loss, amax
+        ctx.mark_non_differentiable(amax, nll)
+        return loss, amax, nll
 
     @staticmethod
-    def backward(ctx, g, _g_amax):
+    def backward(ctx, g, _g_amax, _g_nll=None):
         logits, lse, target, w = ctx.saved_tensors
-        return hip.vocab_nll_bwd(logits, lse, target, w, g.contiguous().reshape(1)), None, None
+        if ctx.eps == 0.0:
+            return hip.vocab_nll_bwd(logits, lse, target, w, g.contiguous().reshape(1)), None, None, None
+        return hip.vocab_nll_ls_bwd(logits, lse, target, w, g.contiguous().reshape(1), ctx.eps), None, None, None
 
 
-def vocab_nll(logits: Tensor, target: Tensor, w: Tensor) -> Tuple[Tensor, Tensor]:
-    """-> (sum_m w[m] * -log_softmax(logits)[m, target[m]]  as a [1] tensor,  argmax over V per row [M] int64)."""
-    return _VocabNLL.apply(logits, target.reshape(-1), w.reshape(-1))
+def vocab_nll(logits: Tensor, target: Tensor, w: Tensor, label_smoothing: float = 0.0, return_nll: bool = False):
+    """-> (sum_m w[m] * -log_softmax(logits)[m, target[m]]  as a [1] tensor,  argmax over V per row [M] int64).
+    label_smoothing, return_nll: as vocab_head_nll"""
+    eps = hip.check_label_smoothing(label_smoothing)
+    if eps == 0.0:
+        loss, amax = _VocabNLL.apply(logits, target.reshape(-1), w.reshape(-1), 0.0)
+        return (loss, amax, loss.detach()) if return_nll else (loss, amax)
+    loss, amax, nll = _VocabNLL.apply(logits, target.reshape(-1), w.reshape(-1), eps)
+    return (loss, amax, nll) if return_nll else (loss, amax)
 
 
 class _Grounder(torch.autograd.Function):

@@ -274,6 +274,10 @@ SIGNATURES = {
     "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
     # grounding F1 of generated captions: picks per object word and frame, per-class counters (csrc/grounding.hip; building block)
     "cvc_grounding_f1": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    # label smoothing in the vocabulary criterion: the fused head, the two-step form and its backward (csrc/vocab.hip; building blocks)
+    "cvc_vocab_head_nll_ls_fwd": [_P, _I, _LL, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_ls_fwd": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_ls_bwd": [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -319,7 +323,7 @@ BLOCKS = {
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
-    "cvc_grounding_f1"}
+    "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -989,6 +993,57 @@ def vocab_head_nll_fwd(parts, bias, target, w):
     _check(lib().cvc_vocab_head_nll_fwd(_dev(parts), ks, M * V, V, _dev(bias), _dev(target, torch.int64), _dev(w), M, V, pre.data_ptr(), V,
                                         _dev(amax, torch.int64), _dev(row_loss), _dev(loss), _stream()), "cvc_vocab_head_nll_fwd")
     return loss, amax, pre
+
+
+def check_label_smoothing(eps, what="label_smoothing") -> float:
+    """eps as a float in [0, 1) -- the share of the target distribution spread uniformly over the vocabulary -- or ValueError (before
+    any tensor is touched or kernel launched)"""
+    try:
+        e = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number in [0, 1), got {eps!r}") from None
+    if not (0.0 <= e < 1.0):                 # (a NaN fails the comparison)
+        raise ValueError(f"{what} must be in [0, 1), got {eps!r}")
+    return e
+
+
+def vocab_nll_ls_fwd(logits, target, w, eps: float, want_argmax=True):
+    """vocab_nll_fwd with label smoothing eps -> loss_sum [1] (smoothed), lse [M], argmax [M] int64 (or None), nll_sum [1] (unsmoothed)"""
+    eps = check_label_smoothing(eps)
+    M, V = logits.shape
+    dev = logits.device
+    lse = torch.empty(M, device=dev, dtype=torch.float32)
+    rows = torch.empty(2, M, device=dev, dtype=torch.float32)
+    loss, nll = torch.empty(1, device=dev, dtype=torch.float32), torch.empty(1, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64) if want_argmax else None
+    _check(lib().cvc_vocab_nll_ls_fwd(_dev(logits), _dev(target, torch.int64), _dev(w), M, V, eps, _dev(lse), _dev(amax, torch.int64),
+                                      _dev(rows), _dev(loss), rows[1].data_ptr(), _dev(nll), _stream()), "cvc_vocab_nll_ls_fwd")
+    return loss, lse, amax, nll
+
+
+def vocab_head_nll_ls_fwd(parts, bias, target, w, eps: float):
+    """vocab_head_nll_fwd with label smoothing eps -> loss_sum [1] (smoothed), argmax [M], pre [M, V] (aliasing slab 0; the
+    smoothed loss's gradient), nll_sum [1] (unsmoothed)"""
+    eps = check_label_smoothing(eps)
+    ks, M, V = parts.shape
+    dev = parts.device
+    rows = torch.empty(2, M, device=dev, dtype=torch.float32)
+    loss, nll = torch.empty(1, device=dev, dtype=torch.float32), torch.empty(1, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64)
+    pre = parts[0]
+    _check(lib().cvc_vocab_head_nll_ls_fwd(_dev(parts), ks, M * V, V, _dev(bias), _dev(target, torch.int64), _dev(w), M, V, eps,
+                                           pre.data_ptr(), V, _dev(amax, torch.int64), _dev(rows), _dev(loss), rows[1].data_ptr(),
+                                           _dev(nll), _stream()), "cvc_vocab_head_nll_ls_fwd")
+    return loss, amax, pre, nll
+
+
+def vocab_nll_ls_bwd(logits, lse, target, w, g, eps: float):
+    eps = check_label_smoothing(eps)
+    M, V = logits.shape
+    d = torch.empty_like(logits)
+    _check(lib().cvc_vocab_nll_ls_bwd(_dev(logits), _dev(lse), _dev(target, torch.int64), _dev(w), _dev(g), M, V, eps, _dev(d),
+                                      _stream()), "cvc_vocab_nll_ls_bwd")
+    return d
 
 
 def scale_by_scalar(x, g):

@@ -82,6 +82,11 @@ def build_parser():
     parser.add_argument("--scheduled_sampling_max_prob", type=float, default=0.25, help="up to this share")
     parser.add_argument("--scheduled_sampling_temperature", type=float, default=1.0, help="temperature of the sampled words")
     parser.add_argument("--scheduled_sampling_seed", type=int, default=1, help="seed of the sampled words' noise and of the coins")
+    # label smoothing of the cross-entropy steps (both language criteria of a training pass; cvc.functional.vocab_head_nll)
+    parser.add_argument("--label_smoothing", type=float, default=0.0,
+                        help="train against (1 - eps) one-hot + eps / vocabulary (torch's cross_entropy label_smoothing), eps in [0, 1); "
+                             "0 = off.  Self-critical steps, scoring and evaluation are never smoothed; with eps > 0 the display line "
+                             "also shows the unsmoothed NLL")
     # consensus (minimum-Bayes-risk) caption selection at evaluation (model._sample(consensus=...); DecodeEngine.consensus)
     parser.add_argument("--consensus", choices=("off", "samples", "beam"), default="off",
                         help="keep per clip the candidate with the highest mean CIDEr-D against the clip's other candidates (training "
@@ -93,6 +98,12 @@ def build_parser():
     return parser
 
 
+def check_label_smoothing_flag(eps):
+    """--label_smoothing lies in [0, 1) (a NaN does not): anything else ends the run with a message, before any set-up"""
+    if not 0.0 <= eps < 1.0:
+        raise SystemExit("--label_smoothing must lie in [0, 1), got %r" % (eps,))
+
+
 def main(argv=None, sample=None, score=None):
     """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p) or (n, temperature, seed, top_k, top_p, consensus) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
@@ -100,6 +111,7 @@ def main(argv=None, sample=None, score=None):
     (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
     parser = build_parser()
     opt = parser.parse_args(argv)
+    check_label_smoothing_flag(opt.label_smoothing)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
     opt.test_mode = opt.val_split in ["testing", "hidden_test"]                       # reference main.py:57
@@ -257,7 +269,8 @@ def main(argv=None, sample=None, score=None):
             infos = {"iter": (epoch + 1) * max(len(loader) - 1, 0), "epoch": epoch, "best_val_score": best, "vocab": full.itow,
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
-                         "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history)}
+                         "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history),
+                         "nll_history": dict(trainer.nll_history)}
             with open(os.path.join(save_dir, "infos_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(infos, f)
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:

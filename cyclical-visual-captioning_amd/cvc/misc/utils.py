@@ -79,36 +79,47 @@ def _text_mask(target):
     return torch.cat([torch.ones_like(m[:, :1]), m[:, :-1]], 1)   # includes the first EOS (:135-137)
 
 
-def _masked_nll_mean(txt_input, target):
+def _masked_nll_mean(txt_input, target, label_smoothing=0.0):
     mask = _text_mask(target)
     w = mask.reshape(-1).to(torch.float32)
-    total = F_.masked_nll_sum(txt_input, target.reshape(-1), w)
+    total = F_.masked_nll_sum(txt_input, target.reshape(-1), w, label_smoothing=label_smoothing)
     count = w.sum()
     return (total / count).reshape(())
 
 
-def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None):
+def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None, label_smoothing=0.0, want_nll=False):
     """Same value as _masked_nll_mean(log_softmax(logits), target), plus the per-row argmax, from one fused pass.
     t_major: the rows of `logits` are ordered t * B + b (the C-driven training loops' outputs) instead of b * T + t.
-    row_weight: see _masked_nll_mean_from_head."""
+    row_weight, label_smoothing, want_nll: see _masked_nll_mean_from_head."""
     w = _text_mask(target).to(torch.float32)
     if row_weight is not None:
         total, argmax = F_.vocab_nll(logits, (target.t() if t_major else target).reshape(-1), row_weight.reshape(-1))
-        return (total / w.sum()).reshape(()), (argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
-    if t_major:
-        total, argmax = F_.vocab_nll(logits, target.t().reshape(-1), w.t().reshape(-1))
-        return (total / w.sum()).reshape(()), argmax.view(target.shape[1], target.shape[0]).t()
-    total, argmax = F_.vocab_nll(logits, target.reshape(-1), w.reshape(-1))
-    return (total / w.sum()).reshape(()), argmax.view(target.shape)
+        nll = total.detach()
+    elif t_major:
+        total, argmax, nll = F_.vocab_nll(logits, target.t().reshape(-1), w.t().reshape(-1), label_smoothing=label_smoothing,
+                                          return_nll=True)
+    else:
+        total, argmax, nll = F_.vocab_nll(logits, target.reshape(-1), w.reshape(-1), label_smoothing=label_smoothing, return_nll=True)
+    count = w.sum()
+    res = ((total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
+    return (*res, (nll / count).reshape(())) if want_nll else res
 
 
-def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False, row_weight=None):
+def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False, row_weight=None,
+                               label_smoothing=0.0, want_nll=False):
     """_masked_nll_mean_from_logits(x W^T + b, target) with the criterion folded into the vocabulary head's GEMM finish: the logits
     are never materialised (cvc.functional.vocab_head_nll); falls back to the two-step form for shapes that kernel does not take.
     row_weight: a real weight per row of x (in x's row order, any sign, 0 where the loss mask is 0) in place of the 0 / 1 loss mask:
-    -sum_r row_weight[r] log p(target[r]) / sum(mask) -- the self-critical loss, row_weight = advantage x mask.  None: the mask."""
+    -sum_r row_weight[r] log p(target[r]) / sum(mask) -- the self-critical loss, row_weight = advantage x mask.  None: the mask.
+    label_smoothing: eps in [0, 1), the target distribution (1 - eps) onehot + eps / V (cvc.functional.vocab_head_nll).  The
+    self-critical loss IGNORES it: with row_weight the criterion is the one-hot one whatever eps is, because REINFORCE's gradient
+    is advantage x grad log p(sampled word) -- it needs the log-prob itself, not a regularised target.
+    want_nll: a third result, the UNSMOOTHED mean as a scalar without a graph (the figure to log beside a smoothed loss)."""
+    if row_weight is not None:
+        label_smoothing = 0.0
     if not F_.vocab_head_nll_ok(x, weight):
-        return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major, row_weight=row_weight)
+        return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major, row_weight=row_weight,
+                                            label_smoothing=label_smoothing, want_nll=want_nll)
     # the loss mask, its count and the t-major copies depend on the target alone: both heads of a cyclical pass (decode,
     # reconstruction) score against the same target tensor, so they are formed once and kept on it
     pre = getattr(target, "_cvc_nll_pre", None)
@@ -121,26 +132,42 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
     if row_weight is not None:
         wf = row_weight.reshape(-1).contiguous()
     if compute_only:       # -> (opaque result for a later call with done=, the argmax words)
-        done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf)
+        done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf, label_smoothing=label_smoothing)
         argmax = done[1]
         return done, (argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
-    total, argmax = F_.vocab_head_nll(x, weight, bias, tf, wf, done)
-    if t_major:
-        return (total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t()
-    return (total / count).reshape(()), argmax.view(target.shape)
+    total, argmax, nll = F_.vocab_head_nll(x, weight, bias, tf, wf, done, label_smoothing=label_smoothing, return_nll=True)
+    res = ((total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
+    return (*res, (nll / count).reshape(())) if want_nll else res
+
+
+def _opt_label_smoothing(opt, label_smoothing):
+    """the criteria's eps: the constructor argument, else opt.label_smoothing, else 0; validated (ValueError outside [0, 1))"""
+    from .. import hip
+    if label_smoothing is None:
+        label_smoothing = getattr(opt, "label_smoothing", 0.0) if opt is not None else 0.0
+    return hip.check_label_smoothing(0.0 if label_smoothing is None else label_smoothing)
 
 
 class LMCriterion(nn.Module):
-    """reference misc/utils.py:127-172"""
+    """reference misc/utils.py:127-172.  label_smoothing (argument, else opt.label_smoothing, else 0): the language loss is the
+    smoothed cross entropy of torch.nn.functional.cross_entropy(label_smoothing=); after a from_logits / from_head call with it > 0
+    last_nll is the UNSMOOTHED mean NLL of that call (a device scalar without a graph), else None."""
 
-    def __init__(self, opt):
+    def __init__(self, opt, label_smoothing=None):
         super().__init__()
         self.vocab_size = opt.vocab_size
+        self.label_smoothing = _opt_label_smoothing(opt, label_smoothing)
+        self.last_nll = None
+
+    def _keep(self, res):
+        """(loss, argmax[, unsmoothed mean -- asked for when smoothing is on]) -> (loss, argmax); the third stays on the module"""
+        self.last_nll = res[2] if len(res) > 2 else None
+        return res[0], res[1]
 
     def forward(self, txt_input, att2_weights, ground_weights, target, att2_target, input_seq):
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0                  # reference :134 (host check; skipped under capture)
-        loss = _masked_nll_mean(txt_input, target)
+        loss = _masked_nll_mean(txt_input, target, self.label_smoothing)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target))
 
     def from_logits(self, logits, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False):
@@ -148,25 +175,27 @@ class LMCriterion(nn.Module):
         SURVEY section 8(f) rank 2: the criterion folded into the vocabulary head's epilogue pass."""
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
-        loss, argmax = _masked_nll_mean_from_logits(logits, target, t_major)
+        loss, argmax = self._keep(_masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing,
+                                                               want_nll=self.label_smoothing > 0))
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
     def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None, row_weight=None):
         """from_logits() fed the vocabulary head's INPUT x [rows, R] and the head module (nn.Linear): the head's GEMM and the
         criterion run as one op, no logits tensor.  done: head_words()'s first result for the same x (the arithmetic then is not
-        repeated)."""
+        repeated).  row_weight: the self-critical loss, which ignores label smoothing (_masked_nll_mean_from_head)."""
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
-        loss, argmax = _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done, row_weight=row_weight)
+        loss, argmax = self._keep(_masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done, row_weight=row_weight,
+                                                             label_smoothing=self.label_smoothing, want_nll=self.label_smoothing > 0))
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
-    @staticmethod
-    def head_words(x, head, target, t_major=False):
+    def head_words(self, x, head, target, t_major=False):
         """the head + criterion arithmetic of from_head() ahead of its graph node: -> (done, argmax words [B, T]), or None for
         shapes the fused head does not take"""
         if not F_.vocab_head_nll_ok(x, head.weight):
             return None
-        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, compute_only=True)
+        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, compute_only=True,
+                                          label_smoothing=self.label_smoothing)
 
     @staticmethod
     def attention_losses(att2_weights, ground_weights, att2_target):
@@ -185,16 +214,22 @@ class LMCriterion(nn.Module):
 
 
 class LanguageCriterion(nn.Module):
-    """reference misc/utils.py:175-192"""
+    """reference misc/utils.py:175-192.  label_smoothing (argument, else opt.label_smoothing, else 0): as LMCriterion; a call with
+    row_weight (the self-critical loss) ignores it."""
+
+    def __init__(self, opt=None, label_smoothing=None):
+        super().__init__()
+        self.label_smoothing = _opt_label_smoothing(opt, label_smoothing)
 
     def forward(self, txt_input, target):
-        return _masked_nll_mean(txt_input, target)
+        return _masked_nll_mean(txt_input, target, self.label_smoothing)
 
     def from_logits(self, logits, target, t_major=False):
-        return _masked_nll_mean_from_logits(logits, target, t_major)[0]
+        return _masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing)[0]
 
     def from_head(self, x, head, target, t_major=False, row_weight=None):
-        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, row_weight=row_weight)[0]
+        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, row_weight=row_weight,
+                                          label_smoothing=self.label_smoothing)[0]
 
 
 def bbox_overlaps(rois, gt_box, frm_mask):

@@ -89,7 +89,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.attended_roi_decoder_core = AttenedDecoderCore(opts, self.decoder_core.att_lstm, self.decoder_core.lang_lstm)
         self.critLM = utils.LMCriterion(opts)
         self.unk_idx = int(opts.wtoi['UNK'])
-        self.xe_criterion = utils.LanguageCriterion()
+        self.xe_criterion = utils.LanguageCriterion(opts)
+        # label smoothing of the two language criteria of a training pass (loop A's decode loss, loop C's reconstruction loss): both
+        # criteria read opts.label_smoothing; model.label_smoothing = eps changes both.  With eps > 0 a training pass leaves loop A's
+        # UNSMOOTHED mean NLL here as a device scalar (no graph), else None.  The self-critical loss and every scoring / evaluation
+        # path are not smoothed.
+        self.last_nll = None
         self.beam_size = int(getattr(opts, "beam_size", 1))
         self.use_hip_graph = bool(getattr(opts, "hip_graph", False))
         # decoding rule of _sample: sample_max = 1 takes the arg-max word (greedy / beam); sample_max = 0 samples from
@@ -202,6 +207,14 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         instead of gt_caption[:, :T] -- scheduled sampling; targets, label glue, the grounder's class inputs and loops B / C are the
         ground truth's.  None: teacher forcing, as always."""
         F_.new_step()
+        if lang_eval and teacher_forcing and self.label_smoothing > 0:
+            # an evaluation pass reports the model's true log-probs: label smoothing is the training criterion's alone
+            eps, self.label_smoothing = self.label_smoothing, 0.0
+            try:
+                return self._forward_3_loops(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes,
+                                             region_feats, frm_mask, sample_idx, pnt_mask, ss_inputs)
+            finally:
+                self.label_smoothing = eps
         if lang_eval is False or teacher_forcing:
             return self._forward_3_loops(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes,
                                          region_feats, frm_mask, sample_idx, pnt_mask, ss_inputs)
@@ -321,6 +334,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # criteria fused with log_softmax and the argmax cut of :313 (one pass over the logits, no [B,T,V] log-probs)
         lm_loss, att2_loss, ground_loss, output_seq = self.critLM.from_logits(
             lang_logits, att2_weights, ground_weights, target, roi_labels[:, :T, :].clone(), input_seq[:, 1:T + 1, 0].clone())
+        self.last_nll = self.critLM.last_nll
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
 
@@ -349,6 +363,15 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         lm_recon_loss = self.xe_criterion.from_logits(self._logits(torch.stack(rec_outputs, 1).view(B * T, -1)), target)
         return (lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1),
                 lm_recon_loss.reshape(1))
+
+    @property
+    def label_smoothing(self) -> float:
+        return self.critLM.label_smoothing
+
+    @label_smoothing.setter
+    def label_smoothing(self, eps):
+        eps = hip.check_label_smoothing(eps)
+        self.critLM.label_smoothing = self.xe_criterion.label_smoothing = eps
 
     # ------------------------------------------------------------------ training pass on the C-driven loops
     def _loop_plan(self, B, like):
@@ -435,6 +458,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         lm_loss, att2_loss, ground_loss, output_seq = self.critLM.from_head(
             out_a.view(T * B, R), self.logit, att2_weights, ground_weights, target, roi_labels[:, :T, :], input_seq[:, 1:T + 1, 0],
             t_major=True, done=done)
+        self.last_nll = self.critLM.last_nll
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
         if out_c is None:

@@ -127,6 +127,11 @@ class Trainer:
         self.ss_seed = int(getattr(opts, "ss_seed", 1))
         self._ss_steps = 0
         self.last_ss = None
+        # ---- label smoothing of the cross-entropy steps (the model's criteria: cvc.main --label_smoothing): fixed when the trainer is
+        # built -- a captured step holds it as a launch argument.  With eps > 0 every cross-entropy step's result carries one more
+        # element at its END, loop A's unsmoothed mean NLL (model.last_nll), and train() logs it beside the smoothed LM loss
+        self.label_smoothing = float(getattr(getattr(model, "module", model), "label_smoothing", 0.0))
+        self.nll_history = {}         # epoch -> the mean unsmoothed NLL of every display interval (label_smoothing > 0)
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -182,6 +187,16 @@ class Trainer:
             loss = 0.0 * lm_loss
         return loss, lm_loss, att2_loss, cls_loss, lm_recon
 
+    def _nll_tail(self):
+        """(loop A's unsmoothed mean NLL of the pass that just ran,) with label smoothing on, else ()"""
+        if not self.label_smoothing > 0:
+            return ()
+        model = getattr(self.model, "module", self.model)
+        if float(model.label_smoothing) != self.label_smoothing:
+            raise RuntimeError(f"Trainer: the model's label_smoothing is {model.label_smoothing}, the trainer was built with "
+                               f"{self.label_smoothing} (captured steps hold it as a launch argument: build a new Trainer)")
+        return (model.last_nll.detach().reshape(()),)
+
     def train_step(self, batch):
         return self.train_step_prepared(self._prepare(batch, True))
 
@@ -195,7 +210,7 @@ class Trainer:
         loss, lm, att2, cls, rec = self.loss_mix(out)
         self._backward_and_update(loss)
         self._weights_changed()
-        return loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach()
+        return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), *self._nll_tail())
 
     def _ss_step_prepared(self, b):
         """The scheduled-sampling step (Bengio et al. 2015; model.ss_prob > 0): the encoder once in eval mode without autograd, one
@@ -221,6 +236,7 @@ class Trainer:
             model.train(was_training)
         out = self._call(b, ss_inputs=ss_inputs)
         loss, lm, att2, cls, rec = self.loss_mix(out)
+        nll = self._nll_tail()
         self._backward_and_update(loss)
         model.refresh_decode_weights()
         T = took.size(1)
@@ -228,7 +244,7 @@ class Trainer:
         self.last_ss = dict(inputs=ss_inputs, took=took, given_logprob=given_logprob, seed=seed, share=share,
                             prob=float(model.ss_prob))
         self._ss_steps += 1
-        return loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach()
+        return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), *nll)
 
     def _backward_and_update(self, loss, set_to_none=True):
         """zero_grad -> backward -> [gradient exchange] -> clip_grad_norm_ -> step (trainer.py:116-122).  With a GradReducer
@@ -346,6 +362,7 @@ class Trainer:
     def _core_step(self, b):
         out = self._call(b)
         loss, lm, att2, cls, rec = self.loss_mix(out)
+        nll = self._nll_tail()
         self._backward_and_update(loss, set_to_none=False)
         res = torch.stack([loss.detach().reshape(()), lm.detach().reshape(()), att2.detach().reshape(()),
                            cls.detach().reshape(()), rec.detach().reshape(())])
@@ -355,7 +372,11 @@ class Trainer:
             # element; the word is cleared at the END of the step (whoever sets it before a step voids that step: tests do)
             void = st != 0
             res = torch.cat((torch.where(void, torch.zeros_like(res), res), void.to(res.dtype)))
+            if nll:                       # (label smoothing: the unsmoothed NLL goes last, behind the layout everybody knows)
+                res = torch.cat((res, torch.where(void, torch.zeros_like(nll[0]), nll[0]).reshape(1)))
             st.zero_()
+        elif nll:
+            res = torch.cat((res, nll[0].reshape(1)))
         return res
 
     def train_step_graphed(self, batch):
@@ -364,7 +385,8 @@ class Trainer:
         capturable=True (build_optimizer(..., capturable=True)).  The gradient exchange of a multi-rank GradReducer is part of
         the captured step when it runs on RCCL (backend "nccl": the collectives are issued on the communicator's stream behind
         events of the capturing stream, which stream capture records as graph dependencies); other backends (gloo) cannot be
-        captured.  Returns a static tensor [loss, lm, att2, cls, recon] (clone to keep)."""
+        captured.  Returns a static tensor [loss, lm, att2, cls, recon] (clone to keep); with label smoothing one more element at
+        the end, loop A's unsmoothed mean NLL."""
         self._check_capturable()
         b = self._prepare(batch, True)
         if self._graph is None:
@@ -554,7 +576,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ epoch loops
     def train(self, epoch, tb_logger=None):
-        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled")}
+        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled", "nll")}
         self.model.train()
         end = time.time()
         n_steps = len(self.train_loader) - 1                 # the reference drops the last batch (:55)
@@ -562,6 +584,7 @@ class Trainer:
         # scheduled-sampling epochs (model.ss_prob > 0, set per epoch by cvc.main): eager steps with a rollout in front
         ss = not scst and float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0
         graphed = self.graph_capable() and not scst and not ss
+        smooth = self.label_smoothing > 0 and not scst       # (a last element of every step's result: the unsmoothed NLL)
         self._active_buckets = self.shape_buckets if graphed else 0       # (read by _prepare, which the prefetcher calls)
         # batch k+1 is staged into HBM on a side stream while step k runs
         batches = DevicePrefetcher(self.train_loader, lambda raw: self._prepare(raw, True), self.device, limit=n_steps)
@@ -581,16 +604,21 @@ class Trainer:
             if acc is None:
                 return
             if deferred:
-                sums, cur, flags = torch.cat([acc, last, void_flags[:pending]]).split([6, 6, pending])
+                width = last.numel()
+                sums, cur, flags = torch.cat([acc, last, void_flags[:pending]]).split([width, width, pending])
                 sums, cur, flags = sums.tolist(), cur.tolist(), flags.tolist()
                 void = [i for i, f in enumerate(flags) if f != 0]
                 if void:
                     self.deferred_stats["void_steps"] += len(void)
                     for r in self.rerun_void_steps([kept[i] for i in void]):
                         r = r.tolist()
-                        sums[:5] = [a + b_ for a, b_ in zip(sums[:5], r)]
+                        sums[:5] = [a + b_ for a, b_ in zip(sums[:5], r[:5])]
+                        if smooth:
+                            sums[-1] += r[-1]
                         if void[-1] == pending - 1:
-                            cur[:5] = r
+                            cur[:5] = r[:5]
+                            if smooth:
+                                cur[-1] = r[-1]
                 kept.clear()
             else:
                 sums, cur = torch.stack([acc, last]).tolist()
@@ -601,6 +629,10 @@ class Trainer:
             if ss:                                    # (a sixth element: the share of loop A's inputs that were sampled words)
                 meters["sampled"].update(sums[5] / pending, n * pending)
                 meters["sampled"].val = cur[5]
+            if smooth:                                # (the last element: loop A's unsmoothed mean NLL beside the smoothed LM loss)
+                meters["nll"].update(sums[-1] / pending, n * pending)
+                meters["nll"].val = cur[-1]
+                self.nll_history.setdefault(epoch, []).append(sums[-1] / pending)
             for name, i in (("lm", 1), ("attn", 2), ("cls", 3), ("recon", 4)):
                 meters[name].update(sums[i] / pending, n * pending)
                 meters[name].val = cur[i]
@@ -621,7 +653,8 @@ class Trainer:
                 elif graphed:
                     res = self.train_step_bucketed(b)
                 elif ss:                          # (a sixth element: the step's share of sampled inputs)
-                    res = torch.stack([x.reshape(()) for x in self.train_step_prepared(b)] + [self.last_ss["share"].to(torch.float32)])
+                    vals = [x.reshape(()) for x in self.train_step_prepared(b)]
+                    res = torch.stack(vals[:5] + [self.last_ss["share"].to(torch.float32)] + vals[5:])
                 else:
                     res = torch.stack([x.reshape(()) for x in self.train_step_prepared(b)])
                 acc = res.clone() if acc is None else acc.add_(res)
@@ -638,7 +671,8 @@ class Trainer:
                               epoch, step, n_steps, b=meters["batch"], d=meters["data"], l=meters["lm"], a=meters["attn"],
                               c=meters["cls"], r=meters["recon"]) +
                           ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else '') +
-                          ('\tSampled {s.val:.3f} ({s.avg:.3f})'.format(s=meters["sampled"]) if ss else ''))
+                          ('\tSampled {s.val:.3f} ({s.avg:.3f})'.format(s=meters["sampled"]) if ss else '') +
+                          ('\tNLL {s.val:.4f} ({s.avg:.4f})'.format(s=meters["nll"]) if smooth else ''))
                 else:
                     if deferred and pending >= KEEP_MAX:
                         flush()
@@ -653,6 +687,8 @@ class Trainer:
             tb_logger.add_scalar('train/lm_recon_loss', meters["recon"].avg, epoch)
             if scst:
                 tb_logger.add_scalar('train/scst_reward', meters["reward"].avg, epoch)
+            if smooth:
+                tb_logger.add_scalar('train/lm_nll', meters["nll"].avg, epoch)
 
     def _segment_timestamps(self):
         """{video: {segment: [start, end]}} of the validation segments: the reference reads them from the ANet-Entities

@@ -570,6 +570,28 @@ int cvc_grounding_f1(const int64_t* seq, const float* att, const float* ppls, co
                      const int32_t* word_cls, int rows, int T, int P, int F, int Np, int K, int C, int V, int per_clip,
                      int32_t* pick, int32_t* counts, float* f1, int32_t* table, cvc_stream_t stream);
 
+/* ---- label smoothing in the vocabulary criterion (csrc/vocab.hip; cvc.functional.vocab_head_nll / vocab_nll label_smoothing=).
+ * The three forms of include/cvc_hip.h's criterion with the target distribution (1 - eps) onehot + eps / V of
+ * torch.nn.functional.cross_entropy(label_smoothing=eps); the smoothing mass is uniform over all V ids.  Per row, with
+ * lse = logsumexp(z):
+ *   row_loss = w (lse - (1 - eps) z[t] - (eps / V) sum_v z[v])
+ *   pre[v] / d_logits[v] = (g[0]) w (softmax(z)[v] - (1 - eps) [v == t] - eps / V)
+ *   row_nll  = w (lse - z[t]), the unsmoothed value (logging), nll_sum[0] its sum over the rows in loss_sum's fixed order;
+ *     row_nll and nll_sum are nullable, both or neither.
+ * Every other argument, the size limits (fused head: V <= 8192) and the outputs are those of cvc_vocab_head_nll_fwd,
+ * cvc_vocab_nll_fwd and cvc_vocab_nll_bwd.  The row's sum of logits is one more fixed-order block reduction: a row stays
+ * bit-reproducible.  eps == 0 gives the bits of the unsmoothed entries.  w == 0 rows write zeros.
+ * Null pointers (but bias, argmax, row_nll / nll_sum), eps outside [0, 1) or not finite, the unsmoothed entries' size limits:
+ * CVC_E_BADARG, before any launch. */
+int cvc_vocab_head_nll_ls_fwd(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
+                              const int64_t* target, const float* w, int M, int V, float eps, float* pre, int ld_pre,
+                              int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll, float* nll_sum,
+                              cvc_stream_t stream);
+int cvc_vocab_nll_ls_fwd(const float* logits, const int64_t* target, const float* w, int M, int V, float eps, float* lse,
+                         int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll, float* nll_sum, cvc_stream_t stream);
+int cvc_vocab_nll_ls_bwd(const float* logits, const float* lse, const int64_t* target, const float* w, const float* g, int M,
+                         int V, float eps, float* d_logits, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
