@@ -11,6 +11,7 @@
 // dispatch's NG ladder (1, 2, 4, 5, 8) is not the scan's (1 .. 8).  That changes code and needs measurements on the device.
 #include "row_block.h"
 #include "ban_set.h"
+#include "sample_select.h"      // the STOCH forms: gumbel(), the one definition of the noise, and the hash (dropout_rng.h)
 #include <math.h>
 #include <type_traits>
 
@@ -44,9 +45,41 @@ constexpr int ROW_CACHE = 32;        // values per thread kept in registers: V <
 // unused entry), and thread 0 writes the word ca.fws[4 * row + 3]: bits 0-2 the row's met mask (the history is already in LDS),
 // bits 8-10 the clip's active entries; ca.nmet[row] = the met mask's pop-count.  Nothing else in the scan changes: cand_v, cand_i,
 // lse and nbanned are the HIST form's bit for bit.
+// STOCH (cvc_beam_select_stoch_parts, always with HIST, never with FORCE; the rule: the comment of beam_merge_kernel's STOCH form): a
+// row's top `beam` are taken by the Gumbel-perturbed value s = z * inv_tau + noise instead of z.  After the ban map is applied the
+// registers are scaled by inv_tau in place, the candidate-only log-sum-exp lseq (banned slots and padding hold -inf and add nothing)
+// is taken from per-wave (max, sum) pairs like the full row's, and the noise of counter row * V + v is added; the selection rounds
+// then run on s unchanged.  cand_v carries s; the RAW logit of each of the row's `beam` finalists is reloaded by lane sel of wave 0
+// -- `beam` scalars per row, summed in the slab order of the loader (slab 0 + slab 1 + ... + bias), so they are the bits the
+// registers held before the scaling, and no second register copy is kept -- and written to ca.raw[8 * row + sel]; ca.lseq[row].
+// lse and nbanned are the HIST form's bit for bit.
 struct ForceArgs : ConsArgs { const int32_t* force; int nforce; float* fws; int32_t* nmet; };
-template <bool HIST, bool FORCE> struct scan_args { using type = typename cons_args<HIST>::type; };
-template <> struct scan_args<true, true> { using type = ForceArgs; };
+struct StochScanArgs : ConsArgs { float inv_tau; const uint32_t* state; uint32_t site; float* lseq; float* raw; };
+template <bool HIST, bool FORCE, bool STOCH = false> struct scan_args { using type = typename cons_args<HIST>::type; };
+template <> struct scan_args<true, true, false> { using type = ForceArgs; };
+template <> struct scan_args<true, false, true> { using type = StochScanArgs; };
+
+// The arithmetic of stochastic beam search, compiled with contraction off like the sampler's kernel (csrc/sample_select.h): the
+// scaled logit is one rounded multiply, and no product is ever fused into the add or subtract that follows it.
+__device__ __forceinline__ float stoch_scale(float z, float inv_tau) {
+#pragma clang fp contract(off)
+    return z * inv_tau;
+}
+// phi = logq + (z * inv_tau - lseq): the sampling log-prob of the child
+__device__ __forceinline__ float stoch_phi(float logq, float z, float inv_tau, float lseq) {
+#pragma clang fp contract(off)
+    const float zt = z * inv_tau;
+    return logq + (zt - lseq);
+}
+// the child's key conditioned on its parent's key G and the row's maximum Z >= g: -log(exp(-G) - exp(-Z) + exp(-g)) in the stable
+// form of include/cvc_hip_blocks.h; g == Z gives G exactly (l = -inf, u = -inf)
+__device__ __forceinline__ float stoch_condition(float G, float Z, float g) {
+#pragma clang fp contract(off)
+    const float d = g - Z;
+    const float l = d > -0.693147180559945f ? logf(-expm1f(d)) : log1pf(-expf(d));
+    const float u = (G - g) + l;
+    return (G - fmaxf(u, 0.f)) - log1pf(expf(-fabsf(u)));
+}
 
 // Forced words of a clip, f[0 .. C): bit j is set iff entry j is active -- 0 < f[j] < V, f[j] != unk and no earlier entry of the
 // clip holds the same word.  The one definition the row scan, the merge and the final ranking share.
@@ -61,12 +94,14 @@ __device__ __forceinline__ int force_active(const int32_t* f, int C, int V, int 
     return m;
 }
 
-template <int NG, int NP = 0, bool VEC = true, bool HIST = false, bool FORCE = false>      // float4 groups per thread: V <= NG * 1024
+template <int NG, int NP = 0, bool VEC = true, bool HIST = false, bool FORCE = false, bool STOCH = false>      // float4 groups per thread: V <= NG * 1024
 __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, int nparts, long long part_stride, const float* bias, int beam,
                                                           int V, int unk, float* cand_v, int* cand_i, float* lse_out,
-                                                          typename scan_args<HIST, FORCE>::type ca) {
+                                                          typename scan_args<HIST, FORCE, STOCH>::type ca) {
     static_assert(HIST || !FORCE, "the FORCE form is a history form");
+    static_assert(!STOCH || (HIST && !FORCE), "the STOCH form is a history form without forced words");
     __shared__ float wm[4], ws[4];
+    [[maybe_unused]] __shared__ float wqm[4], wqs[4];       // STOCH: the waves' (max, sum) pairs of the candidate-only log-sum-exp
     [[maybe_unused]] __shared__ int wb[4];
     __shared__ float wv[4 * BEAM_MAX];
     __shared__ int wi[4 * BEAM_MAX];
@@ -159,6 +194,37 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
                 if (ca.nmet != nullptr) ca.nmet[row] = __popc(met);
             }
         }
+        if constexpr (STOCH) {
+            const uint32_t seed_lo = ca.state[0], seed_hi = ca.state[1], call = ca.state[2];
+            const uint32_t base = (uint32_t)row * (uint32_t)V;
+            float mq = -INFINITY;
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v4[g][e] = stoch_scale(v4[g][e], ca.inv_tau);           // -inf (banned, padding) stays -inf
+                    mq = fmaxf(mq, v4[g][e]);
+                }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mq = fmaxf(mq, __shfl_xor(mq, o, 64));
+            float sq = 0.f;
+            if (mq != -INFINITY) {
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sq += expf(v4[g][e] - mq);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+            if (lane == 0) { wqm[wave] = mq; wqs[wave] = sq; }
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t v = (uint32_t)((tid + g * WG) * 4 + e);
+                    v4[g][e] += gumbel(cvc_drop_hash(seed_lo, seed_hi, call, ca.site, base + v));
+                }
+        }
     } else {
 #pragma unroll
         for (int g = 0; g < NG; ++g)
@@ -203,6 +269,16 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
                 if (ca.nbanned != nullptr) ca.nbanned[row] = (wb[0] + wb[1]) + (wb[2] + wb[3]);
             }
         }
+        if constexpr (STOCH) {
+            if (lane == 0) {
+                const float M = fmaxf(fmaxf(wqm[0], wqm[1]), fmaxf(wqm[2], wqm[3]));
+                float S = 0.f;
+                for (int w = 0; w < 4; ++w)
+                    if (wqm[w] != -INFINITY) S += wqs[w] * expf(wqm[w] - M);
+                ca.lseq[row] = M + logf(S);                    // no candidate: -inf + log 0 = -inf
+            }
+        }
+        [[maybe_unused]] int my_i = 0x7fffffff;                // STOCH: lane sel keeps the row's sel-th finalist
         const int cw = lane / BEAM_MAX, cs = lane % BEAM_MAX;      // lane -> (wave, rank) candidate
         float cv = -INFINITY;
         int ci = 0x7fffffff;
@@ -219,7 +295,19 @@ __global__ __launch_bounds__(WG) void beam_rowtop4_kernel(const float* logits, i
                 bi = take ? oi : bi;
             }
             if (lane == 0) { cand_v[row * BEAM_MAX + sel] = bv; cand_i[row * BEAM_MAX + sel] = bi; }
+            if constexpr (STOCH) my_i = lane == sel ? bi : my_i;
             if (ci == bi) { cv = -INFINITY; ci = 0x7fffffff; }
+        }
+        if constexpr (STOCH) {
+            if (lane < beam) {
+                float xv = -INFINITY;
+                if (my_i >= 0 && my_i < V) {                   // the loader's sum, in its order
+                    xv = x[my_i];
+                    for (int p = 1; p < nparts; ++p) xv += x[(size_t)p * part_stride + my_i];
+                    if (bias != nullptr) xv += bias[my_i];
+                }
+                ca.raw[row * BEAM_MAX + lane] = xv;
+            }
         }
     }
 }
@@ -298,14 +386,40 @@ template <bool GROUPS, bool BANKS = false> struct group_args { using type = NoGr
 template <> struct group_args<true, false> { using type = GroupArgs; };
 template <> struct group_args<false, true> { using type = BankArgs; };
 
-template <bool HIST = false, bool GROUPS = false, bool BANKS = false>
+// STOCH (cvc_beam_select_stoch_parts, always with HIST, never with GROUPS or BANKS): stochastic beam search (Kool, van Hoof and
+// Welling 2019).  The rule, once (restated by include/cvc_hip_blocks.h and in fp64 by tests/sbs_ref.py):
+//   state     row r = (b, k) enters step t with its history, score_in[r] (the sum of the model's log-probs), logq_in[r] (its sampling
+//             log-prob) and G_in[r] (its perturbed key); t == 0: only slot 0 of a clip is live, the others are at G = -inf.
+//   live row  candidates = the words outside Ban(t, r); lseq[r] = log-sum-exp of z * inv_tau over the candidates ONLY, so that
+//             q(v | r) = exp(z * inv_tau - lseq) is the distribution the sampling engine draws from, renormalised over what may be
+//             chosen; phi(k, v) = logq_in[k] + (z * inv_tau - lseq[k]); g(k, v) = phi(k, v) + gumbel(hash(seed_lo, seed_hi, call,
+//             CVC_SBS_SITE + t, (r * V + v) mod 2^32)); Z[k] = max_v g(k, v); the key is g conditioned on the parent's,
+//             gt = -log(exp(-G_in[k]) - exp(-Z[k]) + exp(-g)), in the stable form of stoch_condition(): the arg-max child gets G_in[k].
+//   others    a frozen row offers only (k, 0) at gt = G_in[k], logq and score carried; a row at G = -inf or with every word banned
+//             offers only -inf.
+//   selection the `beam` largest gt of the clip, ties -> lowest flat (k, v); the i-th goes to slot i (draw order); fillers as HIST.
+//   outputs   score_out = score_in[k] + (z - lse[k]) on the RAW logit (the HIST form's expression and bits), logq_out = phi,
+//             G_out = gt, -inf all three for a filler; parent, word, done_out, the histories as in the HIST form.
+// gt increases with g, and g = s + const per row up to rounding, so the row scan's top `beam` by s = z * inv_tau + noise hold the row's
+// top `beam` by gt; only these beam * beam finalists are transformed, here: phi and g are recomputed from the raw logit the scan
+// reloaded (the noise from the same counter) and Z[k] is the maximum over the row's finalists, so g - Z <= 0 holds in fp32 as well.
+// The winner's own lane writes score_out, logq_out and G_out, as GROUPS and BANKS write score_out.
+struct NoStoch {};
+struct StochArgs { float inv_tau; const uint32_t* state; uint32_t site; const float* lseq; const float* raw; const float* logq_in;
+                   const float* G_in; float* logq_out; float* G_out; };
+template <bool STOCH> struct stoch_args { using type = NoStoch; };
+template <> struct stoch_args<true> { using type = StochArgs; };
+
+template <bool HIST = false, bool GROUPS = false, bool BANKS = false, bool STOCH = false>
 __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, const int* cand_i, const float* lse,
                                                         const float* score_in, const uint8_t* done_in, int beam, int V,
                                                         int first_step, int64_t* parent, int64_t* word, float* score_out,
                                                         uint8_t* done_out, typename hist_args<HIST>::type ha,
-                                                        typename group_args<GROUPS, BANKS>::type ga) {
+                                                        typename group_args<GROUPS, BANKS>::type ga,
+                                                        typename stoch_args<STOCH>::type sa) {
     static_assert(HIST || !(GROUPS || BANKS), "the GROUPS and BANKS forms are history forms");
     static_assert(!(GROUPS && BANKS), "groups and banks exclude each other");
+    static_assert(!STOCH || (HIST && !GROUPS && !BANKS), "the STOCH form is a history form without groups or banks");
     const int b = blockIdx.x, lane = threadIdx.x;
     [[maybe_unused]] __shared__ int sel_k[BEAM_MAX], sel_v[BEAM_MAX];      // HIST: parent and word of every selected slot
     [[maybe_unused]] __shared__ int sel_p[BEAM_MAX];                       // GROUPS: its word if the parent was live, else -1
@@ -315,6 +429,8 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
     int flat = 0x7fffffff;
     [[maybe_unused]] int bd = beam, pw = -2;             // GROUPS: slots per group; this lane's word if it can be penalised
     [[maybe_unused]] int tb = 0, adv = -1;               // BANKS: the candidate's target bank; the entry of an advance lane
+    // STOCH: the row's key, the candidate's unconditioned g (-inf: it offers nothing), and what its lane writes if it wins
+    [[maybe_unused]] float c_G = -INFINITY, c_g = -INFINITY, c_sc = -INFINITY, c_lq = -INFINITY;
     if constexpr (GROUPS) bd = beam / ga.groups;
     if constexpr (BANKS) {
         bd = beam / (ga.nforce + 1);
@@ -333,7 +449,28 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             tb = __popc(fm & 7);
             unmet = (fm >> 8) & ~fm & 7;
         }
-        if (done_in[row]) {
+        if constexpr (STOCH) {
+            float G = sa.G_in[row];
+            if (first_step && k > 0) G = -INFINITY;
+            c_G = G;
+            c_sc = sc;
+            c_lq = sa.logq_in[row];
+            if (done_in[row]) {                          // frozen: (k, 0) at the carried key, logq and score carried
+                cv = r == 0 ? G : -INFINITY;
+                flat = k * V + r;
+            } else {
+                const float s = cand_v[row * BEAM_MAX + r];
+                const int vi = cand_i[row * BEAM_MAX + r];
+                flat = vi == 0x7fffffff ? 0x7fffffff : k * V + vi;
+                if (s != -INFINITY && G != -INFINITY && vi != 0x7fffffff) {
+                    const float zr = sa.raw[row * BEAM_MAX + r];
+                    const float phi = stoch_phi(c_lq, zr, sa.inv_tau, sa.lseq[row]);
+                    c_g = phi + gumbel(cvc_drop_hash(sa.state[0], sa.state[1], sa.state[2], sa.site, (uint32_t)row * (uint32_t)V + (uint32_t)vi));
+                    c_sc = sc + (zr - lse[row]);
+                    c_lq = phi;
+                }
+            }
+        } else if (done_in[row]) {
             // frozen hypothesis: candidates (k, 0) at the carried score, every other (k, v) at -inf; keep the
             // -inf fillers at distinct low flat indices so that tie-breaking matches a full scan
             cv = r == 0 ? sc : -INFINITY;
@@ -356,6 +493,13 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
                 tb += 1;
             }
         }
+    }
+    if constexpr (STOCH) {                               // Z[k] over the row's finalists (every lane shuffles), then the conditioned key
+        float Z = -INFINITY;
+        const int l0 = (k < beam ? k : beam - 1) * beam;
+        for (int j = 0; j < beam; ++j) Z = fmaxf(Z, __shfl(c_g, l0 + j, 64));
+        if (c_g != -INFINITY) cv = stoch_condition(c_G, Z, c_g);
+        if (cv == -INFINITY) { c_sc = -INFINITY; c_lq = -INFINITY; }      // a filler
     }
     [[maybe_unused]] float aug = -INFINITY;              // GROUPS: the candidate's augmented value while its group is served
     [[maybe_unused]] int g0 = 0;                         // GROUPS: first slot of the group being served
@@ -390,7 +534,10 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
             if (bi == 0x7fffffff) { kk = GROUPS ? g0 : 0; vv = 0; }      // every candidate NaN: parent / word feed gathers, keep them in range
             parent[b * beam + sel] = kk;
             word[b * beam + sel] = vv;
-            if (!(GROUPS || BANKS) || bi == 0x7fffffff) score_out[b * beam + sel] = bv;
+            if (!(GROUPS || BANKS || STOCH) || bi == 0x7fffffff) score_out[b * beam + sel] = STOCH ? -INFINITY : bv;
+            if constexpr (STOCH) {
+                if (bi == 0x7fffffff) { sa.logq_out[b * beam + sel] = -INFINITY; sa.G_out[b * beam + sel] = -INFINITY; }
+            }
             const bool frozen = done_in[b * beam + kk] != 0;
             done_out[b * beam + sel] = (frozen || vv == 0) ? 1 : 0;
             if constexpr (GROUPS) sel_p[sel] = (frozen || bi == 0x7fffffff || bv == -INFINITY) ? -1 : vv;
@@ -400,6 +547,13 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* cand_v, con
         }
         if constexpr (BANKS) {
             if (flat == bi && bi != 0x7fffffff) score_out[b * beam + sel] = cv;                           // the winner's lane
+        }
+        if constexpr (STOCH) {
+            if (flat == bi && bi != 0x7fffffff) {                                                         // the winner's lane
+                score_out[b * beam + sel] = c_sc;
+                sa.logq_out[b * beam + sel] = c_lq;
+                sa.G_out[b * beam + sel] = cv;
+            }
         }
         if constexpr (HIST) {
             if (lane == 0) {
@@ -450,12 +604,13 @@ static int beam_select_check(const float* logits, int nparts, const float* score
 // know the hypotheses' histories (ra: the row scan's history and rules, ma: the merge's gather).  GROUPS: the HIST row scan and the
 // merge that serves the groups in turn (ga: their number and the diversity strength).
 // BANKS: the FORCE row scan and the merge that serves the banks in turn (ra, ga: the forced words and the rows' workspace slots).
-template <bool HIST, bool GROUPS = false, bool BANKS = false>
+// STOCH: the STOCH row scan and merge (ra, sa: the temperature, the generator state and the rows' workspace slots).
+template <bool HIST, bool GROUPS = false, bool BANKS = false, bool STOCH = false>
 static int beam_select_run(const float* logits, int nparts, long long part_stride, const float* bias, const float* score_in,
                            const uint8_t* done_in, int B, int beam, int V, int unk_idx, int first_step, int64_t* parent, int64_t* word,
                            float* score_out, uint8_t* done_out, float* workspace, cvc_stream_t stream,
-                           typename scan_args<HIST, BANKS>::type ra, typename hist_args<HIST>::type ma,
-                           typename group_args<GROUPS, BANKS>::type ga = {}) {
+                           typename scan_args<HIST, BANKS, STOCH>::type ra, typename hist_args<HIST>::type ma,
+                           typename group_args<GROUPS, BANKS>::type ga = {}, typename stoch_args<STOCH>::type sa = {}) {
     // workspace: [rows*8] candidate values, [rows*8] candidate indices, [rows] lse   (rows = B*beam)
     const int rows = B * beam;
     float* cand_v = workspace;
@@ -475,7 +630,7 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
     auto scan = [&](auto ng_, auto np_, auto vec_) {
         constexpr int NG = decltype(ng_)::value, NP = decltype(np_)::value;
         constexpr bool VEC = decltype(vec_)::value;
-        hipLaunchKernelGGL((beam_rowtop4_kernel<NG, NP, VEC, HIST, BANKS>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, nparts,
+        hipLaunchKernelGGL((beam_rowtop4_kernel<NG, NP, VEC, HIST, BANKS, STOCH>), dim3(rows), dim3(WG), 0, (hipStream_t)stream, logits, nparts,
                            part_stride, bias, beam, V, unk_idx, cand_v, cand_i, lse, ra);
     };
     auto groups = [&](auto ng_) {
@@ -498,8 +653,8 @@ static int beam_select_run(const float* logits, int nparts, long long part_strid
         case 7: groups(integral_constant<int, 7>{}); break;
         default: groups(integral_constant<int, 8>{}); break;
     }
-    hipLaunchKernelGGL((beam_merge_kernel<HIST, GROUPS, BANKS>), dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in, done_in,
-                       beam, V, first_step, parent, word, score_out, done_out, ma, ga);
+    hipLaunchKernelGGL((beam_merge_kernel<HIST, GROUPS, BANKS, STOCH>), dim3(B), dim3(64), 0, (hipStream_t)stream, cand_v, cand_i, lse, score_in,
+                       done_in, beam, V, first_step, parent, word, score_out, done_out, ma, ga, sa);
     return cvc_launch_status();
 }
 
@@ -587,6 +742,35 @@ extern "C" int cvc_beam_select_force_parts(const float* logits, int nparts, long
     if (!force || nforce < 1 || nforce > 3 || (beam >= 1 && beam % (nforce + 1) != 0)) return CVC_E_BADARG;
     return beam_select_hist(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t, hist_in, hist_out, hist_stride, c,
                             parent, word, score_out, done_out, nbanned, workspace, stream, 0, 0.f, force, nforce, nmet);
+}
+
+// Stochastic beam search: cvc_beam_select_hist_parts whose ranking key is a Gumbel-perturbed sampling log-prob conditioned on the
+// parent's key (the rule: the comment of beam_merge_kernel's STOCH form; contract: include/cvc_hip_blocks.h).
+// workspace: 26 * B * beam floats -- the 17 of cvc_beam_select_hist_parts, then per row lseq and the raw logits of its 8 finalists.
+extern "C" int cvc_beam_select_stoch_parts(const float* logits, int nparts, long long part_stride, const float* bias,
+                                           const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                           const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                           float inv_tau, const uint32_t* state, const float* logq_in, const float* G_in,
+                                           int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, float* logq_out,
+                                           float* G_out, int32_t* nbanned, float* workspace, cvc_stream_t stream) {
+    const int rc = beam_select_check(logits, nparts, score_in, done_in, B, beam, V, parent, word, score_out, done_out, workspace);
+    if (rc != 0) return rc;
+    if (t < 0 || t > CONS_T_MAX) return CVC_E_TOOBIG;
+    if (c != nullptr && cons_rules_check(c) != 0) return CVC_E_BADARG;
+    if (!hist_out || (t > 0 && !hist_in) || (const int64_t*)hist_out == hist_in || hist_stride < (long long)B * beam) return CVC_E_BADARG;
+    if (!(inv_tau > 0.f) || !isfinite(inv_tau) || !state || !logq_in || !G_in || !logq_out || !G_out) return CVC_E_BADARG;
+    if ((const float*)logq_out == logq_in || (const float*)G_out == G_in || (const float*)score_out == score_in) return CVC_E_BADARG;
+    const cvc_constraint none = {0, 0, 0, 0, nullptr, nullptr, 0};
+    if (c == nullptr) c = &none;
+    const ConsArgs ra{hist_in, hist_stride, t, c->no_repeat_ngram, c->no_immediate_repeat != 0, c->min_len, c->ban, c->nban,
+                      c->bad_end, c->nbad, nbanned};
+    const uint32_t site = CVC_SBS_SITE + (uint32_t)t;
+    float* lseq = workspace + (size_t)17 * B * beam;
+    float* raw = workspace + (size_t)18 * B * beam;
+    return beam_select_run<true, false, false, true>(logits, nparts, part_stride, bias, score_in, done_in, B, beam, V, unk_idx, t == 0 ? 1 : 0,
+                                                     parent, word, score_out, done_out, workspace, stream,
+                                                     StochScanArgs{ra, inv_tau, state, site, lseq, raw}, HistArgs{hist_in, hist_out, hist_stride, t},
+                                                     NoGroups{}, StochArgs{inv_tau, state, site, lseq, raw, logq_in, G_in, logq_out, G_out});
 }
 
 namespace {

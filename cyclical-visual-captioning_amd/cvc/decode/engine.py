@@ -68,7 +68,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                  top_k: int = 0, top_p: float = 1.0, forced_n: int = 0, no_repeat_ngram: int = 0, no_immediate_repeat: bool = False,
                  min_len: int = 0, ban_words=None, bad_endings=None, beam_groups: int = 1, diversity: float = 0.0,
                  length_penalty: float = 0.0, force_n: int = 0, tail: Optional[str] = None, mix: bool = False,
-                 beam_history: bool = False):
+                 stochastic: bool = False, stochastic_tau: float = 1.0, beam_history: bool = False):
         """driver: enqueue the decode through the C-ABI drivers cvc_decode_greedy / cvc_decode_beam (one host call per decode);
         False walks the launch list in Python (one ctypes call per kernel; tests compare the two).
         embgate: packed path only -- the embedding-gate schedule (the embedded word's share of the att-LSTM gates is a row of
@@ -164,7 +164,19 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         driver, capture() works.  run() returns (inputs_next [rows, T] = the words that were fed on, att2_weights, logprob of the
         DRAWN words); self.drawn [T, rows] int64, self.took [T, rows] uint8 and self.given_logprob [T, rows] (the given word's
         log-prob, the forced block's bits) stay on the engine.  Refused: no temperature, beam > 1, forced_n, any constraint, top_k /
-        top_p, weights_dtype="bf16"."""
+        top_p, weights_dtype="bf16".
+        stochastic, stochastic_tau: stochastic beam search ("Stochastic beam search"; Kool, van Hoof and Welling
+        2019; the rule is the comment of cvc_beam_select_stoch_parts in include/cvc_hip_blocks.h) -- a history beam whose ranking
+        key is a Gumbel-perturbed sampling log-prob conditioned on the parent's key: a clip's `beam` slots are a sample WITHOUT
+        replacement from q_tau = the sampling engine's distribution at temperature stochastic_tau (UNK and the ban set left out,
+        renormalised per step), in draw order, pairwise distinct; slot 0 is an ordinary sample.  The word_select launch is
+        cvc_beam_select_stoch_parts on the tile path (fused slabs or finished logits) and on the ring path; tau and t are launch
+        constants and the noise comes from the engine's generator state (seed(); every decode and every replay of a captured graph
+        first advances `call`), so capture() works and a replay draws afresh.  The engine owns self.logq / self.G [2, rows]
+        (ping-pong like score); run() returns slot 0 (the beam engine's tuple, scores = sums of the model's log-probs in slot
+        order), hypotheses() returns (seq, score, G, logq) in draw order, consensus() works as for any history beam (fillers are
+        not live), and it composes with the five constraints.  Needs beam > 1 and beam_history=True; refused with beam_groups > 1,
+        diversity, length_penalty, force_n, a temperature (stochastic_tau is its own) and gsk / gate_ksplit / lang_ksx."""
         W = self.W = weights
         self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
         if weights_dtype not in WEIGHTS_DTYPES:
@@ -250,6 +262,28 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 raise RuntimeError(f"DecodeEngine: beam_groups = {self.groups} must divide beam = {self.beam}")
         if self.diversity != 0.0 and not self.grouped:
             raise RuntimeError("DecodeEngine: diversity acts between groups: it needs beam_groups > 1")
+        if not isinstance(stochastic, (bool, np.bool_)):
+            raise RuntimeError(f"DecodeEngine: stochastic must be a bool, got {stochastic!r}")
+        self.stoch = bool(stochastic)
+        if self.stoch:
+            why = None
+            if self.beam == 1 or not self.beam_hist:
+                why = "it is a beam search over hypotheses that carry their histories: it needs beam > 1 and beam_history=True"
+            elif self.grouped or self.diversity != 0.0:
+                why = "beam_groups > 1 / diversity are not part of it (the slots are one sample in draw order)"
+            elif self.length_penalty != 0.0:
+                why = "length_penalty is not part of it (the slots are ranked by their perturbed keys)"
+            elif self.forcing:
+                why = "force_n is not part of it"
+            elif temperature is not None:
+                why = "it takes no sampling temperature (stochastic_tau is its own)"
+            elif gsk or gate_ksplit or lang_ksx:
+                why = "it runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)"
+            elif not (0.0 < float(stochastic_tau) < float("inf")):
+                why = f"stochastic_tau must be a positive finite number, got {stochastic_tau!r}"
+            if why is not None:
+                raise RuntimeError(f"DecodeEngine: stochastic beam search (stochastic=True) is refused: {why}")
+            self.stoch_inv_tau = 1.0 / float(stochastic_tau)
         if self.constrained:
             if self.beam != 1 and not self.beam_hist:
                 raise RuntimeError("DecodeEngine: constrained decoding under beam search (beam > 1) needs beam_history=True (a "
@@ -360,7 +394,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         # fc is per clip; beams of a clip read the same row through a row-gather index
         self.fc = fc
         self.clip_of_row = torch.arange(rows, device=dev, dtype=torch.int64) // self.nq
-        if self.sampling:
+        if self.sampling or self.stoch:
             self.rng = torch.zeros(4, device=dev, dtype=torch.int32)          # {seed_lo, seed_hi, call, 0} (uint32 bit patterns)
             self.seed(0 if seed is None else seed)
         if self.mix:
@@ -388,7 +422,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.bt_seq = torch.zeros(self.B, self.T, dtype=torch.int64, device=dev)      # the returned hypothesis (cvc_beam_backtrack: rank 0; ranked engines: the best by norm)
             self.bt_att = z(self.B, self.T, N)
             self.gather_tmp = [z(rows, R) for _ in range(4)]
-            self.beam_ws = z((21 if self.forcing else 17) * rows)
+            self.beam_ws = z((26 if self.stoch else 21 if self.forcing else 17) * rows)
+            if self.stoch:                   # sampling log-prob and perturbed key of every slot, ping-pong like score
+                self.logq, self.G = z(2, rows), z(2, rows)
             if self.beam_hist:               # the hypotheses' own histories, ping-pong: step t reads [t & 1], writes [(t + 1) & 1]
                 self.bhist = torch.zeros(2, self.T, rows, dtype=torch.int64, device=dev)
             if self.ranked:                  # the final ranking (cvc_beam_rank): slots by norm, norm, len
@@ -558,6 +594,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             if self.beam > 1:
                 self.score.zero_()
                 self.done.zero_()
+                if self.stoch:
+                    self.logq.zero_()
+                    self.G.zero_()
             return
         if self.packed:
             self.XA[0].copy_(self.XA0_init)
@@ -574,6 +613,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.beam > 1:
             self.score.zero_()
             self.done.zero_()
+            if self.stoch:
+                self.logq.zero_()
+                self.G.zero_()
 
     def _run_launches(self, timers=None):
         """timers: optional dict name -> list of (start_event, end_event), filled per launch
@@ -717,7 +759,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
 
     def _build_launches(self):
         out = self._build_packed() if self.packed else (self._build_tile() if self.tile else self._build())
-        if self.sampling:            # first entry: a fresh `call` for every decode (and every replay of a captured graph)
+        if self.sampling or self.stoch:  # first entry: a fresh `call` for every decode (and every replay of a captured graph)
             out.insert(0, ("sample_advance", hip.lib().cvc_sample_advance, (self.rng.data_ptr(),)))
         return out
 
@@ -759,6 +801,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             return ("word_select", L.cvc_beam_select_parts, head + (1 if t == 0 else 0,) + tail + (ws,))
         cons = (self._cons_desc, self.nbanned[t].data_ptr()) if self.constrained else (None, None)
         hist = (t, self.bhist[srd].data_ptr(), self.bhist[swr].data_ptr(), self.rows, cons[0])
+        if self.stoch:
+            return ("word_select", L.cvc_beam_select_stoch_parts, head + hist + (
+                self.stoch_inv_tau, self.rng.data_ptr(), self.logq[srd].data_ptr(), self.G[srd].data_ptr()) + tail + (
+                self.logq[swr].data_ptr(), self.G[swr].data_ptr(), cons[1], ws))
         if self.grouped:
             return ("word_select", L.cvc_beam_select_groups_parts, head + hist + (self.groups, self.diversity) + tail + (cons[1], ws))
         if self.forcing:
@@ -769,13 +815,18 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def hypotheses(self, ranked: bool = False):
         """n-best: all `beam` hypotheses of every clip after run(), in slot order (one group: rank order by score) -- (seq
         [B, beam, T] int64, score [B, beam]), views of engine-owned buffers (beam_history=True: the histories the selection block
-        carried, no backtracking).  ranked=True (beam_groups > 1 or a length_penalty): (seq, score, norm, group [B, beam] int64) in
+        carried, no backtracking); a stochastic beam: (seq, score, G [B, beam], logq [B, beam]) in draw order, G the perturbed keys
+        (non-increasing over the slots) and logq the captions' log-probs under q_tau.  ranked=True (beam_groups > 1 or a length_penalty): (seq, score, norm, group [B, beam] int64) in
         the order of cvc_beam_rank -- norm descending, ties to the lowest slot -- as new tensors; with force_n the fourth is nmet
         [B, beam] int32, the forced words each hypothesis met, and the order is cvc_beam_rank_force's."""
         if not self.beam_hist:
             raise RuntimeError("DecodeEngine.hypotheses needs beam_history=True")
         B, beam, T = self.B, self.beam, self.T
         seq, score = self.bhist[T & 1].view(T, B, beam).permute(1, 2, 0), self.score[T & 1].view(B, beam)
+        if self.stoch:                      # draw order is slot order; a filler holds -inf in all three
+            if ranked:
+                raise RuntimeError("DecodeEngine.hypotheses(ranked=True): a stochastic beam's slots are in draw order, there is no ranking")
+            return seq, score, self.G[T & 1].view(B, beam), self.logq[T & 1].view(B, beam)
         if not ranked:
             return seq, score
         if not self.ranked:
@@ -807,7 +858,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             utility, pick, best = table.consensus(cand, n)
             at = torch.arange(B, device=cand.device) * n + pick
             return (best, self.att_steps.permute(1, 0, 2).index_select(0, at), self.logprob.t().index_select(0, at), pick, utility)
-        seq, score = self.hypotheses()
+        seq, score = self.hypotheses()[:2]
         utility, pick, _ = table.consensus(seq.reshape(B * n, T), n, live=torch.isfinite(score).reshape(-1))
         start = pick.to(torch.int64)
         bt_seq = torch.empty(B, T, dtype=torch.int64, device=start.device)
@@ -868,9 +919,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
         key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail, self.mix)
+               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail, self.mix, self.stoch)
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
-            saved = self.rng.clone() if self.sampling else None     # (the warm-up decode must not advance the sampling state)
+            saved = self.rng.clone() if (self.sampling or self.stoch) else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -888,7 +939,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     def seed(self, s: int):
         """Sampling: the generator state becomes {seed_lo, seed_hi, 0, 0} of the 64-bit seed s (a stream-ordered copy); the k-th
         decode after it draws its noise with call = k."""
-        if not self.sampling:
+        if not self.sampling and not self.stoch:
             raise RuntimeError("DecodeEngine.seed: this engine does not sample (temperature=None)")
         s = int(s) & 0xFFFFFFFFFFFFFFFF
         words = np.array([s & 0xFFFFFFFF, s >> 32, 0, 0], dtype=np.uint32).view(np.int32)

@@ -258,6 +258,9 @@ SIGNATURES = {
     "cvc_beam_select_force_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _P, _I, _P, _P, _P,
                                     _P, _P, _P, _P, _P],
     "cvc_beam_rank_force": [_P, _LL, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P],
+    # stochastic beam search: k distinct sampled captions per clip, in draw order (csrc/beam.hip; building block)
+    "cvc_beam_select_stoch_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _F, _P, _P, _P,
+                                    _P, _P, _P, _P, _P, _P, _P, _P, _P],
     # packed GEMMs with bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip; building blocks)
     "cvc_packed_lstm_bf16w_fwd": [_P, _LL, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P],
     "cvc_packed_linear_bf16w_fwd": [_P, _P, _I, _P, _I, _I, _I, _P, _I, _P, _P],
@@ -315,7 +318,7 @@ BLOCKS = {
     "cvc_attn_bwd_pair", "cvc_ctxfeat_bwd_steps", "cvc_dproj_bwd_steps", "cvc_tile_gemm_big", "cvc_tile_gemm_plan", "cvc_linear_splitk_fwd", "cvc_linear_top2_fwd", "cvc_top2_final", "cvc_packed_lstm_fwd", "cvc_packed_linear_fwd",
     "cvc_packed_lstm_embgate_fwd", "cvc_packed_lstm_embgate_ex_fwd", "cvc_packed_lstm_late_fwd", "cvc_packed_lstm_train_fwd",
     "cvc_packed_lstm_train_pre_fwd", "cvc_packed_lstm_train_drop_fwd", "cvc_lstm_pointwise_bwd", "cvc_lstm_pointwise_bwd3",
-    "cvc_lstm_pointwise_bwd3_drop", "cvc_pack_lstm_weights", "cvc_linear_nn_planes_fwd", "cvc_linear_nn_planes2_fwd", "cvc_gru_seq_train_fwd", "cvc_lstm_pointwise_bwd4_pair", "cvc_beam_select_parts", "cvc_sample_select_parts", "cvc_sample_select_trunc_parts", "cvc_sample_advance", "cvc_forced_select_parts", "cvc_constrained_select_parts", "cvc_beam_select_hist_parts", "cvc_beam_select_groups_parts", "cvc_beam_rank", "cvc_beam_select_force_parts", "cvc_beam_rank_force", "cvc_beam_backtrack_from", "cvc_tile_lstm_finish",
+    "cvc_lstm_pointwise_bwd3_drop", "cvc_pack_lstm_weights", "cvc_linear_nn_planes_fwd", "cvc_linear_nn_planes2_fwd", "cvc_gru_seq_train_fwd", "cvc_lstm_pointwise_bwd4_pair", "cvc_beam_select_parts", "cvc_sample_select_parts", "cvc_sample_select_trunc_parts", "cvc_sample_advance", "cvc_forced_select_parts", "cvc_constrained_select_parts", "cvc_beam_select_hist_parts", "cvc_beam_select_groups_parts", "cvc_beam_rank", "cvc_beam_select_force_parts", "cvc_beam_rank_force", "cvc_beam_select_stoch_parts", "cvc_beam_backtrack_from", "cvc_tile_lstm_finish",
     "cvc_tile_lstm_finish_embgate", "cvc_tile_reorder_pack", "cvc_decode_num_launches", "cvc_gemm_force_generic",
     "cvc_tile_gemm_loaders", "cvc_gru_persistent_waves8", "cvc_relu_dropout_fwd", "cvc_relu_dropout_bwd", "cvc_bn_workspace",
     "cvc_bn_relu_train_fwd", "cvc_bn_relu_train_bwd", "cvc_class_softmax_bwd", "cvc_layernorm_cat_bwd", "cvc_stable_order", "cvc_col_sum", "cvc_col_sum_ws", "cvc_attn_weighted_rows",

@@ -95,6 +95,13 @@ def build_parser():
     parser.add_argument("--consensus_samples", type=int, default=16, help="sampled candidates per clip (2 .. 32)")
     parser.add_argument("--consensus_temperature", type=float, default=1.0, help="temperature of the sampled candidates")
     parser.add_argument("--consensus_seed", type=int, default=1, help="seed of the sampled candidates' noise")
+    # stochastic beam search at evaluation (model._sample(stochastic_beam=...); DecodeEngine stochastic)
+    parser.add_argument("--stochastic_beam", action="store_true",
+                        help="beam search by Gumbel-perturbed keys: the --beam_size hypotheses are distinct samples drawn without "
+                             "replacement, the reported caption is the first draw (an ordinary sample); composes with the "
+                             "constraints and --consensus beam, not with --group_size, --length_penalty or forced words")
+    parser.add_argument("--stochastic_tau", type=float, default=1.0, help="temperature of the stochastic beam's sampling distribution")
+    parser.add_argument("--sample_seed", type=int, default=0, help="seed of the stochastic beam's noise")
     return parser
 
 
@@ -105,7 +112,7 @@ def check_label_smoothing_flag(eps):
 
 
 def main(argv=None, sample=None, score=None):
-    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p) or (n, temperature, seed, top_k, top_p, consensus) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
     score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
     (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
@@ -171,6 +178,8 @@ def main(argv=None, sample=None, score=None):
                          "--scheduled_sampling_increase_prob >= 0 and --scheduled_sampling_max_prob in [0, 1]")
     if not 2 <= opt.consensus_samples <= 32 or opt.consensus_temperature <= 0:
         raise SystemExit("--consensus_samples lies in 2 .. 32 and --consensus_temperature must be > 0")
+    if opt.stochastic_beam and (opt.beam_size < 2 or not opt.stochastic_tau > 0):
+        raise SystemExit("--stochastic_beam needs --beam_size > 1 and --stochastic_tau > 0")
     if opt.consensus == "beam" and opt.beam_size < 2:
         raise SystemExit("--consensus beam chooses among the hypotheses of beam search: it needs --beam_size > 1")
     from .metrics import parse_reward_weights
@@ -220,7 +229,7 @@ def main(argv=None, sample=None, score=None):
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
-        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus"), sample[3:])))
+        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus", "without_replacement"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
         if comm is not None:

@@ -125,6 +125,9 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # of _sample draws consensus_samples captions per clip and keeps the consensus one) or "beam" (the hypotheses of beam search);
         # consensus_table is the cvc.cider.CiderD the utilities are taken over (Trainer sets the training captions' table)
         self.consensus = str(getattr(opts, "consensus", "off") or "off")
+        # stochastic beam search (_sample(stochastic_beam=...); DecodeEngine stochastic): beam_size distinct sampled captions per clip
+        self.stochastic_beam = bool(getattr(opts, "stochastic_beam", False))
+        self.stochastic_tau = float(getattr(opts, "stochastic_tau", 1.0))
         self.consensus_samples = int(getattr(opts, "consensus_samples", 16))
         self.consensus_temperature = float(getattr(opts, "consensus_temperature", 1.0))
         self.consensus_seed = int(getattr(opts, "consensus_seed", 1))
@@ -668,7 +671,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 top_k: Optional[int] = None, top_p: Optional[float] = None, no_repeat_ngram: Optional[int] = None,
                 no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
                 beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None,
-                force_words=None, encoded=None, consensus=None):
+                force_words=None, encoded=None, consensus=None, stochastic_beam: Optional[bool] = None,
+                stochastic_tau: Optional[float] = None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -701,7 +705,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         consensus_seed where sample_n / temperature / seed are not given, beam_size 1.  "beam": as True, beam_size > 1 required.
         The candidates are exactly what the same call returns with consensus=False and the same seed; self.last_consensus =
         dict(candidates, pick, utility) keeps them (seq [B * n, T] / hypotheses [B, beam, T]) with the picks [B] and the utilities
-        [B * n], device tensors."""
+        [B * n], device tensors.
+        stochastic_beam / stochastic_tau (arguments, else the model's attributes, read from opts; off by default): stochastic beam
+        search with beam_size > 1 -- the engine is built with beam_history=True and stochastic=True, seeded once with seed (else the
+        model's sample_seed); the result is a beam decode's (seq, att2_weights, None) of slot 0, an ordinary sample of q_tau, and
+        self.last_stochastic = dict(seq [B, beam, T], score, G, logq [B, beam]) keeps the clip's beam_size distinct captions in
+        draw order with their model log-probs, perturbed keys and sampling log-probs (clones).  It composes with the five
+        constraints and with consensus "beam" / True (the candidates are the distinct samples); what the engine refuses raises."""
         mode = self.consensus if consensus is None else consensus
         mode = "on" if mode is True else (None if (not mode or mode == "off") else mode)
         if mode not in (None, "on", "samples", "beam"):
@@ -726,6 +736,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         s_seed = (d_seed if seed is None else int(seed)) if sampling else None
         if mode == "samples":
             beam = 1
+        # (the model's attribute is the default of a beam decode only: a sampling call that does not ask for it is left as it was)
+        stoch = (self.stochastic_beam and not sampling) if stochastic_beam is None else bool(stochastic_beam)
+        stau = self.stochastic_tau if stochastic_tau is None else float(stochastic_tau)
+        if stoch and not sampling:
+            s_seed = self.sample_seed if seed is None else int(seed)
         if mode is not None and not (n > 1 if (sampling and mode != "beam") else (not sampling and beam > 1)):
             raise RuntimeError(f"_sample: consensus selection needs several candidates per clip -- sample_max = 0 with sample_n > 1, or "
                                f"beam_size > 1 without sampling (got consensus = {mode!r}, sampling = {sampling}, sample_n = {n}, "
@@ -753,7 +768,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
         # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
         key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha) + (mode is not None,)
+               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha) + (mode is not None,) + ((stoch, stau) if stoch else ())
         cached = getattr(self, "_engine_cache", None)
         if cached is not None and cached[0] == key:
             engine = cached[1]
@@ -768,14 +783,17 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
                                   sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
                                   beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0)
-                                  or (beam > 1 and mode is not None),      # (consensus chooses among hypotheses())
-                                  beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n, **cons)
+                                  or (beam > 1 and mode is not None) or stoch,      # (consensus chooses among hypotheses())
+                                  beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n,
+                                  **(dict(stochastic=True, stochastic_tau=stau) if stoch else {}), **cons)
             if self.use_hip_graph:
                 engine.capture()
             self._engine_cache = (key, engine)
         if force_n > 0:
             engine.load_force_words(force_words)
         res = engine.run()
+        if stoch:
+            self.last_stochastic = dict(zip(("seq", "score", "G", "logq"), (x.clone() for x in engine.hypotheses())))
         if mode is not None:
             seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table)
             self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility)

@@ -6,8 +6,10 @@ temperature) without UNK, written to <results_dir>/densecap-<val_split>-<id>_sam
   python -m cvc.sample --temperature 1.0 --top_k 40 --top_p 0.9 ...      (top-k, then nucleus truncation of the distribution)
 
   python -m cvc.sample --sample_n 16 --consensus ...                     (also the consensus pick and the samples' utilities)
+  python -m cvc.sample --sample_n 5 --without_replacement ...            (5 DISTINCT captions per segment in draw order, by
+                                                                          stochastic beam search, with each one's logq and G)
 
---temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
+--temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus / --without_replacement are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
 --resume with --load_best_score: the same checkpoint loading as an --inference_only evaluation).
 """
 from __future__ import annotations
@@ -29,7 +31,14 @@ def parse(argv=None):
     p.add_argument("--consensus", action="store_true",
                    help="add to every segment the index of its consensus pick and the samples' utilities (CIDEr-D against the other "
                         "samples, training captions' table); needs --sample_n > 1")
+    p.add_argument("--without_replacement", action="store_true",
+                   help="draw the --sample_n captions of a segment without replacement (stochastic beam search at --temperature): "
+                        "pairwise distinct, in draw order, with each one's logq and G; needs --sample_n > 1, refused with --top_k / --top_p")
     own, rest = p.parse_known_args(argv)
+    if own.without_replacement and own.sample_n < 2:
+        raise SystemExit("--without_replacement needs --sample_n > 1")
+    if own.without_replacement and (own.top_k != 0 or own.top_p != 1.0):
+        raise SystemExit("--without_replacement is refused with --top_k / --top_p")
     if own.consensus and own.sample_n < 2:
         raise SystemExit("--consensus needs --sample_n > 1")
     if not own.temperature > 0:
@@ -47,7 +56,7 @@ def main(argv=None):
     own, rest = parse(argv)
     if "--inference_only" not in rest:
         rest = rest + ["--inference_only"]
-    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus))
+    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus, own.without_replacement))
 
 
 if __name__ == "__main__":

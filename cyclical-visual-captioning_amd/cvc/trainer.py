@@ -922,7 +922,7 @@ class Trainer:
         return stats
 
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
-               constraints: dict = None, consensus: bool = False):
+               constraints: dict = None, consensus: bool = False, without_replacement: bool = False):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
         without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise);
         top_k / top_p truncate that distribution (0 / 1.0 = off; the log-probs stay the model's, over the full vocabulary).
@@ -934,6 +934,11 @@ class Trainer:
         consensus=True (n > 1): every entry also holds "consensus": the index of the consensus pick among its n sentences, and
         "utilities": [n], each sentence's CIDEr-D against the segment's other samples over the training captions' table
         (cvc.cider.CiderD.consensus); the last batch's device tensors stay in model.last_consensus.
+        without_replacement=True (n > 1): the n captions of a segment are drawn WITHOUT replacement by stochastic beam search
+        (model._sample(beam_size=n, stochastic_beam=True, stochastic_tau=temperature)): pairwise distinct, in draw order, the first
+        an ordinary sample.  "logprobs" is then each caption's model log-prob as the beam carries it (the same sum), and every entry
+        also holds "logq": [n], the captions' log-probs under the sampling distribution q_tau, and "G": [n], their perturbed keys
+        (non-increasing).  top_k / top_p are refused with it; the constraints and consensus work.
         Returns the path (None on the other ranks)."""
         model = getattr(self.model, "module", self.model)
         model.eval()
@@ -941,16 +946,28 @@ class Trainer:
         timestamps = self._segment_timestamps()
         samples = defaultdict(list)
         n = int(n)
+        if without_replacement:
+            if n < 2:
+                raise RuntimeError(f"Trainer.sample: without_replacement draws n > 1 distinct captions per segment, got n = {n}")
+            if top_k != 0 or top_p != 1.0:
+                raise RuntimeError("Trainer.sample: without_replacement is refused with top_k / top_p (stochastic beam search samples "
+                                   "the untruncated distribution)")
         if consensus:
             if n < 2:
                 raise RuntimeError(f"Trainer.sample: consensus selection needs n > 1 samples per segment, got n = {n}")
             self._consensus_table(model)
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
-                seq, _, logprob = model._sample(b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"],
-                                                b["gt_bboxs"], b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"],
-                                                sample_max=0, temperature=temperature, sample_n=n, seed=seed, top_k=top_k,
-                                                top_p=top_p, consensus=False, **(constraints or {}))
+                args = (b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"], b["gt_bboxs"],
+                        b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"])
+                if without_replacement:
+                    model._sample(*args, beam_size=n, sample_max=1, stochastic_beam=True, stochastic_tau=temperature, seed=seed,
+                                  consensus=False, beam_groups=1, diversity_lambda=0.0, length_penalty=0.0, **(constraints or {}))
+                    draws = model.last_stochastic
+                    seq, logprob = draws["seq"].reshape(-1, draws["seq"].size(2)), None
+                else:
+                    seq, _, logprob = model._sample(*args, sample_max=0, temperature=temperature, sample_n=n, seed=seed, top_k=top_k,
+                                                    top_p=top_p, consensus=False, **(constraints or {}))
                 if consensus:
                     utility, pick, _ = model.consensus_table.consensus(seq, n)
                     model.last_consensus = dict(candidates=seq, pick=pick, utility=utility)
@@ -959,11 +976,16 @@ class Trainer:
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 # sequence log-prob: the steps up to and including the first EOS (word 0)
                 ended = torch.cumsum((seq == 0).to(torch.int32), 1) - (seq == 0).to(torch.int32)
-                seq_lp = (logprob * (ended == 0).to(logprob.dtype)).sum(1).tolist()
+                if without_replacement:
+                    seq_lp, seq_lq, seq_G = (draws[k].reshape(-1).tolist() for k in ("score", "logq", "G"))
+                else:
+                    seq_lp = (logprob * (ended == 0).to(logprob.dtype)).sum(1).tolist()
                 for k, seg_id in enumerate(b["seg_id"]):
                     vid_idx, entry = densecap_entry(sents[k * n], seg_id, timestamps)
                     samples[vid_idx].append({"segment": entry["segment"], "timestamp": entry["timestamp"],
                                              "sentences": sents[k * n:(k + 1) * n], "logprobs": seq_lp[k * n:(k + 1) * n]})
+                    if without_replacement:
+                        samples[vid_idx][-1].update(logq=seq_lq[k * n:(k + 1) * n], G=seq_G[k * n:(k + 1) * n])
                     if consensus:
                         samples[vid_idx][-1].update(consensus=picks[k], utilities=utils_[k])
         samples, _ = gather_eval_outputs(samples, {})

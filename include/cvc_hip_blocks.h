@@ -324,6 +324,50 @@ int cvc_beam_select_force_parts(const float* parts, int nparts, long long part_s
 int cvc_beam_rank_force(const int64_t* hist, long long hist_stride, const float* score, const int32_t* force, int nforce, int B,
                         int beam, int T, int V, int unk_idx, float alpha, int64_t* order, float* norm, int32_t* len, int32_t* nmet,
                         cvc_stream_t stream);
+/* Stochastic beam search (Kool, van Hoof and Welling 2019, "Stochastic Beams and Where to Find Them"; csrc/beam.hip: the STOCH forms
+ * of the row scan and the merge of cvc_beam_select_hist_parts): a beam-search step whose ranking key is a Gumbel-perturbed sampling
+ * log-prob, conditioned top-down so that a child's key never exceeds its parent's.  After T steps a clip's finite slots are a sample
+ * WITHOUT replacement, in draw order, from q over length-T prefixes; slot 0 is an exact sample of q; all are pairwise distinct.
+ *   state       row r = b * beam + k enters step t with its history (as cvc_beam_select_hist_parts), score_in[r] (the sum of the
+ *               model's log-probs), logq_in[r] (its sampling log-prob) and G_in[r] (its perturbed key).  t == 0: only slot 0 of a clip
+ *               is live and the caller hands it score = logq = G = 0; slots k > 0 are taken at G = -inf whatever the buffers hold.
+ *   candidates  of a live row: the words outside Ban(t, r) of cvc_beam_select_hist_parts (UNK always, the rules of c when given).
+ *               lse[r]  = the log-sum-exp of the full row, as in that block.
+ *               lseq[r] = the log-sum-exp of z * inv_tau over the candidates ONLY: q(v | r) = exp(z * inv_tau - lseq) is renormalised
+ *                         over what may be chosen, the distribution cvc_sample_select_parts / cvc_constrained_select_parts draw from
+ *                         (their arg-max leaves the ban set out); with the full-row normaliser slot 0 would not be such a draw.
+ *               phi(k, v) = logq_in[k] + (z[k, v] * inv_tau - lseq[k])
+ *               g(k, v)   = phi(k, v) + gumbel(cvc_drop_hash(seed_lo, seed_hi, call, CVC_SBS_SITE + t, (r * V + v) mod 2^32)), gumbel
+ *                           the definition of cvc_sample_select_parts (u = ((h >> 9) + 0.5) * 2^-23, -logf(-logf(u)))
+ *               Z[k]      = max_v g(k, v) over the candidates
+ *               key       gt = -log(exp(-G_in[k]) - exp(-Z[k]) + exp(-g)), computed as  d = g - Z;  l = log(-expm1(d)) for d > -ln 2,
+ *                         else log1p(-exp(d));  u = (G_in - g) + l;  gt = (G_in - max(u, 0)) - log1p(exp(-|u|)).  The arg-max child
+ *                         gets gt = G_in exactly.  Accurate logf / expf / log1pf / expm1f, fp32, no contraction.
+ *   other rows  a frozen row (done_in) offers only (k, 0) at gt = G_in[k], logq and score carried; a row at G = -inf, or one whose
+ *               every word is banned, offers only -inf.  No NaN leaves the block from such rows.
+ *   selection   the `beam` largest gt of the clip, ties -> lowest flat (k, v); the i-th goes to slot i, so slots are in draw order and
+ *               G_out is non-increasing over a clip's slots.  Fewer finite candidates than `beam`: fillers as in the history block,
+ *               with score_out = logq_out = G_out = -inf.
+ *   outputs     score_out = score_in[k] + (z[k, v] - lse[k]) on the RAW logit: the expression and the bits of the history block's
+ *               candidate, so scores stay sums of the model's log-probs whatever inv_tau; logq_out = phi; G_out = gt; parent, word,
+ *               done_out, the history gather and append, nbanned as cvc_beam_select_hist_parts writes them.
+ *   mechanics   gt increases with g, so a row's top `beam` by gt are its top `beam` by s = z * inv_tau + noise: the row scan keeps a
+ *               per-row top-`beam` (of s, in registers) and only the beam * beam finalists are transformed, in the merge, from the
+ *               raw logit of each finalist, which the scan reloads (`beam` scalars per row, summed in the slab order) instead of
+ *               holding a second register copy.  inv_tau == 1 and != 1 are one code path.
+ * state: the sampler's device words {seed_lo, seed_hi, call, 0}, read by both kernels (cvc_sample_advance gives a replayed graph
+ * fresh noise).  CVC_SBS_SITE + t is disjoint from CVC_SAMPLE_SITE + t', CVC_MIX_SITE + t' and the dropout sites for t, t' <= 64.
+ * workspace: 26 * B * beam floats (the 17 of cvc_beam_select_hist_parts, then per row lseq and the raw logits of its 8 finalists).
+ * The checks of cvc_beam_select_hist_parts with their codes; inv_tau not finite or <= 0, NULL state / logq_in / G_in / logq_out /
+ * G_out, logq_in == logq_out, G_in == G_out, score_in == score_out: CVC_E_BADARG.  Nothing is launched on a refusal.  Graph-capturable;
+ * bitwise deterministic for a given state. */
+#define CVC_SBS_SITE 0x42000000u
+int cvc_beam_select_stoch_parts(const float* parts, int nparts, long long part_stride, const float* bias,
+                                const float* score_in, const uint8_t* done_in, int B, int beam, int V, int unk_idx, int t,
+                                const int64_t* hist_in, int64_t* hist_out, long long hist_stride, const cvc_constraint* c,
+                                float inv_tau, const uint32_t* state, const float* logq_in, const float* G_in,
+                                int64_t* parent, int64_t* word, float* score_out, uint8_t* done_out, float* logq_out, float* G_out,
+                                int32_t* nbanned, float* workspace, cvc_stream_t stream);
 /* cvc_beam_backtrack (include/cvc_hip.h) from slot start[b * start_stride] of clip b instead of slot 0 (the same kernel; the slot
  * is clamped to [0, beam) like a parent; start_stride = beam reads column 0 of cvc_beam_rank's order in place).  start == 0
  * everywhere: the bits of cvc_beam_backtrack.  Its checks; NULL start, start_stride < 1: CVC_E_BADARG. */
