@@ -4,9 +4,7 @@ The per-path buffers and launch lists live in path_packed / path_tile / path_rin
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Dict, List, Optional, Tuple
-
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -14,34 +12,11 @@ import torch
 from .. import hip
 from .weights import *          # noqa: F401,F403  (packers, layouts, cache plan, switches)
 from .weights import _segs
+from .mode import DecodeMode
 from .path_packed import PackedPath
 from .path_tile import TilePath
 from .path_ring import RingPath
 from .path_experimental import ExperimentalPaths
-
-CONSTRAINT_T_MAX = 64            # history steps of cvc_constrained_select_parts (one lane per step)
-CONSTRAINT_LIST_MAX = 256        # entries of its ban_words / bad_endings lists (one thread per entry)
-
-
-def _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings):
-    """The five constraint arguments checked and normalised: (n, immediate, min_len, ban ids, bad-ending ids), the lists sorted and
-    without duplicates.  Malformed values raise the engine's RuntimeError (ids are checked against V by the caller)."""
-    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-    for name, v, hi in (("no_repeat_ngram", no_repeat_ngram, CONSTRAINT_T_MAX), ("min_len", min_len, None)):
-        if not is_int(v) or v < 0 or (hi is not None and v > hi):
-            raise RuntimeError(f"DecodeEngine: {name} must be an integer >= 0 (0 = off)" + (f" and <= {hi}" if hi else "") + f", got {v!r}")
-    if not isinstance(no_immediate_repeat, (bool, np.bool_)) and no_immediate_repeat not in (0, 1):
-        raise RuntimeError(f"DecodeEngine: no_immediate_repeat must be a bool, got {no_immediate_repeat!r}")
-    lists = []
-    for name, ids in (("ban_words", ban_words), ("bad_endings", bad_endings)):
-        ids = [] if ids is None else list(ids) if isinstance(ids, (list, tuple, set, frozenset, np.ndarray)) else None
-        if ids is None or not all(is_int(v) and v >= 0 for v in ids):
-            raise RuntimeError(f"DecodeEngine: {name} must be a list of word ids (integers >= 0), got {ban_words if name == 'ban_words' else bad_endings!r}")
-        ids = tuple(sorted({int(v) for v in ids}))
-        if len(ids) > CONSTRAINT_LIST_MAX:
-            raise RuntimeError(f"DecodeEngine: {name} takes at most {CONSTRAINT_LIST_MAX} ids, got {len(ids)}")
-        lists.append(ids)
-    return int(no_repeat_ngram), bool(no_immediate_repeat), int(min_len), lists[0], lists[1]
 
 
 def _capture_mode() -> str:
@@ -177,175 +152,19 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         order), hypotheses() returns (seq, score, G, logq) in draw order, consensus() works as for any history beam (fillers are
         not live), and it composes with the five constraints.  Needs beam > 1 and beam_history=True; refused with beam_groups > 1,
         diversity, length_penalty, force_n, a temperature (stochastic_tau is its own) and gsk / gate_ksplit / lang_ksx."""
+        # every check that needs neither the batch nor the library, before a feature is read (cvc/decode/mode.py)
+        m = self.mode = DecodeMode.resolve(
+            T, getattr(weights, "V", None), beam=beam, path=path, gate_ksplit=gate_ksplit, gsk=gsk, embgate=embgate, lang_ksx=lang_ksx,
+            sample_n=sample_n, temperature=temperature, weights_dtype=weights_dtype, top_k=top_k, top_p=top_p, forced_n=forced_n,
+            no_repeat_ngram=no_repeat_ngram, no_immediate_repeat=no_immediate_repeat, min_len=min_len, ban_words=ban_words,
+            bad_endings=bad_endings, beam_groups=beam_groups, diversity=diversity, length_penalty=length_penalty, force_n=force_n,
+            mix=mix, stochastic=stochastic, stochastic_tau=stochastic_tau, beam_history=beam_history)
+        for name in DecodeMode.ENGINE_FIELDS:            # the engine, its path mixins and the tests read them as self.<name>
+            if getattr(m, name) is not None:             # (inv_tau / stoch_inv_tau exist only in the modes that read them)
+                setattr(self, name, getattr(m, name))
+        gsk, gate_ksplit, lang_ksx = m.gsk, m.gate_ksplit, m.lang_ksx     # the schedule requests as the mode leaves them
         W = self.W = weights
-        self.T, self.unk, self.beam = int(T), int(unk_idx), int(beam)
-        if weights_dtype not in WEIGHTS_DTYPES:
-            raise RuntimeError(f"DecodeEngine: weights_dtype must be one of {WEIGHTS_DTYPES}, got {weights_dtype!r}")
-        self.weights_dtype = weights_dtype
-        self.bf16w = weights_dtype == "bf16"
-        if isinstance(forced_n, bool) or not isinstance(forced_n, (int, np.integer)) or forced_n < 0:
-            raise RuntimeError(f"DecodeEngine: forced_n must be an integer >= 0 (0 = off), got {forced_n!r}")
-        self.forced = int(forced_n) >= 1
-        if self.forced:
-            if self.beam != 1:
-                raise RuntimeError("DecodeEngine: the forced mode (forced_n) and beam search (beam > 1) exclude each other")
-            if temperature is not None:
-                raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no sampling temperature")
-            if gsk or gate_ksplit or lang_ksx:
-                raise RuntimeError("DecodeEngine: the forced mode runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
-            gate_ksplit, lang_ksx = False, False
-        self.cons = _constraints(no_repeat_ngram, no_immediate_repeat, min_len, ban_words, bad_endings)
-        self.constrained = bool(self.cons[0] or self.cons[1] or self.cons[2] or self.cons[3] or self.cons[4])
-        if not isinstance(mix, (bool, np.bool_)):
-            raise RuntimeError(f"DecodeEngine: mix must be a bool, got {mix!r}")
-        self.mix = bool(mix)
-        if self.mix:
-            why = None
-            if temperature is None:
-                why = "it draws from the sampling engine: it needs a temperature"
-            elif self.beam != 1:
-                why = "beam search (beam > 1) chooses its own words"
-            elif self.forced:
-                why = "the forced mode (forced_n) follows given words only"
-            elif self.constrained:
-                why = "constrained decoding is not part of it"
-            elif (not isinstance(top_k, bool) and isinstance(top_k, (int, np.integer)) and top_k != 0) or top_p != 1.0:
-                why = "top_k / top_p truncation is not part of it"
-            elif self.bf16w:
-                why = 'weights_dtype="bf16" is not part of it'
-            if why is not None:
-                raise RuntimeError(f"DecodeEngine: the mixed mode (mix=True) is refused: {why}")
-        if not isinstance(beam_history, (bool, np.bool_)):
-            raise RuntimeError(f"DecodeEngine: beam_history must be a bool, got {beam_history!r}")
-        self.beam_hist = bool(beam_history)
-        if self.beam_hist:
-            if self.beam == 1:
-                raise RuntimeError("DecodeEngine: beam_history keeps the histories of beam search: it needs beam > 1")
-            if self.T > CONSTRAINT_T_MAX:
-                raise RuntimeError(f"DecodeEngine: beam_history covers T <= {CONSTRAINT_T_MAX} steps, got T = {self.T}")
-            if gsk or gate_ksplit or lang_ksx:
-                raise RuntimeError("DecodeEngine: beam_history runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
-        if isinstance(beam_groups, bool) or not isinstance(beam_groups, (int, np.integer)) or beam_groups < 1:
-            raise RuntimeError(f"DecodeEngine: beam_groups must be an integer >= 1 (1 = off), got {beam_groups!r}")
-        if not (0.0 <= float(diversity) < float("inf")):
-            raise RuntimeError(f"DecodeEngine: diversity must be a finite number >= 0 (negative values are refused), got {diversity!r}")
-        if not (0.0 <= float(length_penalty) < float("inf")):
-            raise RuntimeError(f"DecodeEngine: length_penalty must be a finite number >= 0, got {length_penalty!r}")
-        self.groups, self.diversity, self.length_penalty = int(beam_groups), float(diversity), float(length_penalty)
-        self.grouped = self.groups > 1
-        if isinstance(force_n, bool) or not isinstance(force_n, (int, np.integer)) or not 0 <= force_n <= 3:
-            raise RuntimeError(f"DecodeEngine: force_n must be an integer in 0 .. 3 (0 = off), got {force_n!r}")
-        self.force_n = int(force_n)
-        self.forcing = self.force_n >= 1
-        if self.forcing:
-            if self.beam == 1:
-                raise RuntimeError("DecodeEngine: force_n is an option of beam search: it needs beam > 1")
-            if not self.beam_hist:
-                raise RuntimeError("DecodeEngine: force_n needs beam_history=True (the forced words a hypothesis has met are read from "
-                                   "its own history)")
-            if self.beam % (self.force_n + 1) != 0:
-                raise RuntimeError(f"DecodeEngine: force_n = {self.force_n} needs beam % (force_n + 1) == 0 (one bank per number of "
-                                   f"forced words met), got beam = {self.beam}")
-            if self.grouped:
-                raise RuntimeError("DecodeEngine: force_n and beam_groups > 1 exclude each other (banks and groups both divide the "
-                                   "clip's slots)")
-        # the decode ends with cvc_beam_rank (cvc_beam_rank_force) / cvc_beam_backtrack_from
-        self.ranked = self.grouped or self.length_penalty != 0.0 or self.forcing
-        if self.ranked:
-            what = "beam_groups > 1" if self.grouped else "length_penalty != 0"
-            if self.beam == 1:
-                raise RuntimeError(f"DecodeEngine: {what} is an option of beam search: it needs beam > 1")
-            if not self.beam_hist:
-                raise RuntimeError(f"DecodeEngine: {what} needs beam_history=True (the groups and the ranking read the hypotheses' "
-                                   "own histories)")
-            if self.beam % self.groups != 0:
-                raise RuntimeError(f"DecodeEngine: beam_groups = {self.groups} must divide beam = {self.beam}")
-        if self.diversity != 0.0 and not self.grouped:
-            raise RuntimeError("DecodeEngine: diversity acts between groups: it needs beam_groups > 1")
-        if not isinstance(stochastic, (bool, np.bool_)):
-            raise RuntimeError(f"DecodeEngine: stochastic must be a bool, got {stochastic!r}")
-        self.stoch = bool(stochastic)
-        if self.stoch:
-            why = None
-            if self.beam == 1 or not self.beam_hist:
-                why = "it is a beam search over hypotheses that carry their histories: it needs beam > 1 and beam_history=True"
-            elif self.grouped or self.diversity != 0.0:
-                why = "beam_groups > 1 / diversity are not part of it (the slots are one sample in draw order)"
-            elif self.length_penalty != 0.0:
-                why = "length_penalty is not part of it (the slots are ranked by their perturbed keys)"
-            elif self.forcing:
-                why = "force_n is not part of it"
-            elif temperature is not None:
-                why = "it takes no sampling temperature (stochastic_tau is its own)"
-            elif gsk or gate_ksplit or lang_ksx:
-                why = "it runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)"
-            elif not (0.0 < float(stochastic_tau) < float("inf")):
-                why = f"stochastic_tau must be a positive finite number, got {stochastic_tau!r}"
-            if why is not None:
-                raise RuntimeError(f"DecodeEngine: stochastic beam search (stochastic=True) is refused: {why}")
-            self.stoch_inv_tau = 1.0 / float(stochastic_tau)
-        if self.constrained:
-            if self.beam != 1 and not self.beam_hist:
-                raise RuntimeError("DecodeEngine: constrained decoding under beam search (beam > 1) needs beam_history=True (a "
-                                   "hypothesis' history follows its parents: it has to travel with it)")
-            if self.forced:
-                raise RuntimeError("DecodeEngine: the forced mode (forced_n) follows given words: it takes no constraints")
-            if gsk or gate_ksplit or lang_ksx:
-                raise RuntimeError("DecodeEngine: constrained decoding runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
-            if self.T > CONSTRAINT_T_MAX:
-                raise RuntimeError(f"DecodeEngine: constrained decoding covers T <= {CONSTRAINT_T_MAX} steps, got T = {self.T}")
-            bad = [v for v in self.cons[3] + self.cons[4] if v >= W.V]
-            if bad:
-                raise RuntimeError(f"DecodeEngine: ban_words / bad_endings ids outside [0, V = {W.V}): {bad}")
-            gate_ksplit, lang_ksx = False, False
-        if self.bf16w:
-            why = None
-            if self.beam != 1:
-                why = f"beam search (beam = {self.beam}) runs on the tile path"
-            elif int(sample_n) != 1:
-                why = f"sample_n = {sample_n} > 1 runs on the tile path"
-            elif int(forced_n) > 1:
-                why = f"forced_n = {forced_n} > 1 runs on the tile path"
-            elif path in ("tile", "ring"):
-                why = f'path="{path}" was asked for'
-            elif gsk or gate_ksplit or lang_ksx:
-                why = "gsk / gate_ksplit / lang_ksx are experimental schedules of the fp32 kernels"
-            elif embgate is not None and not embgate:
-                why = "embgate=False: the packed path without the embedding-gate schedule"
-            if why is not None:
-                raise RuntimeError(f'DecodeEngine: weights_dtype="bf16" covers the packed path with the embedding-gate schedule only '
-                                   f"(beam = 1, one caption per clip, <= 64 rows); refused: {why}")
-            gsk, gate_ksplit, lang_ksx = False, False, False
-        self.sampling = temperature is not None
-        # the next step's word is read from words[t + 1] (sampled there by the selection block, or given): the sampling launch lists
-        # (constrained beam search chooses in the beam block and reorders by parent like every beam engine)
-        self.given = self.sampling or self.forced or (self.constrained and self.beam == 1)
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0:
-            raise RuntimeError(f"DecodeEngine: top_k must be an integer >= 0 (0 = off), got {top_k!r}")
-        if not (0.0 < float(top_p) <= 1.0):
-            raise RuntimeError(f"DecodeEngine: top_p must lie in (0, 1] (1 = off), got {top_p!r}")
-        self.top_k, self.top_p = int(top_k), float(top_p)
-        self.trunc = self.top_k > 0 or self.top_p < 1.0
-        if self.trunc and not self.sampling:
-            raise RuntimeError("DecodeEngine: top_k / top_p truncate the sampled distribution: they need a sampling temperature")
-        if self.sampling:
-            tau = float(temperature)
-            if not (0.0 < tau < float("inf")):
-                raise RuntimeError(f"DecodeEngine: the sampling temperature must be a positive finite number, got {temperature!r}")
-            if self.beam != 1:
-                raise RuntimeError("DecodeEngine: sampling (temperature) and beam search (beam > 1) exclude each other")
-            if gsk or gate_ksplit or lang_ksx:
-                raise RuntimeError("DecodeEngine: sampling runs on the default schedules only (no gsk / gate_ksplit / lang_ksx)")
-            if int(sample_n) < 1:
-                raise RuntimeError(f"DecodeEngine: sample_n must be >= 1, got {sample_n}")
-            self.inv_tau = 1.0 / tau
-            gate_ksplit, lang_ksx = False, False
-        elif self.constrained:
-            self.inv_tau = 0.0                   # the constrained block's arg-max mode
-        if not self.sampling and int(sample_n) != 1:
-            raise RuntimeError("DecodeEngine: sample_n > 1 needs a sampling temperature")
-        # queries per clip: the beams of beam search, the samples of sampled decoding (attention passes, gate_fc rows)
-        self.nq = int(sample_n) if self.sampling else (int(forced_n) if self.forced else self.beam)
+        self.unk = int(unk_idx)
         fc, conv, pconv = feats["fc_feats"], feats["conv_feats"], feats["p_conv_feats"]
         pool, ppool = feats["pool_feats"], feats["p_pool_feats"]
         mask = feats["pnt_mask"][:, 1:] if feats["pnt_mask"].shape[1] == pool.shape[1] + 1 else feats["pnt_mask"]
@@ -371,8 +190,53 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.mask = self.mask.clone()
         self.own_features = own_features
         self.feats = (fc, conv, pconv, pool, ppool)
-        nb = lambda t: t.numel() * t.element_size()
         rows = self.rows = B * self.nq
+        # ---- the schedules: what depends on the batch and on the library (the order decides which refusal fires)
+        self.packed = packed
+        # packed path: K-split gate GEMMs (activations shared through LDS, csrc/gemm_packed_ks.hip) where the shape allows
+        # (True: partial tiles + a finishing launch; "fused": the last-arriving K slice of a tile finishes it in the same launch)
+        self.gate_ksplit = GATE_KSPLIT_DEFAULT if gate_ksplit is None else gate_ksplit
+        self.gate_fused = self.gate_ksplit == "fused"
+        self.gate_ksplit = bool(self.gate_ksplit)
+        gsk_ok = self.packed and R % 64 == 0 and not self.gate_ksplit and hip.gemm_packed_split(-1) == 2
+        if gsk and not gsk_ok:
+            raise RuntimeError("DecodeEngine: the stream-K schedule needs the packed path, R % 64 == 0 and cvc_gemm_packed_split(2)")
+        self.gsk = False if gsk is None else bool(gsk)
+        # more than 64 live rows (beam search, big greedy batches): bf16-fragment tile GEMMs (csrc/gemm_tile.hip)
+        self.tile = (not self.packed) and (self.nq > 1 or rows > 64 or path == "tile") and R % 16 == 0 and W.E % 16 == 0 and path != "ring"
+        eg_ok = (self.packed and not self.gsk and not self.gate_ksplit) or self.tile
+        if embgate and not eg_ok:
+            raise RuntimeError("DecodeEngine: the embedding-gate schedule needs the packed path (without gsk / gate_ksplit) or the tile path")
+        self.embgate = (eg_ok and 4 * V * 4 * R <= EMBGATE_MAX_BYTES) if embgate is None else bool(embgate)
+        if self.given and self.packed and not self.embgate:
+            raise RuntimeError(f"DecodeEngine: {'sampling' if self.sampling else 'the forced mode' if self.forced else 'constrained decoding'} on the packed path needs the "
+                               "embedding-gate schedule (the attention cell reads the word from words[t])")
+        if self.bf16w and not (self.packed and self.embgate):
+            raise RuntimeError('DecodeEngine: weights_dtype="bf16" needs the embedding-gate schedule, and its table '
+                               f"({4 * V * 4 * R} bytes) is over EMBGATE_MAX_BYTES")
+        exp = hip.experimental_built()          # gsk / gate_ksplit / lang_ksx: forms of include/cvc_hip_experimental.h
+        if not exp and (self.gsk or self.gate_ksplit or lang_ksx):
+            raise RuntimeError("DecodeEngine: gsk / gate_ksplit / lang_ksx are experimental schedules (include/cvc_hip_experimental.h): "
+                               "this libcvc_hip.so was built without CVC_EXPERIMENTAL=1")
+        ksx_ok = (exp and self.packed and not self.gsk and not self.gate_ksplit and R == 2048 and self.T > 1 and
+                  hip.gemm_packed_split(-1) == 2 and int(hip.lib().cvc_packed_lstm_ks_slices(3 * R, R)) == 8)
+        if lang_ksx and not ksx_ok:
+            raise RuntimeError("DecodeEngine: lang_ksx needs the packed path at R = 2048, T > 1, split-product arithmetic")
+        self.lang_ksx = ksx_ok and not self.bf16w and (LANG_KSX_DEFAULT if lang_ksx is None else bool(lang_ksx))
+        fused_ok = (self.packed and self.embgate and not self.given and not self.bf16w and not self.gsk and not self.gate_ksplit and
+                    not self.lang_ksx and self.beam == 1 and self.unk >= 0 and hip.gemm_packed_split(-1) == 2)
+        if tail is None:
+            tail = TAIL_DEFAULT if fused_ok else "launch"
+        if tail not in TAILS:
+            raise RuntimeError(f"DecodeEngine: tail must be one of {TAILS} (or None), got {tail!r}")
+        if tail == "fused" and not fused_ok:
+            raise RuntimeError('DecodeEngine: tail="fused" covers plain greedy decode on the packed embedding-gate schedule only (beam = 1, '
+                               "<= 64 rows, fp32 weights, no sampling / forced / constrained mode, no gsk / gate_ksplit / lang_ksx, "
+                               "cvc_gemm_packed_split(2))")
+        self.tail = tail
+        self.fused_tail = tail == "fused"
+        # ---- state and buffers
+        nb = lambda t: t.numel() * t.element_size()
         f32 = dict(device=dev, dtype=torch.float32)
         z = lambda *s: torch.zeros(*s, **f32)
         # ping-pong recurrent state: index t & 1 is read, (t+1) & 1 is written
@@ -438,30 +302,8 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.inv_temp = float(inv_temp)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
-        self.packed = packed
-        # packed path: K-split gate GEMMs (activations shared through LDS, csrc/gemm_packed_ks.hip) where the shape allows
-        # (True: partial tiles + a finishing launch; "fused": the last-arriving K slice of a tile finishes it in the same launch)
-        self.gate_ksplit = GATE_KSPLIT_DEFAULT if gate_ksplit is None else gate_ksplit
-        self.gate_fused = self.gate_ksplit == "fused"
-        self.gate_ksplit = bool(self.gate_ksplit)
-        gsk_ok = self.packed and R % 64 == 0 and not self.gate_ksplit and hip.gemm_packed_split(-1) == 2
-        if gsk and not gsk_ok:
-            raise RuntimeError("DecodeEngine: the stream-K schedule needs the packed path, R % 64 == 0 and cvc_gemm_packed_split(2)")
-        self.gsk = False if gsk is None else bool(gsk)
-        # more than 64 live rows (beam search, big greedy batches): bf16-fragment tile GEMMs (csrc/gemm_tile.hip)
-        self.tile = (not self.packed) and (self.nq > 1 or rows > 64 or path == "tile") and R % 16 == 0 and W.E % 16 == 0 and path != "ring"
-        eg_ok = (self.packed and not self.gsk and not self.gate_ksplit) or self.tile
-        if embgate and not eg_ok:
-            raise RuntimeError("DecodeEngine: the embedding-gate schedule needs the packed path (without gsk / gate_ksplit) or the tile path")
-        self.embgate = (eg_ok and 4 * V * 4 * R <= EMBGATE_MAX_BYTES) if embgate is None else bool(embgate)
-        if self.given and self.packed and not self.embgate:
-            raise RuntimeError(f"DecodeEngine: {'sampling' if self.sampling else 'the forced mode' if self.forced else 'constrained decoding'} on the packed path needs the "
-                               "embedding-gate schedule (the attention cell reads the word from words[t])")
         # what stays in the Infinity Cache between steps: small linear weights, then (embedding-gate schedule on the packed path) the
         # attention cell's gate matrix over K = 2R if it fits, then the largest subset of the feature tensors
-        if self.bf16w and not (self.packed and self.embgate):
-            raise RuntimeError('DecodeEngine: weights_dtype="bf16" needs the embedding-gate schedule, and its table '
-                               f"({4 * V * 4 * R} bytes) is over EMBGATE_MAX_BYTES")
         bpw = 2 if self.bf16w else 4                       # bytes per stored weight
         keep = cache_plan(bpw * (V * R + A * R), {"ppool": nb(ppool), "pconv": nb(pconv), "pool": nb(pool), "conv": nb(conv)},
                           gate_weight_bytes=bpw * 4 * R * 2 * R if (self.packed and self.embgate and (rows > 32 or self.bf16w)) else None,
@@ -474,15 +316,6 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.stream_f = (0 if keep["pconv"] else 1) | (0 if keep["conv"] else 2)
         self._plan = None
         self._driver = driver
-        exp = hip.experimental_built()          # gsk / gate_ksplit / lang_ksx: forms of include/cvc_hip_experimental.h
-        if not exp and (self.gsk or self.gate_ksplit or lang_ksx):
-            raise RuntimeError("DecodeEngine: gsk / gate_ksplit / lang_ksx are experimental schedules (include/cvc_hip_experimental.h): "
-                               "this libcvc_hip.so was built without CVC_EXPERIMENTAL=1")
-        ksx_ok = (exp and self.packed and not self.gsk and not self.gate_ksplit and R == 2048 and self.T > 1 and
-                  hip.gemm_packed_split(-1) == 2 and int(hip.lib().cvc_packed_lstm_ks_slices(3 * R, R)) == 8)
-        if lang_ksx and not ksx_ok:
-            raise RuntimeError("DecodeEngine: lang_ksx needs the packed path at R = 2048, T > 1, split-product arithmetic")
-        self.lang_ksx = ksx_ok and not self.bf16w and (LANG_KSX_DEFAULT if lang_ksx is None else bool(lang_ksx))
         self._ksx_checked = False
         if self.lang_ksx:
             self.ksx_slab = torch.empty(8 * (R // 8) * 2048, device=dev, dtype=torch.float32)
@@ -491,18 +324,6 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self._alloc_packed()
         elif self.tile:
             self._alloc_tile()
-        fused_ok = (self.packed and self.embgate and not self.given and not self.bf16w and not self.gsk and not self.gate_ksplit and
-                    not self.lang_ksx and self.beam == 1 and self.unk >= 0 and hip.gemm_packed_split(-1) == 2)
-        if tail is None:
-            tail = TAIL_DEFAULT if fused_ok else "launch"
-        if tail not in TAILS:
-            raise RuntimeError(f"DecodeEngine: tail must be one of {TAILS} (or None), got {tail!r}")
-        if tail == "fused" and not fused_ok:
-            raise RuntimeError('DecodeEngine: tail="fused" covers plain greedy decode on the packed embedding-gate schedule only (beam = 1, '
-                               "<= 64 rows, fp32 weights, no sampling / forced / constrained mode, no gsk / gate_ksplit / lang_ksx, "
-                               "cvc_gemm_packed_split(2))")
-        self.tail = tail
-        self.fused_tail = tail == "fused"
         if self.fused_tail:
             # [T][4][64] candidate keys, then [T][64] UNK keys (64-bit words; cleared at the start of every decode), and the
             # per-step (max, sum-exp) records of the head's blocks
@@ -589,15 +410,6 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     # ------------------------------------------------------------------ packed path (greedy, rows <= 64)
 
     def _reset(self):
-        if self.tile:
-            self.words[0].zero_()
-            if self.beam > 1:
-                self.score.zero_()
-                self.done.zero_()
-                if self.stoch:
-                    self.logq.zero_()
-                    self.G.zero_()
-            return
         if self.packed:
             self.XA[0].copy_(self.XA0_init)
             self.XL[0].zero_()
@@ -607,8 +419,9 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             if self.fused_tail:
                 self.tail_keys.zero_()
             return
-        for bufs in (self.h_att, self.c_att, self.h_lang, self.c_lang):
-            bufs[0].zero_()
+        if not self.tile:                    # (the tile path's first launch packs its state from t_zero)
+            for bufs in (self.h_att, self.c_att, self.h_lang, self.c_lang):
+                bufs[0].zero_()
         self.words[0].zero_()
         if self.beam > 1:
             self.score.zero_()
@@ -918,8 +731,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                 self._run_once()
             torch.cuda.current_stream().wait_stream(s)
             self.check_ksx()
-        key = (self.packed, self.tile, self.beam > 1, self.sampling, self.weights_dtype, self.trunc, self.forced, self.constrained,
-               self.beam_hist, self.grouped, self.ranked, self.forcing, self.fused_tail, self.mix, self.stoch)
+        key = (self.packed, self.tile, self.fused_tail) + self.mode.flags
         if key not in DecodeEngine._warm:                 # first capture of this path in the process: run once outside capture
             saved = self.rng.clone() if (self.sampling or self.stoch) else None     # (the warm-up decode must not advance the sampling state)
             s = torch.cuda.Stream()                       # (module load, lazy init); later engines skip the extra decode

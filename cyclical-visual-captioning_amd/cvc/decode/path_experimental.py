@@ -4,8 +4,6 @@ cvc.decode.engine.DecodeEngine; nothing here runs unless asked for (gsk / gate_k
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Dict, List, Optional, Tuple
 
 import torch
 

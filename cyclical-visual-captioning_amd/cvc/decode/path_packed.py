@@ -4,10 +4,6 @@ enqueues the same list from a bound descriptor); with the fused tail (tail="fuse
 launches per step and one finishing launch per decode.  Mixin of cvc.decode.engine.DecodeEngine."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-from typing import Dict, List, Optional, Tuple
-
 import torch
 
 from .. import hip

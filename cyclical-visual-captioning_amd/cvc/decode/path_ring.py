@@ -2,10 +2,6 @@
 LDS-DMA ring kernels (csrc/gemm_skinny.hip).  Mixin of cvc.decode.engine.DecodeEngine."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-from typing import Dict, List, Optional, Tuple
-
 import torch
 
 from .. import hip

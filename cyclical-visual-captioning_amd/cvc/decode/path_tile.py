@@ -2,9 +2,7 @@
 (csrc/gemm_tile.hip), 12 launches per step.  Mixin of cvc.decode.engine.DecodeEngine."""
 from __future__ import annotations
 
-import ctypes as C
 import os
-from typing import Dict, List, Optional, Tuple
 
 import torch
 

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import hip
+from .mode import WEIGHTS_DTYPES        # noqa: F401  ("fp32", "bf16": checked with every other option in cvc/decode/mode.py)
 
 
 class DecodeWeights:
@@ -138,7 +139,6 @@ def lstm_packed_rows(R: int, device) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ bf16-stored weights (the WB16 mode of csrc/gemm_packed.hip)
-WEIGHTS_DTYPES = ("fp32", "bf16")
 # the six matrices DecodeEngine(weights_dtype="bf16") rounds when it binds a checkpoint (state_dict names)
 BF16_ROUNDED_KEYS = ("decoder_core.att_lstm.weight_ih", "decoder_core.att_lstm.weight_hh", "decoder_core.lang_lstm.weight_ih",
                      "decoder_core.lang_lstm.weight_hh", "decoder_core.soft_attn.h2attn.weight", "logit.weight")

@@ -616,6 +616,40 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 ent[1].weights_refreshed()
         hip.bump_weights_generation()
 
+    # ------------------------------------------------------------------ the cached decode engines
+    def _decode_engine(self, slot, feats, T, extra=(), unkeyed=(), may_bind=False, prepare=None, **options):
+        """The engine of `slot` (_engine_cache / _score_cache / _ss_cache, each one (key, engine)) with this batch's features in it:
+        the cached one when its key matches -- the batch is copied into the engine's own buffers (0.2 ms at cfg2; a captured graph
+        keeps the pointers it was captured with), or with may_bind the C-ABI plan of a driver-bound engine without a graph is
+        pointed at the new tensors -- else a new DecodeEngine(**options), captured when the model uses HIP graphs, which replaces
+        the slot's.  The key is made of what the engine is built from: the weights object, the feature shapes, softmax_temp, T,
+        use_hip_graph and every option passed on (lists as tuples), so no option reaches the engine without being in the key;
+        `unkeyed` names options that do not distinguish engines (a seed that is set again on every call), `extra` adds what
+        distinguishes them without being an option.  prepare(engine): what has to be bound before capture on a new engine, and
+        after the features on a cached one (the forced mode's captions and frame mask)."""
+        temp = float(getattr(self.opts, "softmax_temp", 1.0))
+        weights = self.decode_weights()
+        hashable = lambda v: tuple(v) if isinstance(v, (list, tuple)) else v
+        key = ((id(weights),) + tuple(tuple(feats[k].shape) for k in ("fc_feats", "conv_feats", "pool_feats")) +
+               (temp, T, self.use_hip_graph, tuple(extra)) + tuple((k, hashable(v)) for k, v in sorted(options.items()) if k not in unkeyed))
+        cached = getattr(self, slot, None)
+        if cached is not None and cached[0] == key:
+            engine = cached[1]
+            if may_bind and engine._plan is not None and engine.graph is None:
+                engine.bind_features(feats)
+            else:
+                engine.load_features(feats)
+            if prepare is not None:
+                prepare(engine)
+            return engine
+        engine = DecodeEngine(weights, feats, T, self.unk_idx, inv_temp=1.0 / temp, own_features=True, **options)
+        if prepare is not None:
+            prepare(engine)
+        if self.use_hip_graph:
+            engine.capture()
+        setattr(self, slot, (key, engine))
+        return engine
+
     # ------------------------------------------------------------------ scheduled sampling: the rollout
     @torch.no_grad()
     def ss_rollout(self, encoded, gt_caption, prob: float, temperature: float = 1.0, seed: int = 0):
@@ -637,20 +671,9 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         try:
             feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
                          pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
-            temp = float(getattr(self.opts, "softmax_temp", 1.0))
-            weights = self.decode_weights()
-            key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), temp, T, self.use_hip_graph,
-                   float(temperature), S)
-            cached = getattr(self, "_ss_cache", None)
-            if cached is not None and cached[0] == key:
-                engine = cached[1]
-                engine.load_features(feats)
-            else:
-                engine = DecodeEngine(weights, feats, T, self.unk_idx, inv_temp=1.0 / temp, own_features=True, sample_n=S,
-                                      temperature=float(temperature), seed=seed, mix=True)
-                if self.use_hip_graph:
-                    engine.capture()
-                self._ss_cache = (key, engine)
+            # (the seed is no part of the key: the engine is re-seeded on every call)
+            engine = self._decode_engine("_ss_cache", feats, T, unkeyed=("seed",), sample_n=S, temperature=float(temperature), seed=seed,
+                                         mix=True)
             engine.load_captions(given)
             engine.set_mix_prob(prob)
             engine.seed(seed)
@@ -727,7 +750,6 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         feats = dict(fc_feats=fc_feats.contiguous(), conv_feats=conv_feats.contiguous(), p_conv_feats=p_conv_feats.contiguous(),
                      pool_feats=pool_feats.contiguous(), p_pool_feats=p_pool_feats.contiguous(), pnt_mask=pnt_mask)
         beam = self.beam_size if beam_size is None else int(beam_size)
-        temp = float(getattr(self.opts, "softmax_temp", 1.0))
         sampling = mode == "samples" or (self.sample_max if sample_max is None else int(sample_max)) == 0
         d_tau, d_n, d_seed = ((self.consensus_temperature, self.consensus_samples, self.consensus_seed) if mode == "samples" else
                               (self.sample_temperature, self.sample_n, self.sample_seed))
@@ -764,31 +786,15 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if force_words is not None and not isinstance(force_words, torch.Tensor):        # ids applied to every clip
             force_words = torch.tensor([int(w) for w in force_words], dtype=torch.int64).view(1, -1).expand(fc_feats.shape[0], -1)
         force_n = 0 if force_words is None else int(force_words.shape[-1])
-        weights = self.decode_weights()
-        # one engine (bound launch list + captured graph) per batch shape, reused across the batches of an evaluation
-        # loop: the next batch is copied into the engine's own feature buffers instead of re-binding and re-capturing
-        key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), beam, temp, self.seq_length,
-               self.use_hip_graph, tau, n, s_seed, wdtype, k, p, force_n, tuple(cons.values()), groups, lam, alpha) + (mode is not None,) + ((stoch, stau) if stoch else ())
-        cached = getattr(self, "_engine_cache", None)
-        if cached is not None and cached[0] == key:
-            engine = cached[1]
-            # next batch of the same shape.  Driver-bound engine without a graph: the C-ABI plan is simply pointed at the new
-            # tensors.  Graph replay (or the ring fallback for odd widths): the batch is copied into the engine's own buffers
-            # (0.2 ms at cfg2) -- a captured graph keeps the pointers it was captured with.
-            if engine._plan is not None and engine.graph is None:
-                engine.bind_features(feats)
-            else:
-                engine.load_features(feats)
-        else:
-            engine = DecodeEngine(weights, feats, self.seq_length, self.unk_idx, beam=beam, inv_temp=1.0 / temp, own_features=True,
-                                  sample_n=n, temperature=tau, seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
-                                  beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0)
-                                  or (beam > 1 and mode is not None) or stoch,      # (consensus chooses among hypotheses())
-                                  beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n,
-                                  **(dict(stochastic=True, stochastic_tau=stau) if stoch else {}), **cons)
-            if self.use_hip_graph:
-                engine.capture()
-            self._engine_cache = (key, engine)
+        # "consensus on" is part of the key although it changes no argument of a sampling engine: a consensus call must not take
+        # over the generator state of the previous call's engine (its candidates are what the same call draws without consensus)
+        engine = self._decode_engine(
+            "_engine_cache", feats, self.seq_length, extra=(mode is not None,), may_bind=True, beam=beam, sample_n=n, temperature=tau,
+            seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
+            beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0)
+            or (beam > 1 and mode is not None) or stoch,      # (consensus chooses among hypotheses())
+            beam_groups=groups, diversity=lam, length_penalty=alpha, force_n=force_n,
+            **(dict(stochastic=True, stochastic_tau=stau) if stoch else {}), **cons)
         if force_n > 0:
             engine.load_force_words(force_words)
         res = engine.run()
@@ -851,25 +857,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if grounding:
             # label glue exactly as _forward_3_loops does it: per-word proposal labels and the frame mask on proposals
             roi_labels, frm_mask_output, step_fmask = hip.label_glue(overlaps, mask_boxes[:, 0, :, 1:T + 1], frm_mask, pnt_mask)
-        temp = float(getattr(self.opts, "softmax_temp", 1.0))
         wdtype = self.decode_weights_dtype if decode_weights is None else decode_weights
-        weights = self.decode_weights()
-        # one forced engine per batch shape, in a slot of its own: a score call between two _sample calls evicts nothing there
-        key = (id(weights), tuple(fc_feats.shape), tuple(conv_feats.shape), tuple(pool_feats.shape), temp, T, self.use_hip_graph, n,
-               wdtype, bool(grounding))
-        cached = getattr(self, "_score_cache", None)
         captions = captions.contiguous()
-        if cached is not None and cached[0] == key:
-            engine = cached[1]
-            engine.load_features(feats)
-            engine.load_captions(captions, step_fmask)
-        else:
-            engine = DecodeEngine(weights, feats, T, self.unk_idx, inv_temp=1.0 / temp, own_features=True, forced_n=n,
-                                  weights_dtype=wdtype)
-            engine.load_captions(captions, step_fmask)         # (the frame mask is part of the launch list: before capture)
-            if self.use_hip_graph:
-                engine.capture()
-            self._score_cache = (key, engine)
+        # one forced engine per batch shape, in a slot of its own: a score call between two _sample calls evicts nothing there
+        # (the frame mask is part of the launch list: it is bound before capture, and grounding is part of the key)
+        engine = self._decode_engine("_score_cache", feats, T, extra=(bool(grounding),), forced_n=n, weights_dtype=wdtype,
+                                     prepare=lambda e: e.load_captions(captions, step_fmask))
         _seq, att, logprob, rank = engine.run()
         first0 = (captions == 0).long().cumsum(1)
         mask = (first0 == 0) | ((first0 == 1) & (captions == 0))           # steps up to and including the first 0 (LMCriterion)

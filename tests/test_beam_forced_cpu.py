@@ -166,7 +166,9 @@ def test_model_cli_and_docs_know_the_switches():
     from cvc import main as cvc_main
     src = inspect.getsource(captioner)
     assert re.search(r"beam_history=beam > 1 and \(any\(cons\.values\(\)\).*or force_n > 0\)", src)
-    assert re.search(r"k, p, force_n, tuple\(cons\.values\(\)\)", src)                     # the engine-cache key
+    # the engine-cache key is made of every option _sample passes on (the key itself: tests/test_decode_mode_cpu.py)
+    call = re.search(r'self\._decode_engine\(\s*"_engine_cache".*?\*\*cons\)', src, re.S).group(0)
+    assert "top_k=k, top_p=p" in call and "force_n=force_n" in call
     assert "force_words" in inspect.signature(captioner.DecodeAndGroundCaptionerGVDROI._sample).parameters
     main_src = inspect.getsource(cvc_main)
     assert all(f'"--{k}"' in main_src for k in ("force_words", "force_detected"))

@@ -140,7 +140,9 @@ def test_model_cli_and_docs_know_the_switches():
     from cvc import main as cvc_main
     src = inspect.getsource(captioner)
     assert re.search(r"beam_history=beam > 1 and \(any\(cons\.values\(\)\) or groups > 1", src)
-    assert re.search(r"tuple\(cons\.values\(\)\), groups, lam, alpha\)", src)               # the engine-cache key
+    # the engine-cache key is made of every option _sample passes on (the key itself: tests/test_decode_mode_cpu.py)
+    call = re.search(r'self\._decode_engine\(\s*"_engine_cache".*?\*\*cons\)', src, re.S).group(0)
+    assert "beam_groups=groups, diversity=lam, length_penalty=alpha" in call
     params = inspect.signature(captioner.DecodeAndGroundCaptionerGVDROI._sample).parameters
     assert all(k in params for k in ("beam_groups", "diversity_lambda", "length_penalty"))
     main_src = inspect.getsource(cvc_main)
