@@ -758,6 +758,14 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.rng.copy_(torch.from_numpy(words))
         return self
 
+    @property
+    def rng_state(self) -> torch.Tensor:
+        """The generator words {seed_lo, seed_hi, call, 0} (int32 [4], device memory, the engine's own buffer): after run() `call` is
+        the one that decode drew its noise with -- what cvc_scst_weights_wor hashes its per-clip root key from.  Read-only."""
+        if not self.sampling and not self.stoch:
+            raise RuntimeError("DecodeEngine.rng_state: this engine does not sample (temperature=None)")
+        return self.rng
+
     def run(self):
         """One full T-step decode.  Returns (seq [B,T] int64, att2_weights [B,T,N]) -- views of
         engine-owned buffers (clone to keep across runs).  Sampling: (seq [B*n, T], att2_weights [B*n, T, N],

@@ -271,6 +271,8 @@ SIGNATURES = {
     # self-critical training: CIDEr-D reward and per-token loss weights (csrc/cider.hip; building blocks)
     "cvc_cider_d": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P],
     "cvc_scst_weights": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P],
+    # self-critical training without replacement: importance weights, per-row baseline, per-token weights (csrc/scst_wor.hip; building block)
+    "cvc_scst_weights_wor": [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     # token-overlap caption metrics: BLEU statistics, sentence BLEU, ROUGE-L (csrc/overlap.hip; building block)
     "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # consensus caption selection: pairwise CIDEr-D among a clip's candidates, pick and picked row (csrc/consensus.hip; building block)
@@ -325,7 +327,7 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
+    "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
     "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
@@ -1212,6 +1214,29 @@ def scst_weights(reward: torch.Tensor, base: Optional[torch.Tensor], per_clip: i
     _check(lib().cvc_scst_weights(_dev(reward, name="reward"), _dev(base, name="base"), rows, int(per_clip), _dev(cand, torch.int64, "cand"),
                                   T, 1 if t_major else 0, _dev(adv), _dev(w), _stream()), "cvc_scst_weights")
     return adv, w
+
+
+def scst_weights_wor(reward: torch.Tensor, logq: torch.Tensor, G: torch.Tensor, state: torch.Tensor, per_clip: int, cand: torch.Tensor,
+                     t_major: bool = False, normalize: bool = True):
+    """Self-critical weights of captions sampled without replacement (csrc/scst_wor.hip; the rule: include/cvc_hip_blocks.h).
+    reward [rows] of the S = per_clip rollouts per clip; logq, G [rows / S, S + 1] the stochastic beam's sampling log-probs and
+    perturbed keys (beam = S + 1: slot S is the threshold); state: the engine's generator words, int32 [4] (DecodeEngine.rng_state);
+    cand [rows, T] int64 -> adv [rows], wgt [rows], est [rows / S], w [rows, T] (t_major: [T, rows])"""
+    S = int(per_clip)
+    if cand.dim() != 2 or S < 1 or reward.numel() != cand.shape[0] or cand.shape[0] % S != 0 or state.numel() != 4 \
+            or logq.numel() != (cand.shape[0] // S) * (S + 1) or G.numel() != logq.numel():
+        raise RuntimeError(f"cvc.hip.scst_weights_wor: reward {tuple(reward.shape)}, logq {tuple(logq.shape)}, G {tuple(G.shape)}, state "
+                           f"{tuple(state.shape)}, per_clip {per_clip}, cand {tuple(cand.shape)} do not fit")
+    rows, T = cand.shape
+    dev = cand.device
+    adv = torch.empty(rows, device=dev, dtype=torch.float32)
+    wgt = torch.empty(rows, device=dev, dtype=torch.float32)
+    est = torch.empty(rows // S, device=dev, dtype=torch.float32)
+    w = torch.empty((T, rows) if t_major else (rows, T), device=dev, dtype=torch.float32)
+    _check(lib().cvc_scst_weights_wor(_dev(reward, name="reward"), _dev(logq, name="logq"), _dev(G, name="G"),
+                                      _dev(state, torch.int32, "state"), rows, S, _dev(cand, torch.int64, "cand"), T, 1 if t_major else 0,
+                                      1 if normalize else 0, _dev(adv), _dev(wgt), _dev(est), _dev(w), _stream()), "cvc_scst_weights_wor")
+    return adv, wgt, est, w
 
 
 # --------------------------------------------------------------------------- token-overlap caption metrics (csrc/overlap.hip)

@@ -67,6 +67,9 @@ def build_parser():
     parser.add_argument("--scst_seed", type=int, default=1, help="seed of the rollouts' noise")
     parser.add_argument("--scst_dropout", action="store_true",
                         help="keep the training dropout on in the self-critical gradient pass (default: off, the policy that was sampled)")
+    parser.add_argument("--scst_wor", action="store_true",
+                        help="draw the self-critical rollouts WITHOUT replacement (a stochastic beam of scst_samples + 1 slots: no two "
+                             "rollouts of a clip are the same sentence) and weight them by importance; 2 <= scst_samples <= 7")
     parser.add_argument("--scst_reward", type=str, default="cider:1",
                         help="the self-critical reward as name:weight pairs over cider, bleu1..bleu4, rougel (cvc.metrics), e.g. "
                              "cider:1,bleu4:0.5,rougel:0.5; the weights apply to the raw scales: CIDEr-D in [0, 10], the others in [0, 1]")
@@ -172,6 +175,9 @@ def main(argv=None, sample=None, score=None):
         raise SystemExit("--group_size must be >= 1, --diversity_lambda and --length_penalty >= 0")
     if opt.scst_samples < 1 or opt.scst_temperature <= 0:
         raise SystemExit("--scst_samples must be >= 1 and --scst_temperature > 0")
+    if opt.scst_wor and not 2 <= opt.scst_samples <= 7:
+        raise SystemExit("--scst_wor needs 2 <= --scst_samples <= 7 (a stochastic beam of scst_samples + 1 <= 8 slots; one rollout's own "
+                         "baseline cancels it)")
     if (opt.scheduled_sampling_increase_every < 1 or opt.scheduled_sampling_temperature <= 0 or opt.scheduled_sampling_increase_prob < 0
             or not 0 <= opt.scheduled_sampling_max_prob <= 1):
         raise SystemExit("--scheduled_sampling_increase_every must be >= 1, --scheduled_sampling_temperature > 0, "

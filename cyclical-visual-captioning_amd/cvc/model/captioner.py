@@ -498,7 +498,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 None if fms[0] is None else torch.cat(fms, 1))
 
     # ------------------------------------------------------------------ self-critical training: the gradient pass
-    def scst_loss(self, encoded, words, reward, base=None, per_clip: int = 1):
+    def scst_loss(self, encoded, words, reward, base=None, per_clip: int = 1, wor=None):
         """The self-critical loss of sampled captions: loop A (reference :242-270) teacher-forced on the SAMPLED words, the vocabulary
         head and its criterion with the advantage as row weight:  -sum_{r,t} w[r, t] log p(words[r, t]) / sum(mask),
         w = advantage x mask (cvc_scst_weights; mask = LMCriterion's: the steps up to and including the first 0).
@@ -507,6 +507,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         words [B * per_clip, T] int64, row b * per_clip + j = sample j of clip b; reward [B * per_clip]; base [B] (per_clip == 1:
         the greedy caption's reward) or None (per_clip > 1: leave-one-out mean of the clip's other samples).
         Dropout follows the module's mode: eval() = the policy that was sampled.  More than 64 rows run loop A as groups of <= 64.
+        wor = dict(logq=, G=, state=, normalize=True): the rows are a stochastic beam's first per_clip slots, a sample WITHOUT
+        replacement (logq, G [B, per_clip + 1] with the threshold slot, state the engine's generator words: model.last_stochastic);
+        w comes from cvc_scst_weights_wor -- importance weights and a per-row baseline ("Self-critical training
+        without replacement") --, base must be None, and self.last_wor = dict(wgt [B * per_clip], est [B]) keeps the weights and the
+        clip's estimated expected reward.  None: cvc_scst_weights, the launches and the bits of a step without it.
         -> (loss (), adv [B * per_clip])"""
         from .. import train_loops
         fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
@@ -556,7 +561,14 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 steps.append(output)
             out = torch.stack(steps, 1).view(rows * T, R)
             t_major = False
-        adv, w = hip.scst_weights(reward, base, S, words, t_major=t_major)
+        if wor is None:
+            adv, w = hip.scst_weights(reward, base, S, words, t_major=t_major)
+        else:
+            if base is not None:
+                raise RuntimeError("scst_loss: wor carries its own per-row baseline, base must be None")
+            adv, wgt, est, w = hip.scst_weights_wor(reward, wor["logq"], wor["G"], wor["state"], S, words, t_major=t_major,
+                                                    normalize=bool(wor.get("normalize", True)))
+            self.last_wor = dict(wgt=wgt, est=est)
         if self.debug_collect is not None:
             self.debug_collect.update(scst_out=out, scst_t_major=t_major, scst_w=w)
         loss = self.xe_criterion.from_head(out, self.logit, target, t_major=t_major, row_weight=w)
@@ -733,7 +745,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         search with beam_size > 1 -- the engine is built with beam_history=True and stochastic=True, seeded once with seed (else the
         model's sample_seed); the result is a beam decode's (seq, att2_weights, None) of slot 0, an ordinary sample of q_tau, and
         self.last_stochastic = dict(seq [B, beam, T], score, G, logq [B, beam]) keeps the clip's beam_size distinct captions in
-        draw order with their model log-probs, perturbed keys and sampling log-probs (clones).  It composes with the five
+        draw order with their model log-probs, perturbed keys and sampling log-probs, and state, the generator words the decode drew
+        its noise with (clones).  It composes with the five
         constraints and with consensus "beam" / True (the candidates are the distinct samples); what the engine refuses raises."""
         mode = self.consensus if consensus is None else consensus
         mode = "on" if mode is True else (None if (not mode or mode == "off") else mode)
@@ -800,6 +813,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         res = engine.run()
         if stoch:
             self.last_stochastic = dict(zip(("seq", "score", "G", "logq"), (x.clone() for x in engine.hypotheses())))
+            self.last_stochastic["state"] = engine.rng_state.clone()     # the generator words this decode drew with (scst_loss(wor=))
         if mode is not None:
             seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table)
             self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility)

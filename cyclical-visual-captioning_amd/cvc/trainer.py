@@ -121,7 +121,11 @@ class Trainer:
         self.last_scst = None
         # the reward mix {name: weight} (cvc.metrics.REWARD_NAMES; cvc.main --scst_reward); None or cider alone at 1: CIDEr-D as ever
         self.scst_reward_weights = getattr(opts, "scst_reward_weights", None)
-        self.reward_history = {}      # epoch -> the mean reward of every display interval
+        # rollouts without replacement (cvc.main --scst_wor): a stochastic beam of scst_samples + 1 slots, importance-weighted
+        self.scst_wor = bool(getattr(opts, "scst_wor", False))
+        if self.scst_wor:
+            self._scst_wor_samples()
+        self.reward_history = {}     # epoch -> the mean reward of every display interval
         # ---- scheduled sampling (train_step_prepared while model.ss_prob > 0): rollout temperature, seed of step k = ss_seed + k
         self.ss_temperature = float(getattr(opts, "ss_temperature", 1.0))
         self.ss_seed = int(getattr(opts, "ss_seed", 1))
@@ -301,6 +305,17 @@ class Trainer:
     def scst_step(self, batch):
         return self.scst_step_prepared(self._prepare(batch, True))
 
+    def _scst_wor_samples(self) -> int:
+        """opts.scst_samples for a step without replacement, refused outside [2, 7]"""
+        S = int(getattr(self.opts, "scst_samples", 5))
+        if S < 2:
+            raise RuntimeError(f"Trainer: scst_wor needs scst_samples >= 2, got {S} (the baseline of a without-replacement rollout is built "
+                               f"from the clip's other rollouts: one rollout's own baseline cancels it)")
+        if S > 7:
+            raise RuntimeError(f"Trainer: scst_wor takes scst_samples <= 7, got {S} (the rollouts are a stochastic beam of scst_samples + 1 "
+                               f"slots, and a beam holds at most 8)")
+        return S
+
     def scst_step_prepared(self, b):
         """One self-critical optimisation step (SCST, Rennie et al. 2017) on a prepared batch: S = opts.scst_samples captions per clip
         sampled from the model at opts.scst_temperature (the cached decode binding, DecodeEngine's sampling mode), scored against the
@@ -312,6 +327,12 @@ class Trainer:
         autograd and in eval mode; the decoder's parameters (decoder_core, embed, logit) are what the loss reaches.  Dropout is off in
         the gradient pass unless opts.scst_dropout.  No host read-back between the rollout and optimizer.step().
         The sampler leaves UNK out while log p is taken over the full vocabulary, as in the sampling engine.  Runs eagerly.
+        opts.scst_wor (2 <= S <= 7): the rollouts are drawn WITHOUT replacement -- model._sample(beam_size=S + 1, stochastic_beam=True,
+        stochastic_tau=scst_temperature), slots 0 .. S-1 -- so no two rollouts of a clip are the same sentence; rewards are taken on
+        those B * S rows unchanged and model.scst_loss(wor=) weights them (cvc_scst_weights_wor: importance weights, per-row
+        baseline; DESIGN section 7, "Self-critical training without replacement").  last_scst then also holds logq, G [B, S + 1],
+        state, wgt [B * S], expected_reward [B] and distinct (the share of live rollouts: 1 whenever a clip has S captions to give);
+        logprob is None, and the third scalar is the mean of expected_reward.
         -> (loss, mean reward, mean baseline, mean |advantage|) as device scalars; the step's samples, rewards and advantages stay
         in self.last_scst (with a mix also reward_parts: the metrics that were weighted, per row)."""
         from . import metrics
@@ -320,6 +341,9 @@ class Trainer:
         mix = None if metrics.is_cider_only(self.scst_reward_weights) else self.scst_reward_weights
         parts = None
         S, tau = int(getattr(o, "scst_samples", 5)), float(getattr(o, "scst_temperature", 1.0))
+        wor = None
+        if self.scst_wor:
+            S = self._scst_wor_samples()
         seed = int(getattr(o, "scst_seed", 1)) + self._scst_steps          # a sampling engine is seeded when it is built: once per step
         cider = self.cider()
         T = model.seq_length
@@ -333,7 +357,16 @@ class Trainer:
                                          b["sample_idx"], b["pnt_mask"])
                 args = (b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"], b["gt_bboxs"], b["ppls_feat"],
                         b["mask_frms"], b["sample_idx"], b["pnt_mask"])
-                seq, _, logprob = model._sample(*args, sample_max=0, temperature=tau, sample_n=S, seed=seed, encoded=enc, **plain)
+                if self.scst_wor:
+                    # a stochastic beam of S + 1 slots: slots 0 .. S-1 are the clip's rollouts (pairwise distinct, in draw order), slot
+                    # S gives the threshold key.  The model's five constraints compose, as they do in the stochastic engine
+                    model._sample(*args, beam_size=S + 1, sample_max=1, stochastic_beam=True, stochastic_tau=tau, seed=seed, encoded=enc,
+                                  consensus=False, beam_groups=1, diversity_lambda=0.0, length_penalty=0.0)
+                    draws = model.last_stochastic
+                    seq, logprob = draws["seq"][:, :S].reshape(-1, T), None
+                    wor = dict(logq=draws["logq"], G=draws["G"], state=draws["state"], normalize=True)
+                else:
+                    seq, _, logprob = model._sample(*args, sample_max=0, temperature=tau, sample_n=S, seed=seed, encoded=enc, **plain)
                 seq = seq.contiguous()
                 refs = b["gt_seqs"][:, :, :T].contiguous()
                 nref = b["num"][:, 0].to(torch.int32)
@@ -347,7 +380,7 @@ class Trainer:
                     base = cider.score(greedy, refs, nref) if mix is None else metrics.reward_mix(mix, cider, greedy, refs, nref)[0]
             if bool(getattr(o, "scst_dropout", False)):
                 model.train()
-            loss, adv = model.scst_loss(enc, seq, reward, base, S)
+            loss, adv = model.scst_loss(enc, seq, reward, base, S) if wor is None else model.scst_loss(enc, seq, reward, None, S, wor=wor)
         finally:
             model.train(was_training)
         self._backward_and_update(loss)
@@ -356,6 +389,12 @@ class Trainer:
         self.last_scst = dict(seq=seq, logprob=logprob, reward=reward, base=base, greedy=greedy, adv=adv, seed=seed)
         if mix is not None:
             self.last_scst["reward_parts"] = parts
+        if wor is not None:
+            est = model.last_wor["est"]
+            self.last_scst.update(logq=wor["logq"], G=wor["G"], state=wor["state"], wgt=model.last_wor["wgt"], expected_reward=est,
+                                  distinct=torch.isfinite(wor["G"][:, :S]).to(torch.float32).mean())
+            # the mean baseline: a row's baseline B_i / W_i estimates the clip's expected reward, which est is
+            return loss.detach(), reward.mean(), est.mean(), adv.abs().mean()
         return loss.detach(), reward.mean(), (reward - adv).mean(), adv.abs().mean()
 
     # ------------------------------------------------------------------ HIP-graph training step

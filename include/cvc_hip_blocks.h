@@ -556,6 +556,49 @@ int cvc_cider_d(const int64_t* cand, const int64_t* refs, const int32_t* nref, i
 int cvc_scst_weights(const float* reward, const float* base, int rows, int per_clip, const int64_t* cand, int T, int t_major,
                      float* adv, float* w, cvc_stream_t stream);
 
+/* ---- self-critical training on captions sampled WITHOUT replacement: importance weights, a per-row baseline and the per-token loss
+ * weights, one launch (csrc/scst_wor.hip; cvc.hip.scst_weights_wor, model.scst_loss(wor=), Trainer.scst_step with opts.scst_wor).
+ * The estimator of Kool, van Hoof and Welling 2019 ("Stochastic Beams and Where to Find Them" section 4; "Buy 4 REINFORCE Samples,
+ * Get a Baseline for Free!") on the output of cvc_beam_select_stoch_parts run with beam = S + 1: slots 0 .. S-1 of a clip are its S
+ * rollouts, slot S gives only its key, the threshold.  THIS COMMENT IS THE DEFINITION; the kernel and tests/wor_ref.py restate it.
+ *   inputs      per clip b: reward f[b * S + i], i < S;  logq[b * (S + 1) + j] and G[b * (S + 1) + j], j <= S (a per-clip stride of
+ *               S + 1);  state = the engine's generator words {seed_lo, seed_hi, call, 0} in device memory.
+ *   derived     live_j = isfinite(G_j);  phi_i = logq_i;  kt = G_S;
+ *               h = cvc_drop_hash(seed_lo, seed_hi, call, CVC_WOR_SITE, b);  u = ((h >> 9) + 0.5) * 2^-23;  a = -log u.
+ *   root key    The engine starts a clip at G_root = 0, which conditions the largest perturbed log-prob on being 0.  The ORDER of the
+ *               draws is unaffected, the GAPS between the keys are: the inclusion probability below assumes an unconditioned
+ *               threshold.  With E = exp(-G), conditioning the minimum on another value shifts every E alike, so a ~ Exp(1) per clip
+ *               stands for exp(-G_root), G_root ~ Gumbel(0), and only the threshold is re-conditioned: exp(-kappa) = a - 1 + exp(-kt).
+ *   threshold   lambda = -kappa = -kt + log1p((a - 1) * exp(kt));  slot S not live: lambda = +inf (the beam holds every caption that
+ *               exists);  kt = 0 gives lambda = log a.
+ *   weight      d_i = phi_i + lambda;  x_i = exp(d_i);  log q_i = log(-expm1(-x_i)) -- for x_i < 1 taken as
+ *               d_i + log(-expm1(-x_i) / x_i) with the ratio read as 1 when x_i underflows to 0, and 0 when x_i = inf;
+ *               l_i = phi_i - log q_i for a live row, -inf for a dead one.  Everything stays in the log domain until a ratio is
+ *               formed: exp(logq) is 0 in fp32 below -88 (ordinary early in training), the normalised weights are not.
+ *   own sums    row i's sums carry row i with weight p_i = exp(phi_i) instead of w_i = exp(l_i):
+ *               W_i = exp(phi_i) + sum_{j != i} exp(l_j);  B_i = exp(phi_i) f_i + sum_{j != i} exp(l_j) f_j;  W = sum_j exp(l_j);
+ *               over live j < S in ascending j, every sum shifted by its largest exponent.
+ *   normalize != 0 (what training uses; consistent, biased):
+ *               wgt_i = exp(l_i) / W;  adv_i = n_live * wgt_i * (f_i - B_i / W_i);  est_b = sum_j wgt_j f_j;  n_live = the number of
+ *               live rollouts (the loss stays on the scale of cvc_scst_weights': when every p is tiny against exp(kappa) all w_j are
+ *               equal and adv_i is f_i minus the mean of the others, its leave-one-out advantage).
+ *   normalize == 0 (exact, unbiased):
+ *               wgt_i = exp(l_i);  adv_i = wgt_i * (f_i - B_i);  est_b = sum_j wgt_j f_j.
+ *   dead rows   wgt = adv = 0;  a clip without a live rollout: est = 0.
+ *   tokens      w[r, t] = adv_r over the steps up to and including the first 0 of cand [rows, T], else 0; row-major, or t-major with
+ *               t_major != 0 (as cvc_scst_weights).
+ *   arithmetic  accurate logf / expf / log1pf / expm1f, fp32, no contraction, fixed summation order: a row's outputs depend on its
+ *               clip's inputs only and are bit-reproducible.  One thread per row, no atomics, no workspace.  Launch only (the state
+ *               is read on the device): capturable in a HIP graph; a replay after cvc_sample_advance uses the new `call`.
+ * CVC_WOR_SITE is disjoint from CVC_SAMPLE_SITE + t, CVC_MIX_SITE + t, CVC_SBS_SITE + t (t <= 64) and the dropout sites.
+ * rows = B * S, per_clip = S;  outputs adv [rows], wgt [rows], est [B], w [rows * T].
+ * A NULL pointer, per_clip < 2 (one rollout's own baseline cancels it) or > 7, rows < 1, rows % per_clip != 0, T < 1: CVC_E_BADARG,
+ * before any launch; nothing is written. */
+#define CVC_WOR_SITE 0x57000000u
+int cvc_scst_weights_wor(const float* reward, const float* logq, const float* G, const uint32_t* state, int rows, int per_clip,
+                         const int64_t* cand, int T, int t_major, int normalize, float* adv, float* wgt, float* est, float* w,
+                         cvc_stream_t stream);
+
 /* ---- token-overlap caption metrics: BLEU statistics, sentence BLEU-1..4 and ROUGE-L, one launch (csrc/overlap.hip; cvc.metrics).
  * cand / refs / nref / per_clip / Rmax as cvc_cider_d, on the same n-gram keys -- but a caption's words here are the ids BEFORE its
  * first 0 (the end mark is no word, what stands behind it is ignored; all T ids without a 0; L = 0 is possible).
