@@ -374,11 +374,77 @@ __global__ __launch_bounds__(WG) void nll_fwd_kernel(const float* logp, const in
 //     row_loss = w (lse - (1 - eps) x[t] - (eps / V) sum_v x[v]),   row_nll = w (lse - x[t]) (the unsmoothed value, nullable)
 // -- the row's sum is taken in the pass that looks for the maximum, one more fixed-order block reduction.  eps == 0 gives the
 // bits of the LS = false form.
-template <bool LS>
+// ENT (with LS): the entropy regulariser beta (finite, any sign) with the entropy weight mrow (the 0 / 1 loss mask):
+//     H = sum_v p[v] (lse - z[v]),  p[v] = exp(z[v] - lse)      (every term >= 0; a column at -inf adds exactly 0)
+//     row_loss -= beta mrow H,   pre[v] += beta mrow p[v] (z[v] - lse + H)  (exactly 0 at -inf),   row_ent = mrow H
+// -- H is one more pass over the row once lse is known, each thread adding its columns in ascending order, and one more
+// fixed-order block reduction.  beta == 0 takes the LS expressions in a uniform branch (the same bits) and still writes row_ent.
+// The expressions below are shared by the fused and the two-step kernels and are kept from contraction, so that the two forms
+// round alike: on equal logits they agree bit for bit.
+// The ROW VALUES of this form are formed in fp64: the fp32 values exp(z - max) are added in fp64 (sd), lse = max + log(sd),
+// H = sum_v e[v] (lse - z[v]) / sd, and the row's loss, NLL and entropy are fp64 expressions of these.  Each is written as its
+// fp32 value plus an fp32 remainder (row_lo), so that the sums over the rows lose nothing to the rows' rounding: a sum is then
+// the fp64 value rounded once.  (What fp32 costs here: a row's lse carries 5e-7 and a sum of 33 rows of 20 some 1e-5; the price
+// is two more expf passes over the registers and fp64 adds.)  pre and d_logits stay fp32, with the fp32 lse and H rounded to fp32.
+// (a column at -inf: e = 0 and lse - z = +inf, whose product would be a NaN -- the difference is clamped to a finite value, so
+// the term is an exact 0 without a compare per column)
+__device__ __forceinline__ double block_sum_wide(double v, double* dred) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) dred[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (dred[0] + dred[1]) + (dred[2] + dred[3]);
+}
+__device__ __forceinline__ double ent_acc_wide(double h, float e, float z, double lse) {
+#pragma clang fp contract(off)
+    return h + (double)e * fmin(lse - (double)z, 1e300);
+}
+struct EntRow { double loss, nll, ent; };
+__device__ __forceinline__ EntRow ent_rows_wide(float wm, float mm, float beta, double lse, float xt, float eps, float zs, int V, double H) {
+#pragma clang fp contract(off)
+    EntRow r;
+    r.nll = wm != 0.f ? (double)wm * (lse - (double)xt) : 0.0;
+    double base = r.nll;
+    if (wm != 0.f && eps != 0.f) base = (double)wm * (lse - (double)(1.f - eps) * (double)xt - (double)(eps / (float)V) * (double)zs);
+    const double coef = (double)beta * (double)mm;
+    r.loss = coef != 0.0 ? base - coef * H : base;
+    r.ent = mm != 0.f ? (double)mm * H : 0.0;
+    return r;
+}
+// v as an fp32 value and the fp32 remainder behind it (0 behind a value that is not finite)
+__device__ __forceinline__ void put_wide(float* hi, float* lo, double v) {
+    const float h = (float)v;
+    *hi = h;
+    *lo = h - h == 0.f ? (float)(v - (double)h) : 0.f;
+}
+__device__ __forceinline__ float ent_row_loss(float wm, float coef, float lse, float xt, float eps, float zs, int V, float H) {
+#pragma clang fp contract(off)
+    float base = 0.f;
+    if (wm != 0.f) base = eps == 0.f ? wm * (lse - xt) : wm * (lse - (1.f - eps) * xt - (eps / (float)V) * zs);
+    return coef != 0.f ? base - coef * H : base;
+}
+// gw: the NLL weight (times the upstream scalar in the two-step backward), coef: beta x mrow (times the same scalar), hit: the
+// target's share at this column (ent_hit at the target, else 0), all: every column's share (ent_all)
+__device__ __forceinline__ float ent_hit(float eps) { return eps == 0.f ? 1.f : 1.f - eps; }
+__device__ __forceinline__ float ent_all(float eps, int V) { return eps == 0.f ? 0.f : eps / (float)V; }
+__device__ __forceinline__ float ent_pre(float gw, float coef, float z, float lse, float hit, float all, float H) {
+#pragma clang fp contract(off)
+    const float p = expf(z - lse);
+    const float base = gw != 0.f ? gw * (p - hit - all) : 0.f;
+    const float both = base + coef * p * (fmaxf(z - lse, -3.402823466e+38f) + H);       // (z = -inf: p = 0, an exact 0)
+    return coef == 0.f ? base : both;
+}
+
+template <bool LS, bool ENT = false>
 __global__ __launch_bounds__(WG) void vocab_nll_fwd_kernel(const float* logits, const int64_t* target, const float* w, int V,
-                                                           float* lse_out, int64_t* argmax, float* row_loss, float eps, float* row_nll) {
+                                                           float* lse_out, int64_t* argmax, float* row_loss, float eps, float* row_nll,
+                                                           float beta = 0.f, const float* mrow = nullptr, float* row_ent = nullptr,
+                                                           float* row_lo = nullptr) {
+    static_assert(LS || !ENT, "the entropy form is built on the label-smoothing form");
     __shared__ float red[4];
     __shared__ int ired[4];
+    __shared__ double dred[4];
     const int row = blockIdx.x;
     const float* x = logits + (size_t)row * V;
     float m = -INFINITY;
@@ -401,6 +467,17 @@ __global__ __launch_bounds__(WG) void vocab_nll_fwd_kernel(const float* logits, 
     for (int v = threadIdx.x; v < V; v += WG) s += expf(x[v] - bm);
     s = block_sum(s, red);
     if (LS) zs = block_sum(zs, red);
+    double lse_w = 0.0, H_w = 0.0;
+    if (ENT) {
+        double sd = 0.0;
+        for (int v = threadIdx.x; v < V; v += WG) sd += (double)expf(x[v] - bm);
+        sd = block_sum_wide(sd, dred);
+        lse_w = (double)bm + log(sd);
+        double hd = 0.0;
+        for (int v = threadIdx.x; v < V; v += WG) hd = ent_acc_wide(hd, expf(x[v] - bm), x[v], lse_w);
+        H_w = block_sum_wide(hd, dred) / sd;
+    }
+    const float H = (float)H_w;
     if (threadIdx.x == 0) {
         const float lse = bm + logf(s);
         lse_out[row] = lse;
@@ -408,7 +485,21 @@ __global__ __launch_bounds__(WG) void vocab_nll_fwd_kernel(const float* logits, 
         const float wm = w[row];
         const float xt = wm != 0.f ? x[target[row]] : 0.f;
         const float nll = wm != 0.f ? wm * (lse - xt) : 0.f;
-        if (LS) {
+        if (ENT) {
+            // (beta == 0: coef is 0 and the helper returns the label-smoothing value -- formed without contraction, as the compiler
+            // forms it in the LS instantiation: a packed multiply and two subtractions -- so the monitor mode has that form's bits)
+            const float mm = mrow[row];
+            const int M = gridDim.x;
+            const EntRow r = ent_rows_wide(wm, mm, beta, lse_w, xt, eps, zs, V, H_w);
+            if (beta != 0.f) {
+                put_wide(row_loss + row, row_lo + row, r.loss);
+                if (row_nll != nullptr) put_wide(row_nll + row, row_lo + 2 * M + row, r.nll);
+            } else {
+                row_loss[row] = ent_row_loss(wm, 0.f, lse, xt, eps, zs, V, H);
+                if (row_nll != nullptr) row_nll[row] = nll;
+            }
+            put_wide(row_ent + row, row_lo + M + row, r.ent);
+        } else if (LS) {
             row_loss[row] = eps == 0.f ? nll : wm != 0.f ? wm * (lse - (1.f - eps) * xt - (eps / (float)V) * zs) : 0.f;
             if (row_nll != nullptr) row_nll[row] = nll;
         } else {
@@ -425,18 +516,50 @@ __global__ __launch_bounds__(WG) void row_sum_kernel(const float* row_loss, int 
     if (threadIdx.x == 0) loss_sum[0] = s;
 }
 
+// The sums of up to three row vectors in one launch (block b sums vector b, a null vector is skipped).  Bit b of `wide` clear: vector b
+// is summed as row_sum_kernel does, so with its bits (what beta == 0 owes the label-smoothing entries).  Set: the rows are added in
+// fp64 together with their fp32 remainders lo [3, M] (the row kernels' fp64 values: row + remainder), in the same fixed order, and
+// the sum is rounded to fp32 once.
+__global__ __launch_bounds__(WG) void row_sums_kernel(const float* r0, float* s0, const float* r1, float* s1, const float* r2, float* s2,
+                                                      int M, int wide, const float* lo) {
+    __shared__ float red[4];
+    __shared__ double dred[4];
+    const float* r = blockIdx.x == 0 ? r0 : blockIdx.x == 1 ? r1 : r2;
+    float* out = blockIdx.x == 0 ? s0 : blockIdx.x == 1 ? s1 : s2;
+    if (r == nullptr) return;
+    if ((wide >> blockIdx.x) & 1) {
+        double d = 0.0;
+        const float* l = lo + (size_t)blockIdx.x * M;
+        for (int m = threadIdx.x; m < M; m += WG) d += (double)r[m] + (double)l[m];
+        d = block_sum_wide(d, dred);
+        if (threadIdx.x == 0) out[0] = (float)d;
+        return;
+    }
+    float s = 0.f;
+    for (int m = threadIdx.x; m < M; m += WG) s += r[m];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
 // d_logits[m, v] = g[0] * w[m] * (softmax(logits[m])[v] - [v == target[m]])
 // LS: ... - (1 - eps) [v == target[m]] - eps / V), the gradient of the smoothed row loss (eps == 0: the bits of LS = false)
-template <bool LS>
+// ENT: ... + g[0] beta mrow[m] p (z - lse + H) with H = row_ent[m] / mrow[m] (the forward wrote row_ent = mrow H); beta == 0: the LS bits
+template <bool LS, bool ENT = false>
 __global__ __launch_bounds__(WG) void vocab_nll_bwd_kernel(const float* logits, const float* lse, const int64_t* target,
-                                                           const float* w, const float* g, int V, float* d_logits, float eps) {
+                                                           const float* w, const float* g, int V, float* d_logits, float eps,
+                                                           float beta = 0.f, const float* mrow = nullptr, const float* row_ent = nullptr) {
+    static_assert(LS || !ENT, "the entropy form is built on the label-smoothing form");
     const int m = blockIdx.y;
     const int v = blockIdx.x * WG + threadIdx.x;
     if (v >= V) return;
     const float gw = g[0] * w[m];
     const size_t o = (size_t)m * V + v;
     const bool hit = v == (int)target[m];
-    if (LS && eps != 0.f)
+    if (ENT && beta != 0.f) {
+        const float mm = mrow[m];
+        const float H = mm != 0.f ? row_ent[m] / mm : 0.f;
+        d_logits[o] = ent_pre(gw, (g[0] * beta) * mm, logits[o], lse[m], hit ? ent_hit(eps) : 0.f, ent_all(eps, V), H);
+    } else if (LS && eps != 0.f)
         d_logits[o] = gw == 0.f ? 0.f : gw * (expf(logits[o] - lse[m]) - (hit ? 1.f - eps : 0.f) - eps / (float)V);
     else
         d_logits[o] = gw == 0.f ? 0.f : gw * (expf(logits[o] - lse[m]) - (hit ? 1.f : 0.f));
@@ -454,13 +577,20 @@ __global__ __launch_bounds__(WG) void vocab_nll_bwd_kernel(const float* logits, 
 //     row_nll  = w (lse - x[t])  (the unsmoothed value, for logging; nullable)
 // -- every thread adds its columns in ascending order while they are in registers, one more fixed-order block reduction gives the
 // row's sum.  eps == 0 takes the LS = false expressions: the same bits.
+// ENT (with LS): the entropy regulariser of vocab_nll_fwd_kernel's comment -- once lse is known every thread adds p (lse - z) over its
+// register-resident columns in ascending order, one more fixed-order block reduction gives H, and the epilogue applies
+// ent_row_loss / ent_pre.  beta == 0 (the monitor mode) takes the LS expressions in a uniform branch and still writes row_ent.
 constexpr int NLL_CACHE = 32;
-template <bool LS>
+template <bool LS, bool ENT = false>
 __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
                                                             const int64_t* target, const float* w, int V, float* pre, int ld_pre,
-                                                            int64_t* argmax, float* row_loss, float eps, float* row_nll) {
+                                                            int64_t* argmax, float* row_loss, float eps, float* row_nll,
+                                                            float beta = 0.f, const float* mrow = nullptr, float* row_ent = nullptr,
+                                                            float* row_lo = nullptr) {
+    static_assert(LS || !ENT, "the entropy form is built on the label-smoothing form");
     __shared__ float red[4];
     __shared__ int ired[4];
+    __shared__ double dred[4];
     __shared__ float xt_s;
     const int row = blockIdx.x;
     const float* x = parts + (size_t)row * ld;
@@ -500,10 +630,42 @@ __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, 
     const float wm = w[row];
     const bool smooth = LS && eps != 0.f;
     if (LS) zs = block_sum(zs, red);
+    const bool ent = ENT && beta != 0.f;
+    const float mm = ENT ? mrow[row] : 0.f;
+    double lse_w = 0.0, H_w = 0.0;
+    if (ENT) {
+        // the two fp64 passes read the row's maximum through copies the compiler cannot see through: it then forms the exponentials
+        // again in each pass instead of keeping 32 of them live across the reductions (which costs a wave per SIMD)
+        float bm_a = bm, bm_b = bm;
+        asm volatile("" : "+v"(bm_a), "+v"(bm_b));
+        double sd = 0.0;
+#pragma unroll
+        for (int u = 0; u < NLL_CACHE; ++u) sd += (double)expf(vals[u] - bm_a);       // (a slot past V holds -inf: it adds nothing)
+        sd = block_sum_wide(sd, dred);
+        lse_w = (double)bm + log(sd);
+        double hd = 0.0;
+#pragma unroll
+        for (int u = 0; u < NLL_CACHE; ++u) hd = ent_acc_wide(hd, expf(vals[u] - bm_b), vals[u], lse_w);
+        H_w = block_sum_wide(hd, dred) / sd;
+    }
+    const float H = (float)H_w;
     if (threadIdx.x == 0) {
         if (argmax != nullptr) argmax[row] = best == 0x7fffffff ? 0 : best;
         const float nll = wm != 0.f ? wm * (lse - xt_s) : 0.f;
-        if (LS) {
+        if (ENT) {
+            // (beta == 0: the helper returns the label-smoothing value -- formed without contraction, as the compiler forms it in
+            // the LS instantiation: a packed multiply and two subtractions -- so the monitor mode has that form's bits)
+            const int M = gridDim.x;
+            const EntRow r = ent_rows_wide(wm, mm, beta, lse_w, xt_s, eps, zs, V, H_w);
+            if (beta != 0.f) {
+                put_wide(row_loss + row, row_lo + row, r.loss);
+                if (row_nll != nullptr) put_wide(row_nll + row, row_lo + 2 * M + row, r.nll);
+            } else {
+                row_loss[row] = ent_row_loss(wm, 0.f, lse, xt_s, eps, zs, V, H);
+                if (row_nll != nullptr) row_nll[row] = nll;
+            }
+            put_wide(row_ent + row, row_lo + M + row, r.ent);
+        } else if (LS) {
             row_loss[row] = !smooth ? nll : wm != 0.f ? wm * (lse - (1.f - eps) * xt_s - (eps / (float)V) * zs) : 0.f;
             if (row_nll != nullptr) row_nll[row] = nll;
         } else {
@@ -515,7 +677,9 @@ __global__ __launch_bounds__(WG) void vocab_head_nll_kernel(const float* parts, 
 #pragma unroll
     for (int u = 0; u < NLL_CACHE; ++u) {
         const int v = threadIdx.x + u * WG;
-        if (!smooth) {
+        if (ent) {
+            if (v < V) out[v] = ent_pre(wm, beta * mm, vals[u], lse, v == tgt ? ent_hit(eps) : 0.f, ent_all(eps, V), H);
+        } else if (!smooth) {
             if (v < V) out[v] = wm == 0.f ? 0.f : wm * (expf(vals[u] - lse) - (v == tgt ? 1.f : 0.f));
         } else {
             if (v < V) out[v] = wm == 0.f ? 0.f : wm * (expf(vals[u] - lse) - (v == tgt ? hit : 0.f) - all);
@@ -704,6 +868,49 @@ extern "C" int cvc_vocab_head_nll_ls_fwd(const float* parts, int nparts, long lo
                        w, V, pre, ld_pre, argmax, row_loss, eps, row_nll);
     hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_loss, M, loss_sum);
     if (row_nll) hipLaunchKernelGGL(row_sum_kernel, dim3(1), dim3(WG), 0, (hipStream_t)stream, row_nll, M, nll_sum);
+    return cvc_launch_status();
+}
+
+// The entropy regulariser's entries (include/cvc_hip_blocks.h): the label-smoothing entries with beta, the entropy weight m and
+// row_ent / ent_sum; the sums of the row vectors are one launch (row_sums_kernel: ent_sum always, loss_sum and nll_sum with beta != 0
+// are accumulated in fp64; with beta == 0 those two have the label-smoothing entries' bits).  beta finite (a NaN or an inf fails the
+// comparison)
+static bool beta_ok(float beta) { return beta - beta == 0.f; }
+
+extern "C" int cvc_vocab_nll_ent_fwd(const float* logits, const int64_t* target, const float* w, const float* m, int M, int V, float eps,
+                                     float beta, float* lse, int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll,
+                                     float* nll_sum, float* row_ent, float* ent_sum, float* row_lo, cvc_stream_t stream) {
+    if (!logits || !target || !w || !m || !lse || !row_loss || !loss_sum || !row_ent || !ent_sum || !row_lo || M < 1 || V < 1 || !smoothing_ok(eps) ||
+        !beta_ok(beta) || !row_nll != !nll_sum)
+        return CVC_E_BADARG;
+    hipLaunchKernelGGL((vocab_nll_fwd_kernel<true, true>), dim3(M), dim3(WG), 0, (hipStream_t)stream, logits, target, w, V, lse, argmax,
+                       row_loss, eps, row_nll, beta, m, row_ent, row_lo);
+    hipLaunchKernelGGL(row_sums_kernel, dim3(3), dim3(WG), 0, (hipStream_t)stream, (const float*)row_loss, loss_sum, (const float*)row_ent,
+                       ent_sum, (const float*)row_nll, nll_sum, M, beta != 0.f ? 7 : 2, (const float*)row_lo);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_vocab_head_nll_ent_fwd(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
+                                          const int64_t* target, const float* w, const float* m, int M, int V, float eps, float beta,
+                                          float* pre, int ld_pre, int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll,
+                                          float* nll_sum, float* row_ent, float* ent_sum, float* row_lo, cvc_stream_t stream) {
+    if (!parts || nparts < 1 || !target || !w || !m || !pre || !row_loss || !loss_sum || !row_ent || !ent_sum || !row_lo || M < 1 || V < 1 ||
+        V > WG * NLL_CACHE || ld < V || ld_pre < V || !smoothing_ok(eps) || !beta_ok(beta) || !row_nll != !nll_sum)
+        return CVC_E_BADARG;
+    hipLaunchKernelGGL((vocab_head_nll_kernel<true, true>), dim3(M), dim3(WG), 0, (hipStream_t)stream, parts, nparts, part_stride, ld, bias,
+                       target, w, V, pre, ld_pre, argmax, row_loss, eps, row_nll, beta, m, row_ent, row_lo);
+    hipLaunchKernelGGL(row_sums_kernel, dim3(3), dim3(WG), 0, (hipStream_t)stream, (const float*)row_loss, loss_sum, (const float*)row_ent,
+                       ent_sum, (const float*)row_nll, nll_sum, M, beta != 0.f ? 7 : 2, (const float*)row_lo);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_vocab_nll_ent_bwd(const float* logits, const float* lse, const int64_t* target, const float* w, const float* m,
+                                     const float* row_ent, const float* g, int M, int V, float eps, float beta, float* d_logits,
+                                     cvc_stream_t stream) {
+    if (!logits || !lse || !target || !w || !m || !row_ent || !g || !d_logits || M < 1 || V < 1 || !smoothing_ok(eps) || !beta_ok(beta))
+        return CVC_E_BADARG;
+    hipLaunchKernelGGL((vocab_nll_bwd_kernel<true, true>), dim3((V + WG - 1) / WG, M), dim3(WG), 0, (hipStream_t)stream, logits, lse,
+                       target, w, g, V, d_logits, eps, beta, m, row_ent);
     return cvc_launch_status();
 }
 

@@ -243,14 +243,86 @@ class _VocabHeadNLL(torch.autograd.Function):
         return d_x, d_w, d_b, None, None, None, None
 
 
+class _VocabHeadNLLEnt(torch.autograd.Function):
+    """_VocabHeadNLL with the entropy term -beta sum_r m[r] H[r] (cvc_vocab_head_nll_ent_fwd): pre is the whole loss's gradient, so
+    the backward is _VocabHeadNLL's; two more results without a graph, the unsmoothed NLL sum and the entropy sum."""
+
+    @staticmethod
+    def compute(x, weight, bias, target, w, m, eps, beta):
+        """-> (loss [1], argmax [M], pre [M, V], unsmoothed NLL sum [1], eps, entropy sum [1], beta)"""
+        parts = hip.tile_mm(_rows(x), hip.weight_operand(weight), parts_only=True)
+        loss, amax, pre, nll, ent = hip.vocab_head_nll_ent_fwd(parts, bias, target.contiguous(), w.contiguous(), m.contiguous(), eps, beta)
+        return loss, amax, pre, nll, eps, ent, beta
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, target, w, m, done, eps, beta):
+        x = _rows(x)
+        res = done if done is not None else _VocabHeadNLLEnt.compute(x, weight, bias, target, w, m, eps, beta)
+        loss, amax, pre, nll, _eps, ent, _beta = res
+        ctx.save_for_backward(weight, bias, x, pre)
+        ctx.has_bias = bias is not None
+        ctx.key = ("linear", weight.data_ptr())
+        if weight.requires_grad:
+            _BATCHER.note_use(ctx.key)
+        ctx.mark_non_differentiable(amax, nll, ent)
+        return loss, amax, nll, ent
+
+    @staticmethod
+    def backward(ctx, g, _g_amax, _g_nll, _g_ent):
+        weight, bias, x, pre = ctx.saved_tensors
+        dy = hip.scale_by_scalar(pre, g.contiguous().reshape(1))
+        ni = ctx.needs_input_grad
+        d_w, d_b, d_x = _linear_backward(ctx, weight, bias, [x], dy, (ni[1], ni[2], ni[0]))
+        return d_x, d_w, d_b, None, None, None, None, None, None
+
+
+def _entropy_args(what, entropy_beta, entropy_weight, return_entropy, rows):
+    """-> None (today's launches: no coefficient and no entropy asked for) or (beta, m [rows]); beta = 0 reports the entropy and
+    changes nothing else"""
+    if entropy_beta is None and not return_entropy:
+        return None
+    beta = hip.check_entropy_beta(0.0 if entropy_beta is None else entropy_beta)
+    if entropy_weight is None:
+        raise ValueError(f"{what}: entropy_beta / return_entropy need entropy_weight, the 0 / 1 loss mask per row")
+    m = entropy_weight.reshape(-1)
+    if m.numel() != rows:
+        raise ValueError(f"{what}: entropy_weight has {m.numel()} elements for {rows} rows")
+    return beta, m if m.dtype == torch.float32 else m.to(torch.float32)
+
+
+def _done_beta(done):
+    """the entropy coefficient a `done` was made with (None: made without the entropy form)"""
+    return done[6] if done is not None and len(done) > 5 else None
+
+
+def _refuse_done(done, eps, beta):
+    made = (done[4] if len(done) > 3 else 0.0, _done_beta(done))
+    if made[0] != eps:
+        raise RuntimeError(f"vocab_head_nll: `done` was computed with label_smoothing = {made[0]}, this call asks for {eps}")
+    if made[1] != beta:
+        raise RuntimeError(f"vocab_head_nll: `done` was computed with entropy_beta = {made[1]}, this call asks for {beta}")
+
+
 def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, done=None, label_smoothing: float = 0.0,
-                   return_nll: bool = False):
+                   return_nll: bool = False, entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None,
+                   return_entropy: bool = False):
     """-> (sum_m w[m] * -log_softmax(x W^T + b)[m, target[m]] as a [1] tensor, argmax over V per row [M] int64); x [M, K]
     done: vocab_head_nll_compute()'s result for the same x (and the same label_smoothing: another one is refused)
     label_smoothing = eps in [0, 1): the loss of the target distribution (1 - eps) onehot + eps / V, what
     torch.nn.functional.cross_entropy(label_smoothing=eps) computes; 0 is the one-hot criterion on its own kernel, no other launch.
-    return_nll: a third result, the UNSMOOTHED sum as a [1] tensor without a graph (eps = 0: the loss, detached)"""
+    return_nll: a third result, the UNSMOOTHED sum as a [1] tensor without a graph (eps = 0: the loss, detached)
+    entropy_beta = beta (finite, any sign), entropy_weight = m [M] (the 0 / 1 loss mask): the loss gains -beta sum_m m[m] H[m] with
+    H the entropy of the row's softmax (the model's full-vocabulary distribution at temperature 1) -- an entropy bonus beside an
+    advantage-weighted w, a confidence penalty beside the mask.  None: today's launches and nothing else; 0: the entropy is
+    computed (return_entropy) and loss, gradient and NLL keep their bits.
+    return_entropy: a last result, sum_m m[m] H[m] as a [1] tensor without a graph"""
     eps = hip.check_label_smoothing(label_smoothing)
+    ent = _entropy_args("vocab_head_nll", entropy_beta, entropy_weight, return_entropy, target.numel())
+    if done is not None and (ent is not None or _done_beta(done) is not None):
+        _refuse_done(done, eps, None if ent is None else ent[0])
+    if ent is not None:
+        loss, amax, nll, h = _VocabHeadNLLEnt.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), ent[1], done, eps, ent[0])
+        return (loss, amax) + ((nll,) if return_nll else ()) + ((h,) if return_entropy else ())
     if eps == 0.0:
         loss, amax = _VocabHeadNLL.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), done, 0.0)
         return (loss, amax, loss.detach()) if return_nll else (loss, amax)
@@ -258,11 +330,16 @@ def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Te
     return (loss, amax, nll) if return_nll else (loss, amax)
 
 
-def vocab_head_nll_compute(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, label_smoothing: float = 0.0):
+def vocab_head_nll_compute(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, label_smoothing: float = 0.0,
+                           entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False):
     """the arithmetic of vocab_head_nll without its graph node (-> an opaque `done` for vocab_head_nll; done[1] is the argmax).
-    `done` carries label_smoothing: vocab_head_nll refuses one computed with another value"""
+    `done` carries label_smoothing and entropy_beta: vocab_head_nll refuses one computed with another value of either"""
     eps = hip.check_label_smoothing(label_smoothing)
+    ent = _entropy_args("vocab_head_nll_compute", entropy_beta, entropy_weight, return_entropy, target.numel())
     with torch.no_grad():
+        if ent is not None:
+            return _VocabHeadNLLEnt.compute(x.detach(), weight.detach(), None if bias is None else bias.detach(), target.reshape(-1),
+                                            w.reshape(-1), ent[1], eps, ent[0])
         return _VocabHeadNLL.compute(x.detach(), weight.detach(), None if bias is None else bias.detach(), target.reshape(-1), w.reshape(-1),
                                      eps)
 
@@ -746,10 +823,35 @@ class _VocabNLL(torch.autograd.Function):
         return hip.vocab_nll_ls_bwd(logits, lse, target, w, g.contiguous().reshape(1), ctx.eps), None, None, None
 
 
-def vocab_nll(logits: Tensor, target: Tensor, w: Tensor, label_smoothing: float = 0.0, return_nll: bool = False):
+class _VocabNLLEnt(torch.autograd.Function):
+    """_VocabNLL with the entropy term -beta sum_r m[r] H[r] (cvc_vocab_nll_ent_fwd / _bwd): the backward reads the forward's per-row
+    entropies; two more results without a graph, the unsmoothed NLL sum and the entropy sum."""
+
+    @staticmethod
+    def forward(ctx, logits, target, w, m, eps, beta):
+        logits, target, w, m = logits.contiguous(), target.contiguous(), w.contiguous(), m.contiguous()
+        ctx.eps, ctx.beta = eps, beta
+        loss, lse, amax, nll, ent, row_ent = hip.vocab_nll_ent_fwd(logits, target, w, m, eps, beta)
+        ctx.save_for_backward(logits, lse, target, w, m, row_ent)
+        ctx.mark_non_differentiable(amax, nll, ent)
+        return loss, amax, nll, ent
+
+    @staticmethod
+    def backward(ctx, g, _g_amax, _g_nll, _g_ent):
+        logits, lse, target, w, m, row_ent = ctx.saved_tensors
+        return (hip.vocab_nll_ent_bwd(logits, lse, target, w, m, row_ent, g.contiguous().reshape(1), ctx.eps, ctx.beta), None, None, None,
+                None, None)
+
+
+def vocab_nll(logits: Tensor, target: Tensor, w: Tensor, label_smoothing: float = 0.0, return_nll: bool = False,
+              entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False):
     """-> (sum_m w[m] * -log_softmax(logits)[m, target[m]]  as a [1] tensor,  argmax over V per row [M] int64).
-    label_smoothing, return_nll: as vocab_head_nll"""
+    label_smoothing, return_nll, entropy_beta, entropy_weight, return_entropy: as vocab_head_nll"""
     eps = hip.check_label_smoothing(label_smoothing)
+    ent = _entropy_args("vocab_nll", entropy_beta, entropy_weight, return_entropy, target.numel())
+    if ent is not None:
+        loss, amax, nll, h = _VocabNLLEnt.apply(logits, target.reshape(-1), w.reshape(-1), ent[1], eps, ent[0])
+        return (loss, amax) + ((nll,) if return_nll else ()) + ((h,) if return_entropy else ())
     if eps == 0.0:
         loss, amax = _VocabNLL.apply(logits, target.reshape(-1), w.reshape(-1), 0.0)
         return (loss, amax, loss.detach()) if return_nll else (loss, amax)

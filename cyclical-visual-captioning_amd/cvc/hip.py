@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -283,6 +284,10 @@ SIGNATURES = {
     "cvc_vocab_head_nll_ls_fwd": [_P, _I, _LL, _I, _P, _P, _P, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P],
     "cvc_vocab_nll_ls_fwd": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
     "cvc_vocab_nll_ls_bwd": [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
+    # entropy regulariser in the vocabulary criterion: the same three forms with beta, the entropy weight and row_ent / ent_sum
+    "cvc_vocab_head_nll_ent_fwd": [_P, _I, _LL, _I, _P, _P, _P, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_ent_fwd": [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_ent_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -328,7 +333,8 @@ BLOCKS = {
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
-    "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd"}
+    "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
+    "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1048,6 +1054,69 @@ def vocab_nll_ls_bwd(logits, lse, target, w, g, eps: float):
     d = torch.empty_like(logits)
     _check(lib().cvc_vocab_nll_ls_bwd(_dev(logits), _dev(lse), _dev(target, torch.int64), _dev(w), _dev(g), M, V, eps, _dev(d),
                                       _stream()), "cvc_vocab_nll_ls_bwd")
+    return d
+
+
+def check_entropy_beta(beta, what="entropy_beta") -> float:
+    """beta as a finite float -- the coefficient of the entropy term -beta m H in the criterion (beta > 0 rewards entropy; 0 only
+    reports it) -- or ValueError (before any tensor is touched or kernel launched)"""
+    try:
+        b = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a finite number, got {beta!r}") from None
+    if not math.isfinite(b):
+        raise ValueError(f"{what} must be finite, got {beta!r}")
+    return b
+
+
+def _check_rows(what, M, **rows):
+    for name, t in rows.items():
+        if t.numel() != M:
+            raise ValueError(f"{what}: {name} has {t.numel()} elements for {M} rows")
+
+
+def vocab_nll_ent_fwd(logits, target, w, m, eps: float, beta: float, want_argmax=True):
+    """vocab_nll_ls_fwd with the entropy term -beta m H -> loss_sum [1], lse [M], argmax [M] int64 (or None), nll_sum [1]
+    (unsmoothed, without the entropy term), ent_sum [1] (sum_r m H), row_ent [M] (the backward's input)"""
+    eps, beta = check_label_smoothing(eps), check_entropy_beta(beta)
+    M, V = logits.shape
+    _check_rows("vocab_nll_ent_fwd", M, target=target, w=w, m=m)
+    dev = logits.device
+    lse = torch.empty(M, device=dev, dtype=torch.float32)
+    rows = torch.empty(6, M, device=dev, dtype=torch.float32)          # (loss, NLL, entropy; then the rows' fp32 remainders)
+    sums = torch.empty(3, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64) if want_argmax else None
+    _check(lib().cvc_vocab_nll_ent_fwd(_dev(logits), _dev(target, torch.int64), _dev(w), _dev(m), M, V, eps, beta, _dev(lse),
+                                       _dev(amax, torch.int64), _dev(rows), _dev(sums), rows[1].data_ptr(), sums[1:].data_ptr(),
+                                       rows[2].data_ptr(), sums[2:].data_ptr(), rows[3].data_ptr(), _stream()), "cvc_vocab_nll_ent_fwd")
+    return sums[0:1], lse, amax, sums[1:2], sums[2:3], rows[2]
+
+
+def vocab_head_nll_ent_fwd(parts, bias, target, w, m, eps: float, beta: float):
+    """vocab_head_nll_ls_fwd with the entropy term -beta m H -> loss_sum [1], argmax [M], pre [M, V] (aliasing slab 0; the whole
+    loss's gradient), nll_sum [1] (unsmoothed, without the entropy term), ent_sum [1] (sum_r m H)"""
+    eps, beta = check_label_smoothing(eps), check_entropy_beta(beta)
+    ks, M, V = parts.shape
+    _check_rows("vocab_head_nll_ent_fwd", M, target=target, w=w, m=m)
+    dev = parts.device
+    rows = torch.empty(6, M, device=dev, dtype=torch.float32)          # (loss, NLL, entropy; then the rows' fp32 remainders)
+    sums = torch.empty(3, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64)
+    pre = parts[0]
+    _check(lib().cvc_vocab_head_nll_ent_fwd(_dev(parts), ks, M * V, V, _dev(bias), _dev(target, torch.int64), _dev(w), _dev(m), M, V, eps,
+                                            beta, pre.data_ptr(), V, _dev(amax, torch.int64), _dev(rows), _dev(sums), rows[1].data_ptr(),
+                                            sums[1:].data_ptr(), rows[2].data_ptr(), sums[2:].data_ptr(), rows[3].data_ptr(), _stream()),
+           "cvc_vocab_head_nll_ent_fwd")
+    return sums[0:1], amax, pre, sums[1:2], sums[2:3]
+
+
+def vocab_nll_ent_bwd(logits, lse, target, w, m, row_ent, g, eps: float, beta: float):
+    eps, beta = check_label_smoothing(eps), check_entropy_beta(beta)
+    M, V = logits.shape
+    _check_rows("vocab_nll_ent_bwd", M, lse=lse, target=target, w=w, m=m, row_ent=row_ent)
+    d = torch.empty_like(logits)
+    _check(lib().cvc_vocab_nll_ent_bwd(_dev(logits), _dev(lse), _dev(target, torch.int64), _dev(w), _dev(m), _dev(row_ent), _dev(g), M, V,
+                                       eps, beta, _dev(d), _stream()), "cvc_vocab_nll_ent_bwd")
     return d
 
 

@@ -8,6 +8,7 @@ gradient all-reduce instead of nn.DataParallel; the dataset is the synthetic sta
 """
 from __future__ import annotations
 
+import argparse
 import json
 import os
 import pickle
@@ -90,6 +91,19 @@ def build_parser():
                         help="train against (1 - eps) one-hot + eps / vocabulary (torch's cross_entropy label_smoothing), eps in [0, 1); "
                              "0 = off.  Self-critical steps, scoring and evaluation are never smoothed; with eps > 0 the display line "
                              "also shows the unsmoothed NLL")
+    # entropy regulariser of the vocabulary criterion (cvc.functional.vocab_head_nll entropy_beta=): all three are off by default
+    # and then leave no key in the options -- every launch is what it was
+    parser.add_argument("--confidence_penalty", type=float, default=argparse.SUPPRESS,
+                        help="beta: the cross-entropy and scheduled-sampling steps add -beta x the mean entropy of the word "
+                             "distribution to both language losses (Pereyra et al. 2017; beta > 0 penalises confident distributions); "
+                             "the display line also shows the mean entropy H.  Evaluation and scoring carry no penalty")
+    parser.add_argument("--scst_entropy", type=float, default=argparse.SUPPRESS,
+                        help="beta: the self-critical steps add the entropy bonus -beta x the mean entropy of the word distribution "
+                             "over the rollouts' steps to the loss (Williams & Peng 1991), against the collapse of the policy onto the "
+                             "greedy caption.  The entropy is the model's full-vocabulary one at temperature 1, not the sampler's")
+    parser.add_argument("--log_entropy", action="store_true", default=argparse.SUPPRESS,
+                        help="report the mean entropy H of the word distribution on the display line and in the histories without "
+                             "changing the loss (beta = 0 wherever no coefficient is given)")
     # consensus (minimum-Bayes-risk) caption selection at evaluation (model._sample(consensus=...); DecodeEngine.consensus)
     parser.add_argument("--consensus", choices=("off", "samples", "beam"), default="off",
                         help="keep per clip the candidate with the highest mean CIDEr-D against the clip's other candidates (training "
@@ -114,6 +128,16 @@ def check_label_smoothing_flag(eps):
         raise SystemExit("--label_smoothing must lie in [0, 1), got %r" % (eps,))
 
 
+def check_entropy_flags(opt):
+    """--confidence_penalty and --scst_entropy are finite numbers where given: anything else ends the run with a message, before any
+    set-up"""
+    import math
+    for name in ("confidence_penalty", "scst_entropy"):
+        beta = getattr(opt, name, None)
+        if beta is not None and not math.isfinite(beta):
+            raise SystemExit("--%s must be a finite number, got %r" % (name, beta))
+
+
 def main(argv=None, sample=None, score=None):
     """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
@@ -122,6 +146,7 @@ def main(argv=None, sample=None, score=None):
     parser = build_parser()
     opt = parser.parse_args(argv)
     check_label_smoothing_flag(opt.label_smoothing)
+    check_entropy_flags(opt)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
     opt.test_mode = opt.val_split in ["testing", "hidden_test"]                       # reference main.py:57
@@ -285,7 +310,7 @@ def main(argv=None, sample=None, score=None):
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
                          "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history),
-                         "nll_history": dict(trainer.nll_history)}
+                         "nll_history": dict(trainer.nll_history), "entropy_history": dict(trainer.entropy_history)}
             with open(os.path.join(save_dir, "infos_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(infos, f)
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:

@@ -87,12 +87,21 @@ def _masked_nll_mean(txt_input, target, label_smoothing=0.0):
     return (total / count).reshape(())
 
 
-def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None, label_smoothing=0.0, want_nll=False):
+def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None, label_smoothing=0.0, want_nll=False,
+                                 entropy_beta=None, want_entropy=False):
     """Same value as _masked_nll_mean(log_softmax(logits), target), plus the per-row argmax, from one fused pass.
     t_major: the rows of `logits` are ordered t * B + b (the C-driven training loops' outputs) instead of b * T + t.
-    row_weight, label_smoothing, want_nll: see _masked_nll_mean_from_head."""
+    row_weight, label_smoothing, want_nll, entropy_beta, want_entropy: see _masked_nll_mean_from_head."""
     w = _text_mask(target).to(torch.float32)
-    if row_weight is not None:
+    count = w.sum()
+    ent = ()
+    if entropy_beta is not None or want_entropy:
+        tf, wf = (target.t().reshape(-1), w.t().reshape(-1)) if t_major else (target.reshape(-1), w.reshape(-1))
+        total, argmax, nll, h = F_.vocab_nll(logits, tf, wf if row_weight is None else row_weight.reshape(-1),
+                                             label_smoothing=0.0 if row_weight is not None else label_smoothing, return_nll=True,
+                                             entropy_beta=entropy_beta, entropy_weight=wf, return_entropy=True)
+        ent = ((h / count).reshape(()),) if want_entropy else ()
+    elif row_weight is not None:
         total, argmax = F_.vocab_nll(logits, (target.t() if t_major else target).reshape(-1), row_weight.reshape(-1))
         nll = total.detach()
     elif t_major:
@@ -100,13 +109,12 @@ def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None,
                                           return_nll=True)
     else:
         total, argmax, nll = F_.vocab_nll(logits, target.reshape(-1), w.reshape(-1), label_smoothing=label_smoothing, return_nll=True)
-    count = w.sum()
     res = ((total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
-    return (*res, (nll / count).reshape(())) if want_nll else res
+    return (*res, *(((nll / count).reshape(()),) if want_nll else ()), *ent)
 
 
 def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False, row_weight=None,
-                               label_smoothing=0.0, want_nll=False):
+                               label_smoothing=0.0, want_nll=False, entropy_beta=None, want_entropy=False):
     """_masked_nll_mean_from_logits(x W^T + b, target) with the criterion folded into the vocabulary head's GEMM finish: the logits
     are never materialised (cvc.functional.vocab_head_nll); falls back to the two-step form for shapes that kernel does not take.
     row_weight: a real weight per row of x (in x's row order, any sign, 0 where the loss mask is 0) in place of the 0 / 1 loss mask:
@@ -114,12 +122,19 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
     label_smoothing: eps in [0, 1), the target distribution (1 - eps) onehot + eps / V (cvc.functional.vocab_head_nll).  The
     self-critical loss IGNORES it: with row_weight the criterion is the one-hot one whatever eps is, because REINFORCE's gradient
     is advantage x grad log p(sampled word) -- it needs the log-prob itself, not a regularised target.
-    want_nll: a third result, the UNSMOOTHED mean as a scalar without a graph (the figure to log beside a smoothed loss)."""
+    want_nll: a further result, the UNSMOOTHED mean as a scalar without a graph (the figure to log beside a smoothed loss).
+    entropy_beta: beta (finite, any sign) adds -beta sum_r mask[r] H[r] / sum(mask) to the loss, H the entropy of the row's softmax
+    (the model's full-vocabulary distribution at temperature 1, not a sampler's tempered, truncated or UNK-free one): an entropy
+    bonus with row_weight, a confidence penalty without.  The entropy weight is always the loss mask of `target`, in x's row
+    order; it applies with row_weight too (label smoothing does not).  None: today's launches; 0: the entropy is computed and
+    nothing else changes.
+    want_entropy: a last result, the mean entropy sum_r mask[r] H[r] / sum(mask) as a scalar without a graph."""
     if row_weight is not None:
         label_smoothing = 0.0
     if not F_.vocab_head_nll_ok(x, weight):
         return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major, row_weight=row_weight,
-                                            label_smoothing=label_smoothing, want_nll=want_nll)
+                                            label_smoothing=label_smoothing, want_nll=want_nll, entropy_beta=entropy_beta,
+                                            want_entropy=want_entropy)
     # the loss mask, its count and the t-major copies depend on the target alone: both heads of a cyclical pass (decode,
     # reconstruction) score against the same target tensor, so they are formed once and kept on it
     pre = getattr(target, "_cvc_nll_pre", None)
@@ -129,15 +144,16 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
         pre = ((target._version, t_major), tf.contiguous(), wf.contiguous(), w.sum())
         target._cvc_nll_pre = pre
     _, tf, wf, count = pre
+    ent = dict(entropy_beta=entropy_beta, entropy_weight=wf, return_entropy=True) if entropy_beta is not None or want_entropy else {}
     if row_weight is not None:
         wf = row_weight.reshape(-1).contiguous()
     if compute_only:       # -> (opaque result for a later call with done=, the argmax words)
-        done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf, label_smoothing=label_smoothing)
+        done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf, label_smoothing=label_smoothing, **ent)
         argmax = done[1]
         return done, (argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
-    total, argmax, nll = F_.vocab_head_nll(x, weight, bias, tf, wf, done, label_smoothing=label_smoothing, return_nll=True)
+    total, argmax, nll, *h = F_.vocab_head_nll(x, weight, bias, tf, wf, done, label_smoothing=label_smoothing, return_nll=True, **ent)
     res = ((total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
-    return (*res, (nll / count).reshape(())) if want_nll else res
+    return (*res, *(((nll / count).reshape(()),) if want_nll else ()), *(((h[0] / count).reshape(()),) if want_entropy else ()))
 
 
 def _opt_label_smoothing(opt, label_smoothing):
@@ -148,21 +164,42 @@ def _opt_label_smoothing(opt, label_smoothing):
     return hip.check_label_smoothing(0.0 if label_smoothing is None else label_smoothing)
 
 
+def _opt_confidence_penalty(opt, confidence_penalty):
+    """the criteria's entropy coefficient: the constructor argument, else opt.confidence_penalty, else None (off: today's launches);
+    validated (ValueError unless finite)"""
+    from .. import hip
+    if confidence_penalty is None:
+        confidence_penalty = getattr(opt, "confidence_penalty", None) if opt is not None else None
+    return None if confidence_penalty is None else hip.check_entropy_beta(confidence_penalty, "confidence_penalty")
+
+
 class LMCriterion(nn.Module):
     """reference misc/utils.py:127-172.  label_smoothing (argument, else opt.label_smoothing, else 0): the language loss is the
     smoothed cross entropy of torch.nn.functional.cross_entropy(label_smoothing=); after a from_logits / from_head call with it > 0
-    last_nll is the UNSMOOTHED mean NLL of that call (a device scalar without a graph), else None."""
+    last_nll is the UNSMOOTHED mean NLL of that call (a device scalar without a graph), else None.
+    confidence_penalty (argument, else opt.confidence_penalty, else None): beta adds -beta x the mean masked entropy of the word
+    distribution to the language loss (Pereyra et al. 2017; beta > 0 penalises confident distributions); after a from_logits /
+    from_head call with it not None (0: only measured) last_entropy is that mean entropy (a device scalar without a graph), else
+    None.  The log-prob form forward() has no entropy term."""
 
-    def __init__(self, opt, label_smoothing=None):
+    def __init__(self, opt, label_smoothing=None, confidence_penalty=None):
         super().__init__()
         self.vocab_size = opt.vocab_size
         self.label_smoothing = _opt_label_smoothing(opt, label_smoothing)
+        self.confidence_penalty = _opt_confidence_penalty(opt, confidence_penalty)
         self.last_nll = None
+        self.last_entropy = None
 
     def _keep(self, res):
-        """(loss, argmax[, unsmoothed mean -- asked for when smoothing is on]) -> (loss, argmax); the third stays on the module"""
-        self.last_nll = res[2] if len(res) > 2 else None
+        """(loss, argmax[, unsmoothed mean -- asked for when smoothing is on][, mean entropy -- when the penalty is not None]) ->
+        (loss, argmax); the others stay on the module"""
+        rest = list(res[2:])
+        self.last_nll = rest.pop(0) if self.label_smoothing > 0 else None
+        self.last_entropy = rest.pop(0) if self.confidence_penalty is not None else None
         return res[0], res[1]
+
+    def _ent(self):
+        return dict(entropy_beta=self.confidence_penalty, want_entropy=self.confidence_penalty is not None)
 
     def forward(self, txt_input, att2_weights, ground_weights, target, att2_target, input_seq):
         if not torch.cuda.is_current_stream_capturing():
@@ -176,7 +213,7 @@ class LMCriterion(nn.Module):
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
         loss, argmax = self._keep(_masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing,
-                                                               want_nll=self.label_smoothing > 0))
+                                                               want_nll=self.label_smoothing > 0, **self._ent()))
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
     def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None, row_weight=None):
@@ -186,7 +223,8 @@ class LMCriterion(nn.Module):
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
         loss, argmax = self._keep(_masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done, row_weight=row_weight,
-                                                             label_smoothing=self.label_smoothing, want_nll=self.label_smoothing > 0))
+                                                             label_smoothing=self.label_smoothing, want_nll=self.label_smoothing > 0,
+                                                             **self._ent()))
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
     def head_words(self, x, head, target, t_major=False):
@@ -195,7 +233,7 @@ class LMCriterion(nn.Module):
         if not F_.vocab_head_nll_ok(x, head.weight):
             return None
         return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, compute_only=True,
-                                          label_smoothing=self.label_smoothing)
+                                          label_smoothing=self.label_smoothing, entropy_beta=self.confidence_penalty)
 
     @staticmethod
     def attention_losses(att2_weights, ground_weights, att2_target):
@@ -215,21 +253,37 @@ class LMCriterion(nn.Module):
 
 class LanguageCriterion(nn.Module):
     """reference misc/utils.py:175-192.  label_smoothing (argument, else opt.label_smoothing, else 0): as LMCriterion; a call with
-    row_weight (the self-critical loss) ignores it."""
+    row_weight (the self-critical loss) ignores it.  confidence_penalty (argument, else opt.confidence_penalty, else None): as
+    LMCriterion, for the calls without row_weight; a call with row_weight takes its own entropy_beta (the self-critical loss's entropy
+    bonus) instead.  last_entropy: the mean masked entropy of the last from_logits / from_head call whose coefficient was not None
+    (a device scalar without a graph), else None."""
 
-    def __init__(self, opt=None, label_smoothing=None):
+    def __init__(self, opt=None, label_smoothing=None, confidence_penalty=None):
         super().__init__()
         self.label_smoothing = _opt_label_smoothing(opt, label_smoothing)
+        self.confidence_penalty = _opt_confidence_penalty(opt, confidence_penalty)
+        self.last_entropy = None
 
     def forward(self, txt_input, target):
         return _masked_nll_mean(txt_input, target, self.label_smoothing)
 
-    def from_logits(self, logits, target, t_major=False):
-        return _masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing)[0]
+    def _keep(self, res, beta):
+        self.last_entropy = res[2] if beta is not None else None
+        return res[0]
 
-    def from_head(self, x, head, target, t_major=False, row_weight=None):
-        return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, row_weight=row_weight,
-                                          label_smoothing=self.label_smoothing)[0]
+    def from_logits(self, logits, target, t_major=False):
+        beta = self.confidence_penalty
+        return self._keep(_masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing, entropy_beta=beta,
+                                                       want_entropy=beta is not None), beta)
+
+    def from_head(self, x, head, target, t_major=False, row_weight=None, entropy_beta=None):
+        beta = self.confidence_penalty if row_weight is None else entropy_beta
+        if beta is not None and row_weight is not None:
+            from .. import hip
+            beta = hip.check_entropy_beta(beta)
+        return self._keep(_masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, row_weight=row_weight,
+                                                     label_smoothing=self.label_smoothing, entropy_beta=beta,
+                                                     want_entropy=beta is not None), beta)
 
 
 def bbox_overlaps(rois, gt_box, frm_mask):

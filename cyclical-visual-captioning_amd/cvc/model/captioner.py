@@ -95,6 +95,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # UNSMOOTHED mean NLL here as a device scalar (no graph), else None.  The self-critical loss and every scoring / evaluation
         # path are not smoothed.
         self.last_nll = None
+        # entropy regulariser: both criteria read opts.confidence_penalty (None = off); model.confidence_penalty = beta changes both.
+        # With it not None a training pass leaves loop A's mean masked entropy of the word distribution here, and scst_loss with
+        # entropy_beta not None the rollouts' (a device scalar, no graph), else None.  Evaluation passes carry no penalty.
+        self.last_entropy = None
         self.beam_size = int(getattr(opts, "beam_size", 1))
         self.use_hip_graph = bool(getattr(opts, "hip_graph", False))
         # decoding rule of _sample: sample_max = 1 takes the arg-max word (greedy / beam); sample_max = 0 samples from
@@ -210,14 +214,17 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         instead of gt_caption[:, :T] -- scheduled sampling; targets, label glue, the grounder's class inputs and loops B / C are the
         ground truth's.  None: teacher forcing, as always."""
         F_.new_step()
-        if lang_eval and teacher_forcing and self.label_smoothing > 0:
-            # an evaluation pass reports the model's true log-probs: label smoothing is the training criterion's alone
+        if lang_eval and teacher_forcing and (self.label_smoothing > 0 or self.confidence_penalty is not None):
+            # an evaluation pass reports the model's true log-probs: label smoothing and the confidence penalty are the training
+            # criterion's alone
             eps, self.label_smoothing = self.label_smoothing, 0.0
+            beta, self.confidence_penalty = self.confidence_penalty, None
             try:
                 return self._forward_3_loops(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes,
                                              region_feats, frm_mask, sample_idx, pnt_mask, ss_inputs)
             finally:
                 self.label_smoothing = eps
+                self.confidence_penalty = beta
         if lang_eval is False or teacher_forcing:
             return self._forward_3_loops(segs_feat, input_seq, proposals, gt_caption, num, mask_boxes, gt_boxes,
                                          region_feats, frm_mask, sample_idx, pnt_mask, ss_inputs)
@@ -338,6 +345,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         lm_loss, att2_loss, ground_loss, output_seq = self.critLM.from_logits(
             lang_logits, att2_weights, ground_weights, target, roi_labels[:, :T, :].clone(), input_seq[:, 1:T + 1, 0].clone())
         self.last_nll = self.critLM.last_nll
+        self.last_entropy = self.critLM.last_entropy
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
 
@@ -375,6 +383,15 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
     def label_smoothing(self, eps):
         eps = hip.check_label_smoothing(eps)
         self.critLM.label_smoothing = self.xe_criterion.label_smoothing = eps
+
+    @property
+    def confidence_penalty(self):
+        return self.critLM.confidence_penalty
+
+    @confidence_penalty.setter
+    def confidence_penalty(self, beta):
+        beta = None if beta is None else hip.check_entropy_beta(beta, "confidence_penalty")
+        self.critLM.confidence_penalty = self.xe_criterion.confidence_penalty = beta
 
     # ------------------------------------------------------------------ training pass on the C-driven loops
     def _loop_plan(self, B, like):
@@ -462,6 +479,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             out_a.view(T * B, R), self.logit, att2_weights, ground_weights, target, roi_labels[:, :T, :], input_seq[:, 1:T + 1, 0],
             t_major=True, done=done)
         self.last_nll = self.critLM.last_nll
+        self.last_entropy = self.critLM.last_entropy
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
         if out_c is None:
@@ -498,7 +516,7 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 None if fms[0] is None else torch.cat(fms, 1))
 
     # ------------------------------------------------------------------ self-critical training: the gradient pass
-    def scst_loss(self, encoded, words, reward, base=None, per_clip: int = 1, wor=None):
+    def scst_loss(self, encoded, words, reward, base=None, per_clip: int = 1, wor=None, entropy_beta=None):
         """The self-critical loss of sampled captions: loop A (reference :242-270) teacher-forced on the SAMPLED words, the vocabulary
         head and its criterion with the advantage as row weight:  -sum_{r,t} w[r, t] log p(words[r, t]) / sum(mask),
         w = advantage x mask (cvc_scst_weights; mask = LMCriterion's: the steps up to and including the first 0).
@@ -512,6 +530,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         w comes from cvc_scst_weights_wor -- importance weights and a per-row baseline ("Self-critical training
         without replacement") --, base must be None, and self.last_wor = dict(wgt [B * per_clip], est [B]) keeps the weights and the
         clip's estimated expected reward.  None: cvc_scst_weights, the launches and the bits of a step without it.
+        entropy_beta = beta (finite): the entropy bonus, -beta x the mean entropy of the word distribution over the steps that count
+        (the mask of w) added to the loss; the entropy is the model's full-vocabulary one at temperature 1, not the sampler's (which
+        leaves UNK out and may be tempered or truncated), as log p above.  self.last_entropy keeps that mean (no graph).  0: the
+        entropy is measured, loss and gradient keep their bits.  None: the launches and the bits of a step without it.
         -> (loss (), adv [B * per_clip])"""
         from .. import train_loops
         fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
@@ -571,7 +593,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             self.last_wor = dict(wgt=wgt, est=est)
         if self.debug_collect is not None:
             self.debug_collect.update(scst_out=out, scst_t_major=t_major, scst_w=w)
-        loss = self.xe_criterion.from_head(out, self.logit, target, t_major=t_major, row_weight=w)
+        loss = self.xe_criterion.from_head(out, self.logit, target, t_major=t_major, row_weight=w, entropy_beta=entropy_beta)
+        self.last_entropy = self.xe_criterion.last_entropy
         return loss.reshape(()), adv
 
     def _vis_embed(self, xt_clamp):

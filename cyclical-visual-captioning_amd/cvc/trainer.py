@@ -136,6 +136,27 @@ class Trainer:
         # element at its END, loop A's unsmoothed mean NLL (model.last_nll), and train() logs it beside the smoothed LM loss
         self.label_smoothing = float(getattr(getattr(model, "module", model), "label_smoothing", 0.0))
         self.nll_history = {}         # epoch -> the mean unsmoothed NLL of every display interval (label_smoothing > 0)
+        # ---- entropy regulariser (cvc.main --confidence_penalty / --scst_entropy / --log_entropy): the cross-entropy and
+        # scheduled-sampling steps take opts.confidence_penalty (else the model's), the self-critical steps opts.scst_entropy; None =
+        # off (the launches of a trainer without it), log_entropy turns a None into 0 = measured only.  Fixed when the trainer is built
+        # -- a captured step holds beta as a launch argument.  With it not None every step's result carries one more element at its
+        # very END (behind the NLL of label smoothing), the mean masked entropy of the word distribution, read back with the rest
+        from . import hip as _hip
+        core = getattr(model, "module", model)
+        self.log_entropy = bool(getattr(opts, "log_entropy", False))
+        beta = getattr(opts, "confidence_penalty", None)
+        if beta is None:
+            beta = getattr(core, "confidence_penalty", None)
+        if beta is None and self.log_entropy:
+            beta = 0.0
+        self.confidence_penalty = None if beta is None else _hip.check_entropy_beta(beta, "confidence_penalty")
+        if self.confidence_penalty is not None and getattr(core, "confidence_penalty", None) != self.confidence_penalty:
+            core.confidence_penalty = self.confidence_penalty
+        beta = getattr(opts, "scst_entropy", None)
+        if beta is None and self.log_entropy:
+            beta = 0.0
+        self.scst_entropy = None if beta is None else _hip.check_entropy_beta(beta, "scst_entropy")
+        self.entropy_history = {}     # epoch -> the mean entropy of every display interval (a coefficient that is not None)
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -201,6 +222,17 @@ class Trainer:
                                f"{self.label_smoothing} (captured steps hold it as a launch argument: build a new Trainer)")
         return (model.last_nll.detach().reshape(()),)
 
+    def _ent_tail(self):
+        """(loop A's mean masked entropy of the pass that just ran,) with a confidence penalty (0 included), else ()"""
+        model = getattr(self.model, "module", self.model)
+        beta = getattr(model, "confidence_penalty", None)
+        if beta != self.confidence_penalty:
+            raise RuntimeError(f"Trainer: the model's confidence_penalty is {beta}, the trainer was built with "
+                               f"{self.confidence_penalty} (captured steps hold it as a launch argument: build a new Trainer)")
+        if self.confidence_penalty is None:
+            return ()
+        return (model.last_entropy.detach().reshape(()),)
+
     def train_step(self, batch):
         return self.train_step_prepared(self._prepare(batch, True))
 
@@ -214,7 +246,7 @@ class Trainer:
         loss, lm, att2, cls, rec = self.loss_mix(out)
         self._backward_and_update(loss)
         self._weights_changed()
-        return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), *self._nll_tail())
+        return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), *self._nll_tail(), *self._ent_tail())
 
     def _ss_step_prepared(self, b):
         """The scheduled-sampling step (Bengio et al. 2015; model.ss_prob > 0): the encoder once in eval mode without autograd, one
@@ -240,7 +272,7 @@ class Trainer:
             model.train(was_training)
         out = self._call(b, ss_inputs=ss_inputs)
         loss, lm, att2, cls, rec = self.loss_mix(out)
-        nll = self._nll_tail()
+        nll = self._nll_tail() + self._ent_tail()
         self._backward_and_update(loss)
         model.refresh_decode_weights()
         T = took.size(1)
@@ -380,7 +412,9 @@ class Trainer:
                     base = cider.score(greedy, refs, nref) if mix is None else metrics.reward_mix(mix, cider, greedy, refs, nref)[0]
             if bool(getattr(o, "scst_dropout", False)):
                 model.train()
-            loss, adv = model.scst_loss(enc, seq, reward, base, S) if wor is None else model.scst_loss(enc, seq, reward, None, S, wor=wor)
+            ent = {} if self.scst_entropy is None else dict(entropy_beta=self.scst_entropy)       # (off: the call of a trainer without it)
+            loss, adv = (model.scst_loss(enc, seq, reward, base, S, **ent) if wor is None else
+                         model.scst_loss(enc, seq, reward, None, S, wor=wor, **ent))
         finally:
             model.train(was_training)
         self._backward_and_update(loss)
@@ -389,6 +423,8 @@ class Trainer:
         self.last_scst = dict(seq=seq, logprob=logprob, reward=reward, base=base, greedy=greedy, adv=adv, seed=seed)
         if mix is not None:
             self.last_scst["reward_parts"] = parts
+        if self.scst_entropy is not None:       # (the mean entropy of the word distribution over the rollouts' steps: a device scalar)
+            self.last_scst["entropy"] = model.last_entropy
         if wor is not None:
             est = model.last_wor["est"]
             self.last_scst.update(logq=wor["logq"], G=wor["G"], state=wor["state"], wgt=model.last_wor["wgt"], expected_reward=est,
@@ -401,7 +437,7 @@ class Trainer:
     def _core_step(self, b):
         out = self._call(b)
         loss, lm, att2, cls, rec = self.loss_mix(out)
-        nll = self._nll_tail()
+        nll = self._nll_tail() + self._ent_tail()
         self._backward_and_update(loss, set_to_none=False)
         res = torch.stack([loss.detach().reshape(()), lm.detach().reshape(()), att2.detach().reshape(()),
                            cls.detach().reshape(()), rec.detach().reshape(())])
@@ -411,11 +447,12 @@ class Trainer:
             # element; the word is cleared at the END of the step (whoever sets it before a step voids that step: tests do)
             void = st != 0
             res = torch.cat((torch.where(void, torch.zeros_like(res), res), void.to(res.dtype)))
-            if nll:                       # (label smoothing: the unsmoothed NLL goes last, behind the layout everybody knows)
-                res = torch.cat((res, torch.where(void, torch.zeros_like(nll[0]), nll[0]).reshape(1)))
+            if nll:                       # (label smoothing: the unsmoothed NLL goes last, behind the layout everybody knows; the
+                tail = torch.stack(nll)   # mean entropy of a confidence penalty behind that)
+                res = torch.cat((res, torch.where(void, torch.zeros_like(tail), tail)))
             st.zero_()
         elif nll:
-            res = torch.cat((res, nll[0].reshape(1)))
+            res = torch.cat((res, torch.stack(nll)))
         return res
 
     def train_step_graphed(self, batch):
@@ -425,7 +462,7 @@ class Trainer:
         the captured step when it runs on RCCL (backend "nccl": the collectives are issued on the communicator's stream behind
         events of the capturing stream, which stream capture records as graph dependencies); other backends (gloo) cannot be
         captured.  Returns a static tensor [loss, lm, att2, cls, recon] (clone to keep); with label smoothing one more element at
-        the end, loop A's unsmoothed mean NLL."""
+        the end, loop A's unsmoothed mean NLL; with a confidence penalty (0 included) one more behind that, loop A's mean entropy."""
         self._check_capturable()
         b = self._prepare(batch, True)
         if self._graph is None:
@@ -615,7 +652,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ epoch loops
     def train(self, epoch, tb_logger=None):
-        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled", "nll")}
+        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled", "nll", "entropy")}
         self.model.train()
         end = time.time()
         n_steps = len(self.train_loader) - 1                 # the reference drops the last batch (:55)
@@ -624,6 +661,8 @@ class Trainer:
         ss = not scst and float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0
         graphed = self.graph_capable() and not scst and not ss
         smooth = self.label_smoothing > 0 and not scst       # (a last element of every step's result: the unsmoothed NLL)
+        ent = (self.scst_entropy if scst else self.confidence_penalty) is not None     # (the very last element: the mean entropy)
+        i_nll = -2 if ent else -1
         self._active_buckets = self.shape_buckets if graphed else 0       # (read by _prepare, which the prefetcher calls)
         # batch k+1 is staged into HBM on a side stream while step k runs
         batches = DevicePrefetcher(self.train_loader, lambda raw: self._prepare(raw, True), self.device, limit=n_steps)
@@ -653,10 +692,14 @@ class Trainer:
                         r = r.tolist()
                         sums[:5] = [a + b_ for a, b_ in zip(sums[:5], r[:5])]
                         if smooth:
+                            sums[i_nll] += r[i_nll]
+                        if ent:
                             sums[-1] += r[-1]
                         if void[-1] == pending - 1:
                             cur[:5] = r[:5]
                             if smooth:
+                                cur[i_nll] = r[i_nll]
+                            if ent:
                                 cur[-1] = r[-1]
                 kept.clear()
             else:
@@ -669,9 +712,13 @@ class Trainer:
                 meters["sampled"].update(sums[5] / pending, n * pending)
                 meters["sampled"].val = cur[5]
             if smooth:                                # (the last element: loop A's unsmoothed mean NLL beside the smoothed LM loss)
-                meters["nll"].update(sums[-1] / pending, n * pending)
-                meters["nll"].val = cur[-1]
-                self.nll_history.setdefault(epoch, []).append(sums[-1] / pending)
+                meters["nll"].update(sums[i_nll] / pending, n * pending)
+                meters["nll"].val = cur[i_nll]
+                self.nll_history.setdefault(epoch, []).append(sums[i_nll] / pending)
+            if ent:                                   # (the very last element: the mean entropy of the word distribution)
+                meters["entropy"].update(sums[-1] / pending, n * pending)
+                meters["entropy"].val = cur[-1]
+                self.entropy_history.setdefault(epoch, []).append(sums[-1] / pending)
             for name, i in (("lm", 1), ("attn", 2), ("cls", 3), ("recon", 4)):
                 meters[name].update(sums[i] / pending, n * pending)
                 meters[name].val = cur[i]
@@ -688,7 +735,8 @@ class Trainer:
                     # the meters' "LM Loss" is the self-critical loss; the attention / class / reconstruction terms take no part
                     s_loss, s_reward, _s_base, _s_adv = self.scst_step_prepared(b)
                     zero = torch.zeros((), device=s_loss.device)
-                    res = torch.stack([s_loss, s_loss, zero, zero, zero, s_reward.to(s_loss.dtype)])
+                    res = torch.stack([s_loss, s_loss, zero, zero, zero, s_reward.to(s_loss.dtype)] +
+                                      ([self.last_scst["entropy"].to(s_loss.dtype).reshape(())] if ent else []))
                 elif graphed:
                     res = self.train_step_bucketed(b)
                 elif ss:                          # (a sixth element: the step's share of sampled inputs)
@@ -711,7 +759,8 @@ class Trainer:
                               c=meters["cls"], r=meters["recon"]) +
                           ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else '') +
                           ('\tSampled {s.val:.3f} ({s.avg:.3f})'.format(s=meters["sampled"]) if ss else '') +
-                          ('\tNLL {s.val:.4f} ({s.avg:.4f})'.format(s=meters["nll"]) if smooth else ''))
+                          ('\tNLL {s.val:.4f} ({s.avg:.4f})'.format(s=meters["nll"]) if smooth else '') +
+                          ('\tH {s.val:.4f} ({s.avg:.4f})'.format(s=meters["entropy"]) if ent else ''))
                 else:
                     if deferred and pending >= KEEP_MAX:
                         flush()
@@ -728,6 +777,8 @@ class Trainer:
                 tb_logger.add_scalar('train/scst_reward', meters["reward"].avg, epoch)
             if smooth:
                 tb_logger.add_scalar('train/lm_nll', meters["nll"].avg, epoch)
+            if ent:
+                tb_logger.add_scalar('train/entropy', meters["entropy"].avg, epoch)
 
     def _segment_timestamps(self):
         """{video: {segment: [start, end]}} of the validation segments: the reference reads them from the ANet-Entities

@@ -679,6 +679,40 @@ int cvc_vocab_nll_ls_fwd(const float* logits, const int64_t* target, const float
 int cvc_vocab_nll_ls_bwd(const float* logits, const float* lse, const int64_t* target, const float* w, const float* g, int M,
                          int V, float eps, float* d_logits, cvc_stream_t stream);
 
+/* ---- entropy regulariser in the vocabulary criterion (csrc/vocab.hip; cvc.functional.vocab_head_nll / vocab_nll entropy_beta=):
+ * the entropy bonus of a policy-gradient loss (Williams & Peng 1991) and the confidence penalty of a cross-entropy loss (Pereyra et
+ * al. 2017).  The three label-smoothing entries above with a coefficient beta (finite, any sign; beta > 0 rewards entropy) and an
+ * entropy weight m [M] (the 0 / 1 loss mask) beside the NLL weight w [M] (the mask, or advantage x mask: any sign).  Per row, with
+ * lse = logsumexp(z) and p[v] = exp(z[v] - lse):
+ *   H        = sum_v p[v] (lse - z[v])       every term >= 0, a column at -inf adds exactly 0; summed, not formed as lse - sum p z
+ *   row_loss = [the label-smoothing entry's, for w and eps]  -  beta m H
+ *   pre[v] / d_logits[v] = [the label-smoothing entry's]  +  (g[0]) beta m p[v] (z[v] - lse + H)      exactly 0 at z[v] = -inf
+ *   row_ent  = m H, always written; ent_sum[0] its sum over the rows in loss_sum's fixed order
+ *   row_nll / nll_sum as above (nullable, both or neither).
+ * H is the entropy of the model's full-vocabulary distribution at temperature 1.  It is one more pass over the row once lse is
+ * known (each thread its columns in ascending order) and one more fixed-order block reduction: a row stays bit-reproducible, and
+ * the fused and the two-step form agree bit for bit on equal logits.  beta == 0 (the monitor mode) gives the bits of the
+ * label-smoothing entries in loss, pre and NLL and still writes row_ent.  m == 0 and w == 0: an exactly zero row.  The backward reads
+ * the forward's row_ent and the same m.
+ * The row values of these entries are formed in fp64 (the fp32 values exp(z - max) added in fp64, lse = max + log of that sum, H and
+ * the three row expressions on top) and written as their fp32 value plus an fp32 remainder: row_lo [3, M] is that workspace (the
+ * remainders of row_loss, row_ent, row_nll; contents are the forward's own business).  The sums are one launch behind the row
+ * kernel: ent_sum, and with beta != 0 loss_sum and nll_sum, add value + remainder in fp64 in a fixed order and round once -- a sum
+ * is the fp64 result rounded to fp32; with beta == 0 row_loss, row_nll and their sums are the label-smoothing entries' (their bits).
+ * pre / d_logits are fp32 throughout.
+ * Null pointers (but bias, argmax, row_nll / nll_sum; row_lo included), beta not finite, eps outside [0, 1), the unsmoothed entries'
+ * size limits (fused head: V <= 8192): CVC_E_BADARG, before any launch. */
+int cvc_vocab_head_nll_ent_fwd(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
+                               const int64_t* target, const float* w, const float* m, int M, int V, float eps, float beta,
+                               float* pre, int ld_pre, int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll,
+                               float* nll_sum, float* row_ent, float* ent_sum, float* row_lo, cvc_stream_t stream);
+int cvc_vocab_nll_ent_fwd(const float* logits, const int64_t* target, const float* w, const float* m, int M, int V, float eps,
+                          float beta, float* lse, int64_t* argmax, float* row_loss, float* loss_sum, float* row_nll, float* nll_sum,
+                          float* row_ent, float* ent_sum, float* row_lo, cvc_stream_t stream);
+int cvc_vocab_nll_ent_bwd(const float* logits, const float* lse, const int64_t* target, const float* w, const float* m,
+                          const float* row_ent, const float* g, int M, int V, float eps, float beta, float* d_logits,
+                          cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
