@@ -656,23 +656,14 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         -> (seq [B, T], att2_weights [B, T, N], logprob [B, T] or None for a beam, pick [B] int32 -- the index of the kept sample /
         the kept slot --, utility [B * n] fp32), new tensors, everything selected on the device with pick (a beam's attention rows
         by cvc_beam_backtrack_from the picked slot); no host read-back."""
-        if self.forced:
-            raise RuntimeError("DecodeEngine.consensus: a forced engine scores given words, it has no candidates to choose among")
-        if self.mix:
-            raise RuntimeError("DecodeEngine.consensus: a mix engine's rows follow given captions (scheduled sampling), they are no "
-                               "candidates of one clip")
-        if self.beam > 1 and not self.beam_hist:
-            raise RuntimeError("DecodeEngine.consensus: a beam engine needs beam_history=True (the candidates are hypotheses())")
-        if self.nq < 2:
-            raise RuntimeError("DecodeEngine.consensus: one candidate per clip -- it needs sample_n > 1 or beam > 1")
-        B, T, N, n = self.B, self.T, self.N, self.nq
+        cand, n, live = self.candidates("consensus")
+        self.consensus_live = live          # (the mask this selection used: None = every sample counts; model.last_consensus keeps it)
+        B, T, N = self.B, self.T, self.N
         if self.sampling:
-            cand = self.words[1:].t().contiguous()
             utility, pick, best = table.consensus(cand, n)
             at = torch.arange(B, device=cand.device) * n + pick
             return (best, self.att_steps.permute(1, 0, 2).index_select(0, at), self.logprob.t().index_select(0, at), pick, utility)
-        seq, score = self.hypotheses()[:2]
-        utility, pick, _ = table.consensus(seq.reshape(B * n, T), n, live=torch.isfinite(score).reshape(-1))
+        utility, pick, _ = table.consensus(cand, n, live=live)
         start = pick.to(torch.int64)
         bt_seq = torch.empty(B, T, dtype=torch.int64, device=start.device)
         bt_att = torch.empty(B, T, N, dtype=torch.float32, device=start.device)
@@ -680,6 +671,33 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
                                                      T, N, start.data_ptr(), 1, bt_seq.data_ptr(), bt_att.data_ptr(), hip._stream()),
                    "cvc_beam_backtrack_from")
         return bt_seq, bt_att, None, pick, utility
+
+    def candidates(self, who: str = "candidates"):
+        """The candidate set of the last run() as consensus() and set_diversity() take it: (cand [B * n, T] int64, n, live [B * n] bool or
+        None).  A sampling engine with sample_n > 1: its rows, all live.  A beam engine with beam_history=True: its hypotheses(), live
+        where the score is finite.  Refuses a forced engine, a mix engine, a beam without histories and one candidate per clip."""
+        if self.forced:
+            raise RuntimeError(f"DecodeEngine.{who}: a forced engine scores given words, it has no candidates to choose among")
+        if self.mix:
+            raise RuntimeError(f"DecodeEngine.{who}: a mix engine's rows follow given captions (scheduled sampling), they are no "
+                               "candidates of one clip")
+        if self.beam > 1 and not self.beam_hist:
+            raise RuntimeError(f"DecodeEngine.{who}: a beam engine needs beam_history=True (the candidates are hypotheses())")
+        if self.nq < 2:
+            raise RuntimeError(f"DecodeEngine.{who}: one candidate per clip -- it needs sample_n > 1 or beam > 1")
+        if self.sampling:
+            return self.words[1:].t().contiguous(), self.nq, None
+        seq, score = self.hypotheses()[:2]
+        return seq.reshape(self.B * self.nq, self.T), self.nq, torch.isfinite(score).reshape(-1)
+
+    def set_diversity(self):
+        """Diversity of every clip's candidate set after run() ("Caption-set diversity"; csrc/diversity.hip):
+        cvc.metrics.set_diversity on exactly the candidates and live mask consensus() uses, with the same refusals.  -> dict(stats
+        [B, 12] int32, mbleu_stats [B * n, 10] int32, mbleu [B * n, 4], div [B, 2]), new tensors on the device; the engine's state
+        and launch lists are not touched, no host read-back.  (Not `diversity`: that attribute is the diverse beam's lambda.)"""
+        from .. import metrics
+        cand, n, live = self.candidates("set_diversity")
+        return metrics.set_diversity(cand, n, live)
 
     def _python_launches(self):
         if self._launches is None:

@@ -278,6 +278,8 @@ SIGNATURES = {
     "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # consensus caption selection: pairwise CIDEr-D among a clip's candidates, pick and picked row (csrc/consensus.hip; building block)
     "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
+    # caption-set diversity: distinct n-grams, mBLEU statistics, distinct captions per clip (csrc/diversity.hip; building block)
+    "cvc_caption_set_stats": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
     # grounding F1 of generated captions: picks per object word and frame, per-class counters (csrc/grounding.hip; building block)
     "cvc_grounding_f1": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # label smoothing in the vocabulary criterion: the fused head, the two-step form and its backward (csrc/vocab.hip; building blocks)
@@ -333,7 +335,7 @@ BLOCKS = {
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
-    "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
+    "cvc_caption_set_stats", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
     "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
@@ -1352,6 +1354,26 @@ def consensus_cider(cand: torch.Tensor, per_clip: int, keys: torch.Tensor, idf: 
                                      float(idf_unseen), float(sigma), _dev(utility), _dev(pick, torch.int32), _dev(best, torch.int64),
                                      _stream()), "cvc_consensus_cider")
     return utility, pick, best
+
+
+# --------------------------------------------------------------------------- caption-set diversity (csrc/diversity.hip)
+def caption_set_stats(cand: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None):
+    """cand [rows, T] int64, per_clip consecutive candidates per clip; live [rows] int32 or None (every row is live).
+    -> set_stats [clips, 12] int32 (distinct_1..4, total_1..4, live, unique, scored, 0), mbleu_stats [rows, 10] int32 and mbleu
+    [rows, 4] fp32 (the row against the clip's other live rows, caption_overlap's layout and bits)."""
+    per_clip = int(per_clip)
+    if cand.dim() != 2 or per_clip < 1 or cand.shape[0] < 1 or cand.shape[0] % per_clip != 0 \
+            or (live is not None and live.numel() != cand.shape[0]):
+        raise RuntimeError(f"cvc.hip.caption_set_stats: cand {tuple(cand.shape)}, per_clip {per_clip}, live "
+                           f"{None if live is None else tuple(live.shape)} do not fit")
+    rows, T = cand.shape
+    set_stats = torch.empty(rows // per_clip, 12, device=cand.device, dtype=torch.int32)
+    mbleu_stats = torch.empty(rows, 10, device=cand.device, dtype=torch.int32)
+    mbleu = torch.empty(rows, 4, device=cand.device, dtype=torch.float32)
+    _check(lib().cvc_caption_set_stats(_dev(cand, torch.int64, "cand"), _dev(live, torch.int32, "live"), rows, T, per_clip,
+                                       _dev(set_stats, torch.int32), _dev(mbleu_stats, torch.int32), _dev(mbleu), _stream()),
+           "cvc_caption_set_stats")
+    return set_stats, mbleu_stats, mbleu
 
 
 # --------------------------------------------------------------------------- grounding F1 of generated captions (csrc/grounding.hip)

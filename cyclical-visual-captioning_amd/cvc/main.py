@@ -119,7 +119,22 @@ def build_parser():
                              "constraints and --consensus beam, not with --group_size, --length_penalty or forced words")
     parser.add_argument("--stochastic_tau", type=float, default=1.0, help="temperature of the stochastic beam's sampling distribution")
     parser.add_argument("--sample_seed", type=int, default=0, help="seed of the stochastic beam's noise")
+    # caption-set diversity of the evaluation's candidates (cvc.metrics.DiversityScorer): off by default and then no key in the options
+    parser.add_argument("--val_diversity", action="store_true", default=argparse.SUPPRESS,
+                        help="score the diversity of every clip's candidate set in validation (Div_1, Div_2, mBLEU_4, Unique and the "
+                             "oracle CIDEr-D, on the GPU); needs --val_metrics device and a candidate set, i.e. --consensus samples|beam")
     return parser
+
+
+def check_val_diversity_flag(opt):
+    """--val_diversity needs the device metrics and an evaluation that decodes a candidate set per clip: anything else ends the run
+    with a message, before any set-up"""
+    if not getattr(opt, "val_diversity", False):
+        return
+    if opt.val_metrics != "device":
+        raise SystemExit("--val_diversity needs --val_metrics device (the diversity scores are computed on the GPU next to them)")
+    if opt.consensus == "off":
+        raise SystemExit("--val_diversity needs a candidate set per clip in evaluation: --consensus samples or --consensus beam")
 
 
 def check_label_smoothing_flag(eps):
@@ -139,7 +154,7 @@ def check_entropy_flags(opt):
 
 
 def main(argv=None, sample=None, score=None):
-    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) or (..., without_replacement, diversity) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
     score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
     (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
@@ -147,6 +162,7 @@ def main(argv=None, sample=None, score=None):
     opt = parser.parse_args(argv)
     check_label_smoothing_flag(opt.label_smoothing)
     check_entropy_flags(opt)
+    check_val_diversity_flag(opt)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
     opt.test_mode = opt.val_split in ["testing", "hidden_test"]                       # reference main.py:57
@@ -256,11 +272,12 @@ def main(argv=None, sample=None, score=None):
     # default: torch.distributed on gloo is the control plane only), whose collectives are captured into the step's HIP graph
     comm = exchange_comm() if (world > 1 and opt.dist_backend == "rccl") else None
     reducer = GradReducer(model.named_parameters(), comm=comm)
-    trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device")
+    trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device",
+                      **(dict(val_diversity=True) if getattr(opt, "val_diversity", False) else {}))
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
-        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus", "without_replacement"), sample[3:])))
+        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus", "without_replacement", "diversity"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
         if comm is not None:

@@ -20,6 +20,8 @@ CIDEr-D counts the end mark, METEOR and SPICE are not attempted.
 
 Further down: the grounding scores of the generated captions (csrc/grounding.hip; grounding, grounding_result, GroundingScorer) --
 F1_all / F1_loc in the manner of ActivityNet-Entities, for Trainer.eval with the device metrics and --eval_obj_grounding both on.
+At the end: the diversity of a clip's caption SET (csrc/diversity.hip; set_diversity, DiversityScorer) -- Div-1, Div-2, mBLEU, distinct
+captions, next to the set's oracle and mean CIDEr-D.
 """
 from __future__ import annotations
 
@@ -268,3 +270,123 @@ class GroundingScorer:
 
     def result(self) -> dict:
         return grounding_result(self.sums())
+
+
+# --------------------------------------------------------------------------- caption-set diversity (csrc/diversity.hip)
+# Definitions (what the kernel computes and tests/diversity_ref.py restates), for the n candidate captions of one clip -- n samples,
+# the n-best of a beam, the groups of a diverse beam, the draws of a stochastic beam -- of which the LIVE rows count:
+# * a caption's words are the ids before its first 0, as for BLEU above (L = 0 is possible, UNK is a word like any other).
+# * distinct_n, n = 1..4: the number of different n-grams of order n in the union of the live rows; total_n = sum over the live rows of
+#   max(0, L - n + 1); unique: the live rows whose word sequence equals that of no earlier live row; scored: live if live >= 2 else 0.
+# * Div_n of a clip = distinct_n / total_1 -- the set's WORD count is the denominator for every n, as in Shetty et al. 2017, Aneja et
+#   al. 2019 and Wang & Chan 2019; Div_1, Div_2 of a corpus: the mean over the clips with total_1 > 0.  Higher is more diverse.
+# * mBLEU: every live row as the candidate against the clip's other live rows as its references (ascending row order), the BLEU
+#   statistics and sentence BLEU above; mBLEU_k of a corpus = corpus_bleu of the statistics summed over all scored rows.  LOWER is more
+#   diverse.  A dead row and a row without another live row score nothing (all zeros).
+# * Unique = sum unique / sum live;  Sets: the clips counted.
+# * with the ground truth at hand: oracle_CIDEr = the mean over the clips with a live row of the best live row's CIDEr-D, mean_CIDEr =
+#   the mean over the live rows -- accuracy and diversity trade against each other, so they are reported side by side.
+# These are scores by word id over the dataset's tokens, NOT a toolkit's numbers: no tokenizer is applied, and mBLEU here is the
+# corpus-level BLEU of the summed statistics, where some papers average sentence BLEU instead.
+DIVERSITY_KEYS = ("Div_1", "Div_2", "mBLEU_1", "mBLEU_2", "mBLEU_3", "mBLEU_4", "Unique", "Sets")
+SET_STATS_COLUMNS = ("distinct_1", "distinct_2", "distinct_3", "distinct_4", "total_1", "total_2", "total_3", "total_4", "live", "unique",
+                     "scored", "reserved")
+
+
+def set_diversity(cand: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None) -> dict:
+    """cand [rows, T] int64 on the device, per_clip consecutive candidates per clip; live [rows] (None: every row counts).
+    -> dict(stats [clips, 12] int32 (SET_STATS_COLUMNS), mbleu_stats [rows, 10] int32, mbleu [rows, 4] fp32, div [clips, 2] fp32 =
+    distinct_1 / total_1, distinct_2 / total_1, 0 where total_1 = 0), all on the device: one launch and a division, no host read."""
+    from . import hip
+    from .cider import MAX_T, MAX_PER_CLIP
+    if cand.dim() != 2 or cand.shape[1] > MAX_T:
+        raise RuntimeError(f"metrics.set_diversity: cand {tuple(cand.shape)}; the kernel takes rows of at most T = {MAX_T} words")
+    if int(per_clip) > MAX_PER_CLIP:
+        raise RuntimeError(f"metrics.set_diversity: {int(per_clip)} candidates per clip; the kernel takes at most per_clip = {MAX_PER_CLIP}")
+    stats, mbleu_stats, mbleu = hip.caption_set_stats(cand.contiguous(), int(per_clip),
+                                                      None if live is None else live.to(torch.int32).contiguous())
+    total = stats[:, 4:5].to(torch.float32)                                 # (counts below 2^24: exact in fp32)
+    div = torch.where(total > 0, stats[:, 0:2].to(torch.float32) / total, 0.0)          # (0 / 0 is not selected)
+    return dict(stats=stats, mbleu_stats=mbleu_stats, mbleu=mbleu, div=div)
+
+
+class DiversityScorer:
+    """Set-diversity scores of a pass over the data without a host read per batch: add() runs the kernel on a batch's candidate sets and
+    adds to the int64 sums (the mBLEU statistics; unique, live, clips) and the fp64 sums (Div_1, Div_2 and the clips they are over; with
+    references the oracle and mean CIDEr-D sums and their counts) on the device; sums() reads them once; result() is fp64 on the host."""
+
+    def __init__(self):
+        self.int_sums = None           # [13] int64: the ten mBLEU statistics over the scored rows, sum unique, sum live, clips
+        self.float_sums = None         # [7] fp64: sum Div_1, sum Div_2, clips with words, sum best CIDEr-D, clips with a live row,
+        #                                sum CIDEr-D over the live rows, live rows scored against references
+
+    def _ensure(self, device):
+        if self.int_sums is None:
+            self.int_sums = torch.zeros(13, dtype=torch.int64, device=device)
+            self.float_sums = torch.zeros(7, dtype=torch.float64, device=device)
+
+    def add(self, seq: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None, refs: Optional[torch.Tensor] = None,
+            nref: Optional[torch.Tensor] = None, cider=None) -> dict:
+        """seq [rows, T] int64 on the device, per_clip consecutive candidates per clip, live [rows] or None; refs [clips, Rmax, T], nref
+        [clips] and cider (a cvc.cider.CiderD), all three or none: the ground truth for oracle_CIDEr / mean_CIDEr.  No host read.
+        -> set_diversity()'s dict of this batch (with "cider" [rows] fp32 when references are given)"""
+        given = [x is not None for x in (refs, nref, cider)]
+        if any(given) and not all(given):
+            raise RuntimeError("DiversityScorer.add: refs, nref and cider go together (the oracle needs all three)")
+        self._ensure(seq.device)
+        per_clip = int(per_clip)
+        out = set_diversity(seq, per_clip, live)
+        st = out["stats"].to(torch.int64)
+        clips = st.shape[0]
+        self.int_sums += torch.cat([out["mbleu_stats"].sum(0, dtype=torch.int64), st[:, 9].sum().reshape(1), st[:, 8].sum().reshape(1),
+                                    torch.full((1,), clips, dtype=torch.int64, device=seq.device)])
+        worded = st[:, 4] > 0
+        ratio = torch.where(worded.unsqueeze(1), st[:, 0:2].to(torch.float64) / st[:, 4:5].clamp(min=1).to(torch.float64),
+                            torch.zeros((), dtype=torch.float64, device=seq.device))
+        fl = [ratio[:, 0].sum(), ratio[:, 1].sum(), worded.sum().to(torch.float64)]
+        zero = torch.zeros((), dtype=torch.float64, device=seq.device)
+        if all(given):
+            score = cider.score(seq.contiguous(), refs.contiguous(), nref)
+            out["cider"] = score
+            on = torch.ones(clips, per_clip, dtype=torch.bool, device=seq.device) if live is None else (live.reshape(clips, per_clip) != 0)
+            s = score.to(torch.float64).view(clips, per_clip)
+            any_live = on.any(1)
+            best = torch.where(on, s, torch.full((), float("-inf"), dtype=torch.float64, device=seq.device)).max(1)[0]
+            fl += [torch.where(any_live, best, zero).sum(), any_live.sum().to(torch.float64), torch.where(on, s, zero).sum(),
+                   on.sum().to(torch.float64)]
+        else:
+            fl += [zero] * 4
+        self.float_sums += torch.stack(fl)
+        return out
+
+    def add_sums(self, int_sums, float_sums):
+        """precomputed sums (another rank's, or a test's), as sums() returns them"""
+        int_sums = torch.as_tensor(int_sums)
+        self._ensure(int_sums.device)
+        dev = self.int_sums.device
+        self.int_sums += int_sums.reshape(13).to(dev, torch.int64)
+        self.float_sums += torch.as_tensor(float_sums, dtype=torch.float64).reshape(7).to(dev)
+
+    def sums(self):
+        """-> (int_sums: list of 13 ints, float_sums: list of 7 floats) on the host: ONE read"""
+        if self.int_sums is None:
+            return [0] * 13, [0.0] * 7
+        flat = torch.cat([self.int_sums.to(torch.float64), self.float_sums]).tolist()        # (sums below 2^53 are exact in fp64)
+        return [int(x) for x in flat[:13]], flat[13:]
+
+    def result(self) -> dict:
+        return diversity_from_sums(*self.sums())
+
+
+def diversity_from_sums(int_sums, float_sums) -> dict:
+    """DiversityScorer.sums() -> the scores of DIVERSITY_KEYS (and oracle_CIDEr, mean_CIDEr when rows were scored against references),
+    fp64 on the host; empty sums give zeros"""
+    i, f = [int(x) for x in int_sums], [float(x) for x in float_sums]
+    bleu = corpus_bleu(np.asarray(i[:10], dtype=np.float64))
+    out = {"Div_1": f[0] / f[2] if f[2] > 0 else 0.0, "Div_2": f[1] / f[2] if f[2] > 0 else 0.0,
+           "mBLEU_1": float(bleu[0]), "mBLEU_2": float(bleu[1]), "mBLEU_3": float(bleu[2]), "mBLEU_4": float(bleu[3]),
+           "Unique": i[10] / i[11] if i[11] > 0 else 0.0, "Sets": i[12]}
+    if f[6] > 0:
+        out["oracle_CIDEr"] = f[3] / f[4] if f[4] > 0 else 0.0
+        out["mean_CIDEr"] = f[5] / f[6]
+    return out

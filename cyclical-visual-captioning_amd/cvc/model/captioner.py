@@ -762,8 +762,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         one.  "samples": sampling whatever sample_max says, with the model's consensus_samples / consensus_temperature /
         consensus_seed where sample_n / temperature / seed are not given, beam_size 1.  "beam": as True, beam_size > 1 required.
         The candidates are exactly what the same call returns with consensus=False and the same seed; self.last_consensus =
-        dict(candidates, pick, utility) keeps them (seq [B * n, T] / hypotheses [B, beam, T]) with the picks [B] and the utilities
-        [B * n], device tensors.
+        dict(candidates, pick, utility, live) keeps them (seq [B * n, T] / hypotheses [B, beam, T]) with the picks [B], the utilities
+        [B * n] and the live mask the selection used (None: every sample counts / [B, beam] bool: the score is finite), device tensors.
         stochastic_beam / stochastic_tau (arguments, else the model's attributes, read from opts; off by default): stochastic beam
         search with beam_size > 1 -- the engine is built with beam_history=True and stochastic=True, seeded once with seed (else the
         model's sample_seed); the result is a beam decode's (seq, att2_weights, None) of slot 0, an ordinary sample of q_tau, and
@@ -839,7 +839,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             self.last_stochastic["state"] = engine.rng_state.clone()     # the generator words this decode drew with (scst_loss(wor=))
         if mode is not None:
             seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table)
-            self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility)
+            self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility,
+                                       live=None if sampling else engine.consensus_live.view(engine.B, -1))
             return seq_c, att_c, logprob_c
         if sampling or (engine.constrained and beam == 1):
             return res[0].clone(), res[1].clone(), res[2].clone()

@@ -8,8 +8,10 @@ temperature) without UNK, written to <results_dir>/densecap-<val_split>-<id>_sam
   python -m cvc.sample --sample_n 16 --consensus ...                     (also the consensus pick and the samples' utilities)
   python -m cvc.sample --sample_n 5 --without_replacement ...            (5 DISTINCT captions per segment in draw order, by
                                                                           stochastic beam search, with each one's logq and G)
+  python -m cvc.sample --sample_n 5 --diversity ...                      (also every segment's Div-1, Div-2, mBLEU-4 and distinct
+                                                                          captions, and the split's summary with the oracle CIDEr-D)
 
---temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus / --without_replacement are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
+--temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus / --without_replacement / --diversity are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
 --resume with --load_best_score: the same checkpoint loading as an --inference_only evaluation).
 """
 from __future__ import annotations
@@ -34,7 +36,13 @@ def parse(argv=None):
     p.add_argument("--without_replacement", action="store_true",
                    help="draw the --sample_n captions of a segment without replacement (stochastic beam search at --temperature): "
                         "pairwise distinct, in draw order, with each one's logq and G; needs --sample_n > 1, refused with --top_k / --top_p")
+    p.add_argument("--diversity", action="store_true",
+                   help="add to every segment the diversity of its --sample_n captions (Div-1, Div-2, mBLEU-4, distinct captions; "
+                        "cvc.metrics.set_diversity) and to the file the split's summary with the oracle and mean CIDEr-D; needs "
+                        "--sample_n > 1")
     own, rest = p.parse_known_args(argv)
+    if own.diversity and own.sample_n < 2:
+        raise SystemExit("--diversity needs --sample_n > 1 (the diversity of a set of one caption says nothing)")
     if own.without_replacement and own.sample_n < 2:
         raise SystemExit("--without_replacement needs --sample_n > 1")
     if own.without_replacement and (own.top_k != 0 or own.top_p != 1.0):
@@ -56,7 +64,7 @@ def main(argv=None):
     own, rest = parse(argv)
     if "--inference_only" not in rest:
         rest = rest + ["--inference_only"]
-    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus, own.without_replacement))
+    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus, own.without_replacement, own.diversity))
 
 
 if __name__ == "__main__":

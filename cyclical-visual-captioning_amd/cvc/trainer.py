@@ -80,7 +80,8 @@ def _copy_into(static, b):
 
 
 class Trainer:
-    def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False):
+    def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False,
+                 val_diversity=False):
         self.opts = opts
         self.dataset = dataset
         self.model = model
@@ -92,6 +93,9 @@ class Trainer:
         # eval(): BLEU-1..4, ROUGE-L and CIDEr-D of the decoded captions against the batches' own references, on the device
         # (cvc.metrics.DeviceScorer); off: eval is what it was
         self.device_metrics = bool(device_metrics)
+        # eval(): the diversity of every clip's candidate set (cvc.metrics.DiversityScorer over model.last_consensus) next to the
+        # device metrics; off: eval is what it was
+        self.val_diversity = bool(val_diversity)
         self._val_cider = None        # cvc.cider.CiderD over the validation loader's captions, built at the first eval
         self._word_cls = None         # word id -> detection class (utils.word_class_table), built at the first eval that grounds
         self.device = next(model.parameters()).device
@@ -816,12 +820,25 @@ class Trainer:
         # the grounding scores of the generated captions (cvc.metrics.GroundingScorer): only with the device metrics AND
         # --eval_obj_grounding; the grounding file then is built from the kernel's picks
         grd_scorer = self._grounding_scorer() if (dev_scorer is not None and getattr(o, "eval_obj_grounding", False)) else None
+        div_scorer = None
+        if self.val_diversity:
+            if dev_scorer is None or getattr(core, "consensus", "off") == "off":
+                raise RuntimeError("Trainer.eval: val_diversity needs device_metrics=True and the model's consensus switch on (samples / "
+                                   "beam): the candidates it scores are those of the consensus selection")
+            from .metrics import DiversityScorer
+            div_scorer = DiversityScorer()
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
                 seq, att2_weights, _ = self._call(b, True)
                 if dev_scorer is not None:                  # the references scst_step_prepared scores against; no host read
                     T = seq.size(1)
                     dev_scorer.add(seq.contiguous(), b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32))
+                    if div_scorer is not None:              # the candidates the consensus pick was chosen among; no host read
+                        last = core.last_consensus
+                        cand = last["candidates"]
+                        per = cand.size(0) // seq.size(0) if cand.dim() == 2 else cand.size(1)
+                        div_scorer.add(cand.reshape(-1, cand.size(-1)), per, None if last.get("live") is None else last["live"].reshape(-1),
+                                       b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32), self._val_cider)
                 if getattr(o, "eval_obj_grounding", False):
                     assert o.beam_size == 1, 'only support beam_size is 1'
                     if grd_scorer is not None:
@@ -840,6 +857,9 @@ class Trainer:
             lang_stats = self._merged_device_metrics(dev_scorer)
         if grd_scorer is not None:
             lang_stats = {**lang_stats, **self._merged_grounding(grd_scorer)}
+        if div_scorer is not None:                          # ONE read per validation pass
+            res = self._merged_diversity(div_scorer)
+            lang_stats = {**lang_stats, **{k: res[k] for k in ("Div_1", "Div_2", "mBLEU_4", "Unique", "oracle_CIDEr") if k in res}}
         if getattr(o, "eval_obj_grounding_gt", False):        # (every rank: its shards are merged like the predictions)
             self._eval_ground_gt(epoch, tb_logger)
         self.submission_file = self.attn_file = None
@@ -880,6 +900,19 @@ class Trainer:
         dist.all_gather_object(parts, mine)
         stats = [sum(p[0][i] for p in parts) for i in range(10)]
         return result_from_sums(stats, *(sum(p[j] for p in parts) for j in (1, 2, 3)))
+
+    @staticmethod
+    def _merged_diversity(div_scorer):
+        """one host read of this rank's sums; with several ranks the sums are exchanged host-side and added on every rank, as
+        _merged_device_metrics does (more than one rank: untested)"""
+        import torch.distributed as dist
+        from .metrics import diversity_from_sums
+        mine = div_scorer.sums()
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return diversity_from_sums(*mine)
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        return diversity_from_sums([sum(p[0][i] for p in parts) for i in range(13)], [sum(p[1][i] for p in parts) for i in range(7)])
 
     def _grounding_scorer(self):
         """a fresh cvc.metrics.GroundingScorer; the word -> detection class table is built once, at the first eval"""
@@ -1012,7 +1045,7 @@ class Trainer:
         return stats
 
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
-               constraints: dict = None, consensus: bool = False, without_replacement: bool = False):
+               constraints: dict = None, consensus: bool = False, without_replacement: bool = False, diversity: bool = False):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
         without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise);
         top_k / top_p truncate that distribution (0 / 1.0 = off; the log-probs stay the model's, over the full vocabulary).
@@ -1029,13 +1062,25 @@ class Trainer:
         an ordinary sample.  "logprobs" is then each caption's model log-prob as the beam carries it (the same sum), and every entry
         also holds "logq": [n], the captions' log-probs under the sampling distribution q_tau, and "G": [n], their perturbed keys
         (non-increasing).  top_k / top_p are refused with it; the constraints and consensus work.
+        diversity=True (n > 1): every entry also holds "diversity": {"div1", "div2", "mbleu4", "unique"} of its n sentences
+        (cvc.metrics.set_diversity: distinct 1- and 2-grams over the set's word count, the corpus BLEU-4 of each sentence against the
+        others, the number of different sentences), and the file gains the top-level key "diversity": the split's summary
+        (cvc.metrics.DiversityScorer.result(), with oracle_CIDEr and mean_CIDEr against the validation references), which is also
+        logged and kept in self.sample_diversity.  Off: the file is what it was.
         Returns the path (None on the other ranks)."""
         model = getattr(self.model, "module", self.model)
+        n = int(n)
+        if diversity and n < 2:
+            raise RuntimeError(f"Trainer.sample: diversity is that of a set of n > 1 captions per segment, got n = {n}")
         model.eval()
         o, ds = self.opts, self.dataset
         timestamps = self._segment_timestamps()
         samples = defaultdict(list)
-        n = int(n)
+        div_scorer = None
+        if diversity:
+            from .metrics import DiversityScorer, corpus_bleu
+            div_scorer = DiversityScorer()
+            self._device_scorer()                           # (builds the validation captions' CIDEr-D table once)
         if without_replacement:
             if n < 2:
                 raise RuntimeError(f"Trainer.sample: without_replacement draws n > 1 distinct captions per segment, got n = {n}")
@@ -1062,6 +1107,14 @@ class Trainer:
                     utility, pick, _ = model.consensus_table.consensus(seq, n)
                     model.last_consensus = dict(candidates=seq, pick=pick, utility=utility)
                     picks, utils_ = pick.tolist(), utility.view(-1, n).tolist()
+                if diversity:                               # a stochastic beam's fillers (score -inf) are no captions
+                    live = torch.isfinite(draws["score"]).reshape(-1) if without_replacement else None
+                    T = seq.size(1)
+                    dv = div_scorer.add(seq.contiguous(), n, live, b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32),
+                                        self._val_cider)
+                    div_l = dv["div"].tolist()
+                    set_l = dv["stats"].tolist()
+                    mb_l = dv["mbleu_stats"].view(-1, n, 10).sum(1).tolist()
                 sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 # sequence log-prob: the steps up to and including the first EOS (word 0)
@@ -1078,8 +1131,15 @@ class Trainer:
                         samples[vid_idx][-1].update(logq=seq_lq[k * n:(k + 1) * n], G=seq_G[k * n:(k + 1) * n])
                     if consensus:
                         samples[vid_idx][-1].update(consensus=picks[k], utilities=utils_[k])
+                    if diversity:
+                        samples[vid_idx][-1]["diversity"] = {"div1": div_l[k][0], "div2": div_l[k][1],
+                                                             "mbleu4": float(corpus_bleu(mb_l[k])[3]), "unique": set_l[k][9]}
         samples, _ = gather_eval_outputs(samples, {})
         self.samples = samples
+        if diversity:
+            self.sample_diversity = self._merged_diversity(div_scorer)
+            samples = dict(samples)
+            samples["diversity"] = self.sample_diversity
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
             return None
         d = getattr(o, "results_dir", "results")
@@ -1087,6 +1147,8 @@ class Trainer:
         path = os.path.join(d, (stem or "densecap-%s-%s" % (o.val_split, o.id)) + "_samples.json")
         with open(path, "w") as f:
             json.dump(samples, f)
+        if diversity:
+            print("diversity of %d captions per segment: %s" % (n, json.dumps(self.sample_diversity)), flush=True)
         return path
 
     def _frame_boxes(self, ppls, weights):

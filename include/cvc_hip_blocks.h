@@ -633,6 +633,27 @@ int cvc_consensus_cider(const int64_t* cand, const int32_t* live, int rows, int 
                         const float* idf, int G, float idf_unseen, float sigma, float* utility, int32_t* pick, int64_t* best,
                         cvc_stream_t stream);
 
+/* ---- caption-set diversity: distinct n-grams of a clip's candidate set, every candidate's BLEU statistics against the set's other
+ * candidates (mBLEU), distinct captions; one launch (csrc/diversity.hip; cvc.metrics.set_diversity, DecodeEngine.set_diversity).
+ *   cand [rows, T] int64, per_clip, live [rows] int32 (nullable: every row is live) as cvc_consensus_cider; a caption's words as
+ *   cvc_caption_overlap: the ids BEFORE its first 0 (what stands behind it is ignored; all T ids without a 0; L = 0 is possible; UNK
+ *   is a word like any other).  "Live rows": the clip's rows with live != 0.  Every output is written for every row and clip.
+ *   set_stats [clips, 12] int32, exact:
+ *     0..3  distinct_n, n = 1..4: the number of different n-grams of order n in the union of the live rows
+ *     4..7  total_n = sum over the live rows of max(0, L - n + 1)  (total_1: the set's word count)
+ *     8     live: the live rows;   9  unique: the live rows whose word sequence equals that of no EARLIER live row of the clip
+ *     10    scored: live if live >= 2, else 0;   11  reserved, 0
+ *   mbleu_stats [rows, 10] int32, mbleu [rows, 4] fp32: the row as the candidate against the clip's other live rows as its
+ *     references, in ascending row order -- cvc_caption_overlap's stats layout (correct_1..4, guess_1..4, cand_len, ref_len) and
+ *     floating-point expressions: bit for bit what cvc_caption_overlap returns for that candidate and those references.  All zeros
+ *     for a dead row and for a row without another live row in its clip.
+ * One workgroup per clip; every caption's 4-word windows are built once and kept in LDS for the pairs.  No atomics, no workspace: a
+ * clip's outputs are bit-reproducible and independent of the other clips.  Launch only (no host read, no allocation): capturable
+ * in a HIP graph.
+ * Null pointers (but live), rows < 1, rows % per_clip != 0, per_clip < 1 or > 32, T < 1 or > 63: CVC_E_BADARG, before any launch. */
+int cvc_caption_set_stats(const int64_t* cand, const int32_t* live, int rows, int T, int per_clip, int32_t* set_stats,
+                          int32_t* mbleu_stats, float* mbleu, cvc_stream_t stream);
+
 /* ---- grounding F1 of generated captions: per object word the most attended proposal of every sampled frame, tested against the
  * clip's annotated boxes and counted per detection class, one launch (csrc/grounding.hip; cvc.metrics.grounding, Trainer.eval).
  *   seq [rows, T] int64: row r belongs to clip r / per_clip; its words are the ids before the first 0 (all T without one).
