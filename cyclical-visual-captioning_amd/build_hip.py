@@ -74,8 +74,10 @@ def up_to_date() -> bool:
 # there is a silent 2x; the entry covers every instantiation of the kernel template, fp32 forms included)
 # (mix.hip: the mixed selection block keeps a row's logits in registers, up to 32 per thread, next to the draw's and the given word's
 # bookkeeping -- a spill there is silent and slow)
+# (ensemble.hip: the combine kernel keeps a member's row and the accumulator in registers, two arrays of up to 32 per thread, and
+# indexes its by-value member table at run time -- neither may end up in scratch)
 NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",),
-                      "mix.hip": ("sample_select_kernel",)}
+                      "mix.hip": ("sample_select_kernel",), "ensemble.hip": ("ensemble_logprobs_kernel",)}
 
 
 def check_no_scratch(src: str, remarks: str):

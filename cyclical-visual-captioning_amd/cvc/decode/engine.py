@@ -35,6 +35,16 @@ def _capture_mode() -> str:
 class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
     """Binds weights + one batch of clip features to preallocated state and a launch list."""
     _warm = set()
+    _ensemble = None                 # an ensemble's member: True (the primary) or the primary engine (DecodeEngine._member)
+
+    @classmethod
+    def _member(cls, primary, *args, **options):
+        """Internal (cvc/decode/ensemble.py): an engine built as a member of an EnsembleEngine -- primary = None for the primary member,
+        else the primary engine whose words / parents this one reads.  What that changes is in __init__'s documentation."""
+        self = cls.__new__(cls)
+        self._ensemble = True if primary is None else primary
+        self.__init__(*args, **options)
+        return self
 
     def __init__(self, weights: DecodeWeights, feats: Dict[str, torch.Tensor], T: int, unk_idx: int, beam: int = 1,
                  inv_temp: float = 1.0, own_features: bool = False, path: str = "auto", gate_ksplit: Optional[bool] = None,
@@ -151,7 +161,14 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         (ping-pong like score); run() returns slot 0 (the beam engine's tuple, scores = sums of the model's log-probs in slot
         order), hypotheses() returns (seq, score, G, logq) in draw order, consensus() works as for any history beam (fillers are
         not live), and it composes with the five constraints.  Needs beam > 1 and beam_history=True; refused with beam_groups > 1,
-        diversity, length_penalty, force_n, a temperature (stochastic_tau is its own) and gsk / gate_ksplit / lang_ksx."""
+        diversity, length_penalty, force_n, a temperature (stochastic_tau is its own) and gsk / gate_ksplit / lang_ksx.
+        An engine built by DecodeEngine._member (cvc/decode/ensemble.py; internal) is a member of an EnsembleEngine: self._ensemble is True
+        on the primary member and the primary engine on a secondary one, which reads words and parents from that primary's buffers.  A
+        member runs every launch of its step but the selection: with beam = 1 its lists take the `given` form (finished logits or
+        K-slice slabs, the next word read from words[t + 1]), its word_select entries are placeholders (fn = None, args = the logit
+        source (parts, nparts, part_stride, bias)) that the ensemble replaces by one combine launch and one selection, no C-driver plan
+        is bound and the fused tail is off; only the primary advances the generator.  Every other engine: _ensemble is None, nothing
+        changes."""
         # every check that needs neither the batch nor the library, before a feature is read (cvc/decode/mode.py)
         m = self.mode = DecodeMode.resolve(
             T, getattr(weights, "V", None), beam=beam, path=path, gate_ksplit=gate_ksplit, gsk=gsk, embgate=embgate, lang_ksx=lang_ksx,
@@ -163,6 +180,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             if getattr(m, name) is not None:             # (inv_tau / stoch_inv_tau exist only in the modes that read them)
                 setattr(self, name, getattr(m, name))
         gsk, gate_ksplit, lang_ksx = m.gsk, m.gate_ksplit, m.lang_ksx     # the schedule requests as the mode leaves them
+        _ensemble = self._ensemble                       # (set by _member before this runs; None on every other engine)
+        if _ensemble is not None and self.beam == 1:
+            self.given = True                            # a member's step ends with its logits; the word comes from words[t + 1]
+        shared = _ensemble if isinstance(_ensemble, DecodeEngine) else None      # a secondary member: the primary's words / parents
         W = self.W = weights
         self.unk = int(unk_idx)
         fc, conv, pconv = feats["fc_feats"], feats["conv_feats"], feats["p_conv_feats"]
@@ -253,7 +274,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         self.emb = z(rows, W.E)            # relu(Emb[word_t]), written by the word-selection kernel of step t-1
         self.top2_part = z((V + 31) // 32, 64, 6)
         self.att_steps = z(self.T, rows, N)                       # post-softmax region attention per step
-        self.words = torch.zeros(self.T + 1, rows, dtype=torch.int64, device=dev)   # words[0] = BOS = 0
+        self.words = torch.zeros(self.T + 1, rows, dtype=torch.int64, device=dev) if shared is None else shared.words   # words[0] = BOS = 0
         self.logprob = z(self.T, rows)
         # fc is per clip; beams of a clip read the same row through a row-gather index
         self.fc = fc
@@ -282,7 +303,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         if self.beam > 1:
             self.score = z(2, rows)
             self.done = torch.zeros(2, rows, dtype=torch.uint8, device=dev)
-            self.parent = torch.zeros(self.T, rows, dtype=torch.int64, device=dev)
+            self.parent = torch.zeros(self.T, rows, dtype=torch.int64, device=dev) if shared is None else shared.parent
             self.bt_seq = torch.zeros(self.B, self.T, dtype=torch.int64, device=dev)      # the returned hypothesis (cvc_beam_backtrack: rank 0; ranked engines: the best by norm)
             self.bt_att = z(self.B, self.T, N)
             self.gather_tmp = [z(rows, R) for _ in range(4)]
@@ -330,7 +351,7 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self.tail_keys = torch.zeros(self.T * 64 * 5, dtype=torch.int64, device=dev)
             self.tail_ms = z(self.T, (V + 31) // 32, 64, 2)
         self._launches = self._build_launches()
-        if driver and not self.given and not self.bf16w and not self.beam_hist and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
+        if driver and _ensemble is None and not self.given and not self.bf16w and not self.beam_hist and (self.tile or (self.packed and not (self.ks_att or self.ks_lang))):
             self._bind_driver()
 
     # ------------------------------------------------------------------ C-ABI decode driver (csrc/decode_driver.hip)
@@ -572,14 +593,18 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
 
     def _build_launches(self):
         out = self._build_packed() if self.packed else (self._build_tile() if self.tile else self._build())
-        if self.sampling or self.stoch:  # first entry: a fresh `call` for every decode (and every replay of a captured graph)
+        if (self.sampling or self.stoch) and not isinstance(self._ensemble, DecodeEngine):
+            # first entry: a fresh `call` for every decode (and every replay of a captured graph); an ensemble: the primary's only
             out.insert(0, ("sample_advance", hip.lib().cvc_sample_advance, (self.rng.data_ptr(),)))
         return out
 
-    def _word_select_sampled(self, t, parts, nparts, part_stride, bias):
+    def _word_select_sampled(self, t, parts, nparts, part_stride, bias, real=False):
         """The sampling paths' word_select launch of step t over logits parts[0] + ... (+ bias): the plain block, or the
         truncating one (top_k / top_p are launch constants: they live in the captured graph); the forced mode: the block that
-        scores the given word words[t + 1] and writes none."""
+        scores the given word words[t + 1] and writes none.  An ensemble's member: the placeholder that names the logit source
+        (real=True: the block itself, what the ensemble asks its primary for over the combined rows)."""
+        if self._ensemble is not None and not real:
+            return ("word_select", None, (parts, nparts, part_stride, bias))
         L, rows, V = hip.lib(), self.rows, self.W.V
         if self.forced:
             return ("word_select", L.cvc_forced_select_parts, (parts, nparts, part_stride, bias, rows, V, self.words[t + 1].data_ptr(), 1,
@@ -601,10 +626,12 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         return ("word_select", L.cvc_sample_select_trunc_parts, head + (self.top_k, self.top_p) + tail +
                 (self.cutoff[t].data_ptr(), self.kept[t].data_ptr()))
 
-    def _word_select_beam(self, t, parts, nparts, part_stride, bias):
+    def _word_select_beam(self, t, parts, nparts, part_stride, bias, real=False):
         """A beam path's word_select launch of step t over logits parts[0] + ... (+ bias): the plain block, or with beam_history
         the block that carries the hypotheses' histories (and applies the constraints to them; t and the rules are launch
-        constants)."""
+        constants).  An ensemble's member: the placeholder, as in _word_select_sampled."""
+        if self._ensemble is not None and not real:
+            return ("word_select", None, (parts, nparts, part_stride, bias))
         L, B, beam, V = hip.lib(), self.B, self.beam, self.W.V
         srd, swr = t & 1, (t + 1) & 1
         head = (parts, nparts, part_stride, bias, self.score[srd].data_ptr(), self.done[srd].data_ptr(), B, beam, V, self.unk)
@@ -721,6 +748,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         else:
             self._reset()
             self._run_launches()
+        self._finish_beam()
+
+    def _finish_beam(self):
+        """What a beam decode enqueues behind its T steps: the returned hypothesis (and, on a ranked engine, the final ranking)."""
         if self.beam > 1 and self.ranked:                  # the final ranking, then the best hypothesis by norm: two launches
             L, T = hip.lib(), self.T
             if self.forcing:
@@ -799,6 +830,10 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
             self._run_once()
             if self.lang_ksx and not self._ksx_checked and self.check_ksx():
                 self._run_once()                           # the fallback's results
+        return self._result()
+
+    def _result(self):
+        """run()'s tuple: views of the engine-owned buffers the last decode filled."""
         if self.forced:
             return self.words[1:].t(), self.att_steps.permute(1, 0, 2), self.logprob.t(), self.rank.t()
         if self.sampling or (self.constrained and self.beam == 1):

@@ -81,7 +81,7 @@ class RingPath:
             else:
                 out.append(("logits", L.cvc_linear_fwd, (seg_o, 1, ptr(W.b_o), None, rows, V, ptr(self.logits), V)))
                 srd, swr = t & 1, (t + 1) & 1
-                if self.beam_hist:
+                if self.beam_hist or self._ensemble is not None:      # (an ensemble's member: the placeholder over its logits)
                     out.append(self._word_select_beam(t, ptr(self.logits), 1, 0, None))
                 else:
                     out.append(("word_select", L.cvc_beam_select, (ptr(self.logits), ptr(self.score[srd]), ptr(self.done[srd]), B,

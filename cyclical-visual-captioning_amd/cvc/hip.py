@@ -13,6 +13,7 @@ import math
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +108,14 @@ class Constraint(C.Structure):
     """cvc_constraint of include/cvc_hip_blocks.h: the rules of cvc_constrained_select_parts (the two lists are device memory)."""
     _fields_ = [("no_repeat_ngram", C.c_int), ("no_immediate_repeat", C.c_int), ("min_len", C.c_int), ("nban", C.c_int),
                 ("ban", C.c_void_p), ("bad_end", C.c_void_p), ("nbad", C.c_int)]
+
+
+class EnsembleSrc(C.Structure):
+    """cvc_ensemble_src of include/cvc_hip_blocks.h: one member's logits as a selection block takes them (device pointers)."""
+    _fields_ = [("parts", C.c_void_p), ("nparts", C.c_int), ("part_stride", C.c_longlong), ("bias", C.c_void_p)]
+
+
+ENSEMBLE_MAX = 8                 # CVC_ENSEMBLE_MAX
 
 
 class TrainLoop(C.Structure):
@@ -246,6 +255,8 @@ SIGNATURES = {
     # scheduled sampling: draw, coin, drawn-or-given word (csrc/mix.hip; building block)
     "cvc_mixed_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P],
     "cvc_forced_select_parts": [_P, _I, _LL, _P, _I, _I, _P, _I, _P, _P, _P],
+    "cvc_ensemble_logprobs": [C.POINTER(EnsembleSrc), _I, C.POINTER(_F), _I, _I, _I, _P, _I, _P],
+    "cvc_ensemble_mix": [C.POINTER(_P), _I, C.POINTER(_F), _LL, _P, _P],
     "cvc_constrained_select_parts": [_P, _I, _LL, _P, _I, _I, _I, _F, _I, _F, _P, _I, _P, _I, _P, _P, _P, _P, _LL, C.POINTER(Constraint),
                                      _P, _P],
     "cvc_beam_select_hist_parts": [_P, _I, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _LL, C.POINTER(Constraint), _P, _P, _P, _P, _P,
@@ -336,7 +347,7 @@ BLOCKS = {
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
     "cvc_caption_set_stats", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
-    "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd"}
+    "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -543,6 +554,25 @@ def _dev(t: Optional[torch.Tensor], dtype=torch.float32, name="tensor") -> Optio
     if not t.is_contiguous():
         raise RuntimeError(f"cvc.hip: {name} must be contiguous")
     return t.data_ptr()
+
+
+def ensemble_log_weights(weights, M: int) -> np.ndarray:
+    """The log-weights cvc_ensemble_logprobs / cvc_ensemble_mix take (fp32 [M]): None = uniform, else M finite numbers > 0,
+    normalised in fp64 to sum to 1, the log rounded once to fp32.  Anything else raises RuntimeError."""
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= ENSEMBLE_MAX:
+        raise RuntimeError(f"ensemble_log_weights: an ensemble has 1 .. {ENSEMBLE_MAX} members, got {M!r}")
+    if weights is None:
+        w = np.ones(M, dtype=np.float64)
+    else:
+        try:
+            w = np.array([float(v) for v in weights], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise RuntimeError(f"ensemble_log_weights: the weights must be {M} numbers, got {weights!r}") from None
+        if w.shape != (M,):
+            raise RuntimeError(f"ensemble_log_weights: {M} members need {M} weights, got {len(w)}")
+        if not np.all(np.isfinite(w)) or not np.all(w > 0):
+            raise RuntimeError(f"ensemble_log_weights: every weight must be a finite number > 0, got {list(w)}")
+    return np.log(w / w.sum()).astype(np.float32)
 
 
 def _mask(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:

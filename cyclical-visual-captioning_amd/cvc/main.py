@@ -123,7 +123,64 @@ def build_parser():
     parser.add_argument("--val_diversity", action="store_true", default=argparse.SUPPRESS,
                         help="score the diversity of every clip's candidate set in validation (Div_1, Div_2, mBLEU_4, Unique and the "
                              "oracle CIDEr-D, on the GPU); needs --val_metrics device and a candidate set, i.e. --consensus samples|beam")
+    # ensemble decoding (cvc.model.CaptionEnsemble): off by default and then no key in the options, no launch changes
+    parser.add_argument("--ensemble", type=str, default=argparse.SUPPRESS,
+                        help="comma-separated checkpoint files (state dicts of models built from the same options): evaluation, "
+                             "cvc.sample and cvc.score decode with the resumed checkpoint (member 0) and these together, one word "
+                             "choice per step from the combined distribution; needs --resume True.  Training steps never see it")
+    parser.add_argument("--ensemble_weights", type=str, default=argparse.SUPPRESS,
+                        help="comma-separated positive weights, one per member (the resumed checkpoint first); default: uniform")
+    parser.add_argument("--ensemble_combine", choices=("prob", "logprob"), default=argparse.SUPPRESS,
+                        help="prob: the weighted mean of the members' probabilities (default); logprob: of their log-probs")
     return parser
+
+
+def check_ensemble_flags(opt):
+    """--ensemble and its two companions -> (checkpoint paths, weights or None, combine), or None with the flag absent.  Ends the run
+    with a message, before any set-up: no --resume True, a weight count that does not match, malformed weights, a missing file, a
+    companion flag without --ensemble."""
+    spec = getattr(opt, "ensemble", None)
+    if spec is None:
+        if hasattr(opt, "ensemble_weights") or hasattr(opt, "ensemble_combine"):
+            raise SystemExit("--ensemble_weights / --ensemble_combine need --ensemble")
+        return None
+    paths = [p.strip() for p in spec.split(",") if p.strip()]
+    if not paths:
+        raise SystemExit("--ensemble names no checkpoint file")
+    if not opt.resume:
+        raise SystemExit("--ensemble needs --resume True: the resumed checkpoint is member 0 of the ensemble")
+    if getattr(opt, "eval_obj_grounding_gt", False):
+        raise SystemExit("--ensemble and --eval_obj_grounding_gt exclude each other: the grounding on GT sentences reads one model's "
+                         "frame-masked attention and grounder")
+    weights = None
+    if hasattr(opt, "ensemble_weights"):
+        try:
+            weights = [float(w) for w in opt.ensemble_weights.split(",")]
+        except ValueError:
+            raise SystemExit("--ensemble_weights must be comma-separated numbers, got %r" % (opt.ensemble_weights,)) from None
+        if len(weights) != len(paths) + 1:
+            raise SystemExit("--ensemble_weights has %d weights for %d members (the resumed checkpoint and %d of --ensemble)"
+                             % (len(weights), len(paths) + 1, len(paths)))
+        if not all(np.isfinite(w) and w > 0 for w in weights):
+            raise SystemExit("--ensemble_weights must be finite numbers > 0, got %r" % (opt.ensemble_weights,))
+    if len(paths) + 1 > 8:
+        raise SystemExit("--ensemble: an ensemble has at most 8 members, got %d" % (len(paths) + 1))
+    for p in paths:
+        if not os.path.isfile(p):
+            raise SystemExit("--ensemble: no such checkpoint file: %s" % p)
+    return paths, weights, getattr(opt, "ensemble_combine", "prob")
+
+
+def check_member_state(path, state, reference):
+    """an --ensemble member's state dict against the resumed model's: a vocabulary of another size (the embedding, the vocabulary
+    head) or any other tensor of another shape ends the run with a message"""
+    for k in ("embed.0.weight", "logit.weight"):
+        if k in state and k in reference and tuple(state[k].shape) != tuple(reference[k].shape):
+            raise SystemExit("--ensemble: %s has a different vocabulary: %s is %s, the resumed checkpoint's %s (the members choose one "
+                             "word from one vocabulary)" % (path, k, tuple(state[k].shape), tuple(reference[k].shape)))
+    bad = sorted(k for k in reference if k not in state or tuple(state[k].shape) != tuple(reference[k].shape))
+    if bad:
+        raise SystemExit("--ensemble: %s does not fit a model built from these options: %s" % (path, ", ".join(bad[:4])))
 
 
 def check_val_diversity_flag(opt):
@@ -165,6 +222,10 @@ def main(argv=None, sample=None, score=None):
     check_val_diversity_flag(opt)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
+    ensemble = check_ensemble_flags(opt)
+    if ensemble is not None and score is not None and score.get("ground_gt"):
+        raise SystemExit("--ensemble and --ground_gt exclude each other: the grounding on GT sentences reads one model's frame-masked "
+                         "attention and grounder")
     opt.test_mode = opt.val_split in ["testing", "hidden_test"]                       # reference main.py:57
     rank, world, local_rank = init_from_env(opt.dist_backend) if "RANK" in os.environ else (0, 1, 0)
     device = torch.device("cuda", local_rank) if torch.cuda.is_available() else None
@@ -274,6 +335,18 @@ def main(argv=None, sample=None, score=None):
     reducer = GradReducer(model.named_parameters(), comm=comm)
     trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device",
                       **(dict(val_diversity=True) if getattr(opt, "val_diversity", False) else {}))
+    if ensemble is not None:                                   # evaluation, cvc.sample and cvc.score decode through the ensemble
+        from .model.ensemble import CaptionEnsemble
+        members = [getattr(model, "module", model)]
+        for p in ensemble[0]:
+            state = torch.load(p, map_location=device)
+            check_member_state(p, state, members[0].state_dict())
+            member = build_model(opt, device)
+            member.load_state_dict(state)
+            members.append(getattr(member, "module", member))
+        trainer.ensemble = CaptionEnsemble(members, weights=ensemble[1], combine=ensemble[2])
+        if rank == 0:
+            print("ensemble of %d checkpoints (%s)" % (len(members), ensemble[2]))
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:

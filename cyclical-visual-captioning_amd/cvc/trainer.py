@@ -80,6 +80,10 @@ def _copy_into(static, b):
 
 
 class Trainer:
+    # a cvc.model.CaptionEnsemble over the model (member 0) and further checkpoints, set by whoever builds the trainer (cvc.main
+    # --ensemble): eval(), sample() and score() then decode through it; training steps never see it.  None: every decode is the model's
+    ensemble = None
+
     def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False,
                  val_diversity=False):
         self.opts = opts
@@ -192,7 +196,14 @@ class Trainer:
                     gt_bboxs=to(bboxs), mask_bboxs=to(box_mask), ppls_feat=to(region_feat), mask_frms=to(frm_mask),
                     sample_idx=to(sample_idx).type_as(to(iseq)), pnt_mask=pnt_mask, seg_id=seg_id)
 
+    def _decoder(self):
+        """who decodes in eval() / sample() / score(): the ensemble when one is set, else the model itself"""
+        return self.ensemble if self.ensemble is not None else getattr(self.model, "module", self.model)
+
     def _call(self, b, lang_eval=False, **kw):
+        if lang_eval and self.ensemble is not None and not kw.get("teacher_forcing", False):
+            return self.ensemble._sample(b["segs_feat"], b["input_seqs"], b["ppls"], b["gt_seqs"], b["num"], b["mask_bboxs"], b["gt_bboxs"],
+                                         b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"])
         return self.model(b["segs_feat"], b["input_seqs"], b["gt_seqs"], b["num"], b["ppls"], b["gt_bboxs"], b["mask_bboxs"],
                           b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"], lang_eval, **kw)
 
@@ -808,7 +819,8 @@ class Trainer:
         candidates (model._sample), with that candidate's attention rows: the densecap file, the device metrics and the grounding
         all see the picked caption."""
         self.model.eval()
-        core = getattr(self.model, "module", self.model)
+        core = self._decoder()
+        core.eval()
         if getattr(core, "consensus", "off") != "off":
             self._consensus_table(core)
         predictions = defaultdict(list)
@@ -971,7 +983,7 @@ class Trainer:
         densecap-<val_split>-<id>):  {video: [{"segment", "timestamp", "logprob": sum of the caption's log-probs over its masked
         steps, "words": the number of those steps, "top1": how many of them have the given word as the model's arg-max}]}
         Returns {"ppl": exp(-sum logprob / sum words), "top1": sum top1 / sum words} over the first caption of every segment."""
-        model = getattr(self.model, "module", self.model)
+        model = self._decoder()
         o = self.opts
         timestamps = self._segment_timestamps()
         scores = defaultdict(list)
@@ -1005,7 +1017,7 @@ class Trainer:
         of the word's boxes (roi_labels).  Writes attn-gt-sent-results-<split>-<id>.json and grd-gt-sent-results-<split>-<id>.json
         (write_grounding_json's layout, 'eval_mode': 'GT'; a stem replaces the first part of both names) and returns the two
         accuracies, their per-class means and the number of annotated object words."""
-        model = getattr(self.model, "module", self.model)
+        model = self._decoder()                     # (an ensemble refuses grounding=True: the frame-masked scores are one member's)
         o = self.opts
         records = defaultdict(list)
         grd_att, grd_grd = defaultdict(dict), defaultdict(dict)
@@ -1068,7 +1080,7 @@ class Trainer:
         (cvc.metrics.DiversityScorer.result(), with oracle_CIDEr and mean_CIDEr against the validation references), which is also
         logged and kept in self.sample_diversity.  Off: the file is what it was.
         Returns the path (None on the other ranks)."""
-        model = getattr(self.model, "module", self.model)
+        model = self._decoder()
         n = int(n)
         if diversity and n < 2:
             raise RuntimeError(f"Trainer.sample: diversity is that of a set of n > 1 captions per segment, got n = {n}")

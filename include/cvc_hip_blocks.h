@@ -734,6 +734,26 @@ int cvc_vocab_nll_ent_bwd(const float* logits, const float* lse, const int64_t* 
                           const float* row_ent, const float* g, int M, int V, float eps, float beta, float* d_logits,
                           cvc_stream_t stream);
 
+/* Ensemble decoding (csrc/ensemble.hip; row loader, argument checks and NC / VEC choice of csrc/select_row.h): M members' logits ->
+ * one [rows, V] matrix of combined log-probs, one workgroup per row; the selection block of the step then runs on `out` with
+ * nparts = 1, bias = NULL.  src (HOST memory, M descriptors, copied into the kernel's arguments): member m's logits are
+ * parts[0][r, :] + ... + parts[nparts-1][r, :] (+ bias) in the order of cvc_tile_linear_finish -- the bits that member's own selection
+ * block sees; nparts and bias may differ between members.  logw (HOST memory, M floats): the log of the members' weights.
+ *   lse_m[r]  = logsumexp_v x_m[r, v];   a_m[v] = (x_m[r, v] - lse_m) + logw[m]
+ *   geometric == 0: out[r, v] = log sum_m w_m p_m(v), a streaming log-sum-exp over the members in index order (acc_0 = a_0, acc_m =
+ *                   fmaxf(acc, a_m) + log1pf(expf(-fabsf(acc - a_m)))): finite for words far below every member's top, normalised
+ *   geometric == 1: out[r, v] = sum_m expf(logw[m]) * (x_m[r, v] - lse_m), unnormalised (product of experts)
+ * M == 1, logw = {0}: the row log-softmax.  Columns >= V of out are not written.  fp32, fixed order, no workspace, no atomics:
+ * capturable, bitwise deterministic.  1 <= M <= CVC_ENSEMBLE_MAX, V <= 8192, rows * V < 2^32 (CVC_E_TOOBIG as the selection blocks);
+ * NULL pointers, M out of range, ld_out < V, a non-finite logw, a member that fails the selection blocks' checks: CVC_E_BADARG. */
+#define CVC_ENSEMBLE_MAX 8
+typedef struct { const float* parts; int nparts; long long part_stride; const float* bias; } cvc_ensemble_src;
+int cvc_ensemble_logprobs(const cvc_ensemble_src* src, int M, const float* logw, int geometric, int rows, int V, float* out,
+                          int ld_out, cvc_stream_t stream);
+/* out[i] = sum_m expf(logw[m]) * src[m][i], i < n, members in index order, fp32 (the ensemble's region attention).  src: HOST array
+ * of M device pointers, logw: HOST memory; both travel in the kernel's arguments.  out may not alias a source other than src[0]. */
+int cvc_ensemble_mix(const float* const* src, int M, const float* logw, long long n, float* out, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
