@@ -76,8 +76,10 @@ def up_to_date() -> bool:
 # bookkeeping -- a spill there is silent and slow)
 # (ensemble.hip: the combine kernel keeps a member's row and the accumulator in registers, two arrays of up to 32 per thread, and
 # indexes its by-value member table at run time -- neither may end up in scratch)
+# (distill.hip: the soft-target criterion keeps the student's and the teacher's row in registers, two arrays of up to 32 per thread)
 NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",),
-                      "mix.hip": ("sample_select_kernel",), "ensemble.hip": ("ensemble_logprobs_kernel",)}
+                      "mix.hip": ("sample_select_kernel",), "ensemble.hip": ("ensemble_logprobs_kernel",),
+                      "distill.hip": ("vocab_kd_fwd_kernel", "vocab_kd_bwd_kernel")}
 
 
 def check_no_scratch(src: str, remarks: str):

@@ -76,9 +76,10 @@ class EnsembleOptions:
     logw: Tuple[float, ...]             # fp32 values (hip.ensemble_log_weights)
     mode: DecodeMode
     engine_options: Tuple               # the keywords every member's DecodeEngine is built with, sorted (key, value) pairs
+    keep_rows: bool = False             # forced mode: the combined rows of every step are kept ([T, rows, V]; a teacher's soft targets)
 
     @classmethod
-    def resolve(cls, M, T, V, member_weights=None, combine="prob", **options) -> "EnsembleOptions":
+    def resolve(cls, M, T, V, member_weights=None, combine="prob", keep_rows=False, **options) -> "EnsembleOptions":
         if isinstance(M, bool) or not isinstance(M, int) or not 1 <= M <= hip.ENSEMBLE_MAX:
             raise RuntimeError(f"EnsembleEngine: an ensemble has 1 .. {hip.ENSEMBLE_MAX} members, got {M!r}")
         if combine not in COMBINES:
@@ -101,8 +102,13 @@ class EnsembleOptions:
             raise RuntimeError('EnsembleEngine: tail="fused" is refused: the fused tail selects inside the member\'s own head, an '
                                "ensemble selects once over the combined rows")
         mode = DecodeMode.resolve(T, V, **{k: v for k, v in options.items() if k in _MODE_OPTIONS})
+        if not isinstance(keep_rows, bool):
+            raise RuntimeError(f"EnsembleEngine: keep_rows must be a bool, got {keep_rows!r}")
+        if keep_rows and not mode.forced:
+            raise RuntimeError("EnsembleEngine: keep_rows=True is refused outside the forced mode (forced_n): the kept rows are a "
+                               "teacher's distributions along GIVEN captions; a decode that chooses its own words keeps the last step's only")
         return cls(M=M, combine=combine, geometric=combine == "logprob", logw=tuple(float(v) for v in logw), mode=mode,
-                   engine_options=tuple(sorted(options.items(), key=lambda kv: kv[0])))
+                   engine_options=tuple(sorted(options.items(), key=lambda kv: kv[0])), keep_rows=keep_rows)
 
 
 class EnsembleEngine:
@@ -111,13 +117,17 @@ class EnsembleEngine:
     mode: rank under the combined distribution), the region attention is sum_m w_m att_m (member order, fp32, on the device inside
     the decode: cvc_ensemble_mix into the primary's att_steps), a beam backtracks over that buffer.  hypotheses / candidates /
     consensus / set_diversity / seed / rng_state / load_force_words are the primary member's, over the buffers the ensemble's
-    selection filled.  M = 1: the single model through the combine launch."""
+    selection filled.  M = 1: the single model through the combine launch.
+    keep_rows=True (forced mode only): `combined` is [T, rows, V] and step t's combine launch and selection use combined[t] -- the
+    ensemble's next-word distribution at every position of the given captions, in the t-major row order of the training loops' head
+    (word-level distillation); nothing else in the launch list changes, so log-probs, ranks and attention keep their bits."""
     _warm = set()
 
-    def __init__(self, members, T: int, unk_idx: int, member_weights=None, combine: str = "prob", **options):
+    def __init__(self, members, T: int, unk_idx: int, member_weights=None, combine: str = "prob", keep_rows: bool = False, **options):
         members = list(members)
         V = getattr(members[0][0], "V", None) if members else None
-        o = self.options = EnsembleOptions.resolve(len(members), T, V, member_weights, combine, **options)
+        o = self.options = EnsembleOptions.resolve(len(members), T, V, member_weights, combine, keep_rows=keep_rows, **options)
+        self.keep_rows = o.keep_rows
         self.M, self.combine, self.mode = o.M, o.combine, o.mode
         self.logw = (C.c_float * o.M)(*o.logw)
         kw = dict(o.engine_options)
@@ -132,7 +142,8 @@ class EnsembleEngine:
             self.members.append(DecodeEngine._member(self.members[0] if m else None, w, f, T, unk_idx, **kw))
         p = self.primary = self.members[0]
         self.T, self.rows, self.V = p.T, p.rows, p.W.V
-        self.combined = torch.zeros(self.rows, self.V, device=pool0.device, dtype=torch.float32)     # the rows the selection reads
+        # the rows the selection reads (keep_rows: one [rows, V] matrix per step)
+        self.combined = torch.zeros(*((self.T,) if self.keep_rows else ()), self.rows, self.V, device=pool0.device, dtype=torch.float32)
         self.att_src = (C.c_void_p * o.M)(*(e.att_steps.data_ptr() for e in self.members))
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._keep: List = []
@@ -146,6 +157,9 @@ class EnsembleEngine:
 
     # ------------------------------------------------------------------ launch list
 
+    def _rows_ptr(self, t) -> int:
+        return (self.combined[t] if self.keep_rows else self.combined).data_ptr()
+
     def _combine_entry(self, t, selects):
         src = (hip.EnsembleSrc * self.M)()
         for m, (_, fn, args) in enumerate(selects):
@@ -154,10 +168,10 @@ class EnsembleEngine:
             src[m] = hip.EnsembleSrc(*args)
         self._keep.append(src)
         return ("ensemble_combine", hip.lib().cvc_ensemble_logprobs, (src, self.M, self.logw, int(self.options.geometric), self.rows, self.V,
-                                                                     self.combined.data_ptr(), self.V))
+                                                                     self._rows_ptr(t), self.V))
 
     def _select_entry(self, t):
-        p, comb = self.primary, self.combined.data_ptr()
+        p, comb = self.primary, self._rows_ptr(t)
         if p.beam > 1:
             return p._word_select_beam(t, comb, 1, 0, None, real=True)
         if p.sampling or p.forced or p.constrained:

@@ -276,6 +276,58 @@ class _VocabHeadNLLEnt(torch.autograd.Function):
         return d_x, d_w, d_b, None, None, None, None, None, None
 
 
+class _VocabHeadNLLKD(torch.autograd.Function):
+    """_VocabHeadNLL against a dense teacher row mixed with the one-hot loss (cvc_vocab_head_nll_kd_fwd, csrc/distill.hip): pre is the
+    mixed loss's gradient, so the backward is _VocabHeadNLL's; two more results without a graph, the unmixed NLL sum and KD sum.  The
+    teacher rows get no gradient."""
+
+    @staticmethod
+    def compute(x, weight, bias, target, w, teacher, row_map, alpha, tau):
+        """-> (loss [1], argmax [M], pre [M, V], unmixed NLL sum [1], 0.0, unmixed KD sum [1], None, alpha, tau)"""
+        parts = hip.tile_mm(_rows(x), hip.weight_operand(weight), parts_only=True)
+        loss, amax, pre, nll, kd = hip.vocab_head_nll_kd_fwd(parts, bias, target.contiguous(), w.contiguous(), teacher, alpha, tau, row_map)
+        return loss, amax, pre, nll, 0.0, kd, None, alpha, tau
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, target, w, teacher, row_map, done, alpha, tau):
+        x = _rows(x)
+        res = done if done is not None else _VocabHeadNLLKD.compute(x, weight, bias, target, w, teacher, row_map, alpha, tau)
+        loss, amax, pre, nll, kd = res[0], res[1], res[2], res[3], res[5]
+        ctx.save_for_backward(weight, bias, x, pre)
+        ctx.has_bias = bias is not None
+        ctx.key = ("linear", weight.data_ptr())
+        if weight.requires_grad:
+            _BATCHER.note_use(ctx.key)
+        ctx.mark_non_differentiable(amax, nll, kd)
+        return loss, amax, nll, kd
+
+    @staticmethod
+    def backward(ctx, g, _g_amax, _g_nll, _g_kd):
+        weight, bias, x, pre = ctx.saved_tensors
+        dy = hip.scale_by_scalar(pre, g.contiguous().reshape(1))
+        ni = ctx.needs_input_grad
+        d_w, d_b, d_x = _linear_backward(ctx, weight, bias, [x], dy, (ni[1], ni[2], ni[0]))
+        return d_x, d_w, d_b, None, None, None, None, None, None, None
+
+
+def _distill_args(what, distill, return_kd, rows, V, eps, entropy_beta, return_entropy):
+    """-> None (today's launches) or (teacher [R, V], alpha, tau, row_map); distillation beside label smoothing or the entropy term is
+    refused: the soft target replaces both"""
+    if distill is None:
+        if return_kd:
+            raise ValueError(f"{what}: return_kd needs distill=(teacher_rows, alpha, tau)")
+        return None
+    if eps != 0.0 or entropy_beta is not None or return_entropy:
+        raise ValueError(f"{what}: distill cannot be combined with label_smoothing > 0 or entropy_beta (the teacher's row is the target "
+                         "distribution)")
+    return hip.check_distill(distill, rows, V, what)
+
+
+def _done_kd(done):
+    """the (alpha, tau) a `done` was made with (None: made without a teacher)"""
+    return (done[7], done[8]) if done is not None and len(done) > 7 else None
+
+
 def _entropy_args(what, entropy_beta, entropy_weight, return_entropy, rows):
     """-> None (today's launches: no coefficient and no entropy asked for) or (beta, m [rows]); beta = 0 reports the entropy and
     changes nothing else"""
@@ -305,7 +357,7 @@ def _refuse_done(done, eps, beta):
 
 def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, done=None, label_smoothing: float = 0.0,
                    return_nll: bool = False, entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None,
-                   return_entropy: bool = False):
+                   return_entropy: bool = False, distill=None, return_kd: bool = False):
     """-> (sum_m w[m] * -log_softmax(x W^T + b)[m, target[m]] as a [1] tensor, argmax over V per row [M] int64); x [M, K]
     done: vocab_head_nll_compute()'s result for the same x (and the same label_smoothing: another one is refused)
     label_smoothing = eps in [0, 1): the loss of the target distribution (1 - eps) onehot + eps / V, what
@@ -315,8 +367,19 @@ def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Te
     H the entropy of the row's softmax (the model's full-vocabulary distribution at temperature 1) -- an entropy bonus beside an
     advantage-weighted w, a confidence penalty beside the mask.  None: today's launches and nothing else; 0: the entropy is
     computed (return_entropy) and loss, gradient and NLL keep their bits.
-    return_entropy: a last result, sum_m m[m] H[m] as a [1] tensor without a graph"""
+    return_entropy: a last result, sum_m m[m] H[m] as a [1] tensor without a graph
+    distill = (teacher_rows [M, V] or [T, B, V] fp32 log-scale scores, alpha in [0, 1], tau > 0[, int32 row map]): word-level
+    distillation -- the loss becomes (1 - alpha) NLL + alpha tau^2 sum_m w[m] KL(softmax(teacher / tau) || softmax(z / tau)); not
+    together with label_smoothing > 0 or entropy_beta (ValueError).  None: today's launches and nothing else.
+    return_kd: a last result, the unmixed tau^2-scaled KL sum as a [1] tensor without a graph; return_nll is then the unmixed NLL"""
     eps = hip.check_label_smoothing(label_smoothing)
+    kd = _distill_args("vocab_head_nll", distill, return_kd, target.numel(), weight.shape[0], eps, entropy_beta, return_entropy)
+    if done is not None and _done_kd(done) != (None if kd is None else (kd[1], kd[2])):
+        raise RuntimeError(f"vocab_head_nll: `done` was computed with distill (alpha, tau) = {_done_kd(done)}, this call asks for "
+                           f"{None if kd is None else (kd[1], kd[2])}")
+    if kd is not None:
+        loss, amax, nll, k = _VocabHeadNLLKD.apply(x, weight, bias, target.reshape(-1), w.reshape(-1), kd[0], kd[3], done, kd[1], kd[2])
+        return (loss, amax) + ((nll,) if return_nll else ()) + ((k,) if return_kd else ())
     ent = _entropy_args("vocab_head_nll", entropy_beta, entropy_weight, return_entropy, target.numel())
     if done is not None and (ent is not None or _done_beta(done) is not None):
         _refuse_done(done, eps, None if ent is None else ent[0])
@@ -331,10 +394,17 @@ def vocab_head_nll(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Te
 
 
 def vocab_head_nll_compute(x: Tensor, weight: Tensor, bias: Optional[Tensor], target: Tensor, w: Tensor, label_smoothing: float = 0.0,
-                           entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False):
+                           entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False,
+                           distill=None):
     """the arithmetic of vocab_head_nll without its graph node (-> an opaque `done` for vocab_head_nll; done[1] is the argmax).
-    `done` carries label_smoothing and entropy_beta: vocab_head_nll refuses one computed with another value of either"""
+    `done` carries label_smoothing, entropy_beta and distill's alpha and tau: vocab_head_nll refuses one computed with another value
+    of any of them"""
     eps = hip.check_label_smoothing(label_smoothing)
+    kd = _distill_args("vocab_head_nll_compute", distill, False, target.numel(), weight.shape[0], eps, entropy_beta, return_entropy)
+    if kd is not None:
+        with torch.no_grad():
+            return _VocabHeadNLLKD.compute(x.detach(), weight.detach(), None if bias is None else bias.detach(), target.reshape(-1),
+                                           w.reshape(-1), kd[0], kd[3], kd[1], kd[2])
     ent = _entropy_args("vocab_head_nll_compute", entropy_beta, entropy_weight, return_entropy, target.numel())
     with torch.no_grad():
         if ent is not None:
@@ -843,11 +913,36 @@ class _VocabNLLEnt(torch.autograd.Function):
                 None, None)
 
 
+class _VocabNLLKD(torch.autograd.Function):
+    """_VocabNLL against a dense teacher row mixed with the one-hot loss (cvc_vocab_nll_kd_fwd / _bwd): the backward reads the forward's
+    per-row statistics and the teacher rows again; two more results without a graph, the unmixed NLL sum and KD sum."""
+
+    @staticmethod
+    def forward(ctx, logits, target, w, teacher, row_map, alpha, tau):
+        logits, target, w = logits.contiguous(), target.contiguous(), w.contiguous()
+        ctx.alpha, ctx.tau = alpha, tau
+        loss, stats, amax, nll, kd = hip.vocab_nll_kd_fwd(logits, target, w, teacher, alpha, tau, row_map)
+        ctx.save_for_backward(logits, stats, target, w, teacher, *(() if row_map is None else (row_map,)))
+        ctx.mark_non_differentiable(amax, nll, kd)
+        return loss, amax, nll, kd
+
+    @staticmethod
+    def backward(ctx, g, _g_amax, _g_nll, _g_kd):
+        logits, stats, target, w, teacher, *rm = ctx.saved_tensors
+        return (hip.vocab_nll_kd_bwd(logits, stats, target, w, teacher, g.contiguous().reshape(1), ctx.alpha, ctx.tau, rm[0] if rm else None),
+                None, None, None, None, None, None)
+
+
 def vocab_nll(logits: Tensor, target: Tensor, w: Tensor, label_smoothing: float = 0.0, return_nll: bool = False,
-              entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False):
+              entropy_beta: Optional[float] = None, entropy_weight: Optional[Tensor] = None, return_entropy: bool = False,
+              distill=None, return_kd: bool = False):
     """-> (sum_m w[m] * -log_softmax(logits)[m, target[m]]  as a [1] tensor,  argmax over V per row [M] int64).
-    label_smoothing, return_nll, entropy_beta, entropy_weight, return_entropy: as vocab_head_nll"""
+    label_smoothing, return_nll, entropy_beta, entropy_weight, return_entropy, distill, return_kd: as vocab_head_nll"""
     eps = hip.check_label_smoothing(label_smoothing)
+    kd = _distill_args("vocab_nll", distill, return_kd, target.numel(), logits.shape[-1], eps, entropy_beta, return_entropy)
+    if kd is not None:
+        loss, amax, nll, k = _VocabNLLKD.apply(logits, target.reshape(-1), w.reshape(-1), kd[0], kd[3], kd[1], kd[2])
+        return (loss, amax) + ((nll,) if return_nll else ()) + ((k,) if return_kd else ())
     ent = _entropy_args("vocab_nll", entropy_beta, entropy_weight, return_entropy, target.numel())
     if ent is not None:
         loss, amax, nll, h = _VocabNLLEnt.apply(logits, target.reshape(-1), w.reshape(-1), ent[1], eps, ent[0])

@@ -301,6 +301,11 @@ SIGNATURES = {
     "cvc_vocab_head_nll_ent_fwd": [_P, _I, _LL, _I, _P, _P, _P, _P, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cvc_vocab_nll_ent_fwd": [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "cvc_vocab_nll_ent_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P],
+    # word-level distillation in the vocabulary criterion: a dense teacher row (base, leading dimension, optional int32 row map, rows),
+    # alpha and tau; row_kd / kd_sum beside the label-smoothing entries' outputs (csrc/distill.hip; building blocks)
+    "cvc_vocab_head_nll_kd_fwd": [_P, _I, _LL, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_kd_fwd": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cvc_vocab_nll_kd_bwd": [_P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _F, _F, _P, _P],
     "cvc_gather_rows": [_P, _P, _I, _I, _I, _P, _P],
     "cvc_tile_rows_alloc": [_I],
     "cvc_tile_gemm_loaders": [_I],
@@ -347,7 +352,8 @@ BLOCKS = {
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
     "cvc_caption_set_stats", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
-    "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix"}
+    "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix",
+    "cvc_vocab_head_nll_kd_fwd", "cvc_vocab_nll_kd_fwd", "cvc_vocab_nll_kd_bwd"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",
@@ -1149,6 +1155,92 @@ def vocab_nll_ent_bwd(logits, lse, target, w, m, row_ent, g, eps: float, beta: f
     d = torch.empty_like(logits)
     _check(lib().cvc_vocab_nll_ent_bwd(_dev(logits), _dev(lse), _dev(target, torch.int64), _dev(w), _dev(m), _dev(row_ent), _dev(g), M, V,
                                        eps, beta, _dev(d), _stream()), "cvc_vocab_nll_ent_bwd")
+    return d
+
+
+def check_distill_scalars(alpha, tau, what="distill"):
+    """(alpha, tau) as floats -- the soft loss's share in [0, 1] and the temperature, finite and > 0 -- or ValueError (before any tensor
+    is touched or kernel launched)"""
+    try:
+        a, t = float(alpha), float(tau)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: alpha and tau must be numbers, got {alpha!r}, {tau!r}") from None
+    if not (0.0 <= a <= 1.0):                # (a NaN fails the comparison)
+        raise ValueError(f"{what}: alpha must be in [0, 1], got {alpha!r}")
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"{what}: tau (the temperature) must be finite and > 0, got {tau!r}")
+    return a, t
+
+
+def check_distill(distill, rows: int, V: int, what="distill"):
+    """distill = (teacher_rows, alpha, tau[, row_map]) -> (teacher [R, V] fp32 contiguous, alpha, tau, row_map int32 [rows]
+    or None), or ValueError.  teacher_rows: [R, V] or [T, R', V] (flattened, rows t * R' + r) log-scale scores; without a row map row m
+    of the criterion takes teacher row m, so R >= rows"""
+    if not isinstance(distill, (tuple, list)) or len(distill) not in (3, 4):
+        raise ValueError(f"{what}: expected (teacher_rows, alpha, tau[, row_map]), got {type(distill).__name__}")
+    alpha, tau = check_distill_scalars(distill[1], distill[2], what)
+    t = distill[0]
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (2, 3) or t.shape[-1] != V:
+        raise ValueError(f"{what}: teacher_rows must be an fp32 [rows, {V}] or [T, rows, {V}] tensor, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dim() == 3:
+        t = t.reshape(-1, V)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    row_map = distill[3] if len(distill) == 4 else None
+    if row_map is not None:
+        if row_map.dtype != torch.int32 or row_map.numel() != rows:
+            raise ValueError(f"{what}: row_map must be int32 with {rows} elements")
+        row_map = row_map.contiguous()
+    elif t.shape[0] < rows:
+        raise ValueError(f"{what}: {t.shape[0]} teacher rows for {rows} rows of the criterion")
+    return t, alpha, tau, row_map
+
+
+def vocab_head_nll_kd_fwd(parts, bias, target, w, teacher, alpha: float, tau: float, row_map=None):
+    """vocab_head_nll_ls_fwd against a dense teacher row (cvc_vocab_head_nll_kd_fwd): -> loss_sum [1] (mixed), argmax [M], pre [M, V]
+    (aliasing slab 0; the mixed loss's gradient), nll_sum [1] (unmixed), kd_sum [1] (unmixed)"""
+    alpha, tau = check_distill_scalars(alpha, tau)
+    ks, M, V = parts.shape
+    _check_rows("vocab_head_nll_kd_fwd", M, target=target, w=w)
+    dev = parts.device
+    rows = torch.empty(3, M, device=dev, dtype=torch.float32)
+    sums = torch.empty(3, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64)
+    pre = parts[0]
+    _check(lib().cvc_vocab_head_nll_kd_fwd(_dev(parts), ks, M * V, V, _dev(bias), _dev(target, torch.int64), _dev(w), _dev(teacher),
+                                           V, _dev(row_map, torch.int32), teacher.shape[0], M, V, alpha, tau, pre.data_ptr(), V,
+                                           _dev(amax, torch.int64), _dev(rows), _dev(sums), rows[1].data_ptr(), sums[1:].data_ptr(),
+                                           rows[2].data_ptr(), sums[2:].data_ptr(), _stream()), "cvc_vocab_head_nll_kd_fwd")
+    return sums[0:1], amax, pre, sums[1:2], sums[2:3]
+
+
+def vocab_nll_kd_fwd(logits, target, w, teacher, alpha: float, tau: float, row_map=None, want_argmax=True):
+    """the two-step form on materialised logits -> loss_sum [1], stats [5, M] (the backward's input), argmax [M] int64 (or None),
+    nll_sum [1], kd_sum [1]"""
+    alpha, tau = check_distill_scalars(alpha, tau)
+    M, V = logits.shape
+    _check_rows("vocab_nll_kd_fwd", M, target=target, w=w)
+    dev = logits.device
+    stats = torch.empty(5, M, device=dev, dtype=torch.float32)
+    rows = torch.empty(3, M, device=dev, dtype=torch.float32)
+    sums = torch.empty(3, device=dev, dtype=torch.float32)
+    amax = torch.empty(M, device=dev, dtype=torch.int64) if want_argmax else None
+    _check(lib().cvc_vocab_nll_kd_fwd(_dev(logits), _dev(target, torch.int64), _dev(w), _dev(teacher), V,
+                                      _dev(row_map, torch.int32), teacher.shape[0], M, V, alpha, tau, _dev(stats), _dev(amax, torch.int64),
+                                      _dev(rows), _dev(sums), rows[1].data_ptr(), sums[1:].data_ptr(), rows[2].data_ptr(),
+                                      sums[2:].data_ptr(), _stream()), "cvc_vocab_nll_kd_fwd")
+    return sums[0:1], stats, amax, sums[1:2], sums[2:3]
+
+
+def vocab_nll_kd_bwd(logits, stats, target, w, teacher, g, alpha: float, tau: float, row_map=None):
+    alpha, tau = check_distill_scalars(alpha, tau)
+    M, V = logits.shape
+    _check_rows("vocab_nll_kd_bwd", M, target=target, w=w)
+    d = torch.empty_like(logits)
+    _check(lib().cvc_vocab_nll_kd_bwd(_dev(logits), _dev(stats), _dev(target, torch.int64), _dev(w), _dev(teacher), V,
+                                      _dev(row_map, torch.int32), teacher.shape[0], _dev(g), M, V, alpha, tau, _dev(d), _stream()),
+           "cvc_vocab_nll_kd_bwd")
     return d
 
 

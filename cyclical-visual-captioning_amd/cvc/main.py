@@ -132,7 +132,67 @@ def build_parser():
                         help="comma-separated positive weights, one per member (the resumed checkpoint first); default: uniform")
     parser.add_argument("--ensemble_combine", choices=("prob", "logprob"), default=argparse.SUPPRESS,
                         help="prob: the weighted mean of the members' probabilities (default); logprob: of their log-probs")
+    # word-level distillation from an ensemble of frozen checkpoints (cvc.model.CaptionEnsemble.soft_targets; cvc.functional
+    # vocab_head_nll distill=): off by default and then no key in the options, no launch changes
+    parser.add_argument("--distill_from", type=str, default=argparse.SUPPRESS,
+                        help="comma-separated checkpoint files (state dicts of models built from the same options), the TEACHER: the "
+                             "cross-entropy steps train loop A against the teacher's next-word distribution at every position of the "
+                             "ground-truth captions, mixed with the one-hot loss; eager steps, the display line also shows NLL and KD.  "
+                             "Not with --label_smoothing, --confidence_penalty / --log_entropy or scheduled sampling; self-critical "
+                             "steps (--scst_after) are not distilled")
+    parser.add_argument("--distill_weights", type=str, default=argparse.SUPPRESS,
+                        help="comma-separated positive weights, one per teacher checkpoint; default: uniform")
+    parser.add_argument("--distill_combine", choices=("prob", "logprob"), default=argparse.SUPPRESS,
+                        help="prob: the weighted mean of the teachers' probabilities (default); logprob: of their log-probs")
+    parser.add_argument("--distill_alpha", type=float, default=argparse.SUPPRESS,
+                        help="the soft loss's share in [0, 1] (default 0.5): loss = (1 - alpha) NLL + alpha tau^2 KL(teacher || student)")
+    parser.add_argument("--distill_temperature", type=float, default=argparse.SUPPRESS,
+                        help="tau > 0 (default 1.0): both distributions are softmax(. / tau)")
     return parser
+
+
+def check_distill_flags(opt):
+    """--distill_from and its companions -> dict(paths, weights or None, combine, alpha, tau), or None with the flag absent.  Ends the
+    run with a message, before any set-up: a companion flag without --distill_from, alpha outside [0, 1], a temperature that is not
+    finite or <= 0, a weight count that does not match, malformed weights, more than 8 members, a missing file, and the combinations
+    with label smoothing, the confidence penalty and scheduled sampling."""
+    import math
+    spec = getattr(opt, "distill_from", None)
+    companions = ("distill_weights", "distill_combine", "distill_alpha", "distill_temperature")
+    if spec is None:
+        if any(hasattr(opt, k) for k in companions):
+            raise SystemExit("--distill_weights / --distill_combine / --distill_alpha / --distill_temperature need --distill_from")
+        return None
+    alpha, tau = getattr(opt, "distill_alpha", 0.5), getattr(opt, "distill_temperature", 1.0)
+    if not 0.0 <= alpha <= 1.0:                # (a NaN fails the comparison)
+        raise SystemExit("--distill_alpha must lie in [0, 1], got %r" % (alpha,))
+    if not (math.isfinite(tau) and tau > 0.0):
+        raise SystemExit("--distill_temperature must be finite and > 0, got %r" % (tau,))
+    if getattr(opt, "label_smoothing", 0.0) > 0 or hasattr(opt, "confidence_penalty") or getattr(opt, "log_entropy", False):
+        raise SystemExit("--distill_from excludes --label_smoothing > 0, --confidence_penalty and --log_entropy: the teacher's row is the "
+                         "target distribution")
+    if getattr(opt, "scheduled_sampling_start", -1) >= 0:
+        raise SystemExit("--distill_from and scheduled sampling (--scheduled_sampling_start) exclude each other: the student would be fed "
+                         "words the teacher never saw")
+    paths = [p.strip() for p in spec.split(",") if p.strip()]
+    if not paths:
+        raise SystemExit("--distill_from names no checkpoint file")
+    weights = None
+    if hasattr(opt, "distill_weights"):
+        try:
+            weights = [float(w) for w in opt.distill_weights.split(",")]
+        except ValueError:
+            raise SystemExit("--distill_weights must be comma-separated numbers, got %r" % (opt.distill_weights,)) from None
+        if len(weights) != len(paths):
+            raise SystemExit("--distill_weights has %d weights for %d teacher checkpoints" % (len(weights), len(paths)))
+        if not all(np.isfinite(w) and w > 0 for w in weights):
+            raise SystemExit("--distill_weights must be finite numbers > 0, got %r" % (opt.distill_weights,))
+    if len(paths) > 8:
+        raise SystemExit("--distill_from: an ensemble has at most 8 members, got %d" % len(paths))
+    for p in paths:
+        if not os.path.isfile(p):
+            raise SystemExit("--distill_from: no such checkpoint file: %s" % p)
+    return dict(paths=paths, weights=weights, combine=getattr(opt, "distill_combine", "prob"), alpha=float(alpha), tau=float(tau))
 
 
 def check_ensemble_flags(opt):
@@ -171,16 +231,16 @@ def check_ensemble_flags(opt):
     return paths, weights, getattr(opt, "ensemble_combine", "prob")
 
 
-def check_member_state(path, state, reference):
-    """an --ensemble member's state dict against the resumed model's: a vocabulary of another size (the embedding, the vocabulary
-    head) or any other tensor of another shape ends the run with a message"""
+def check_member_state(path, state, reference, flag="--ensemble"):
+    """an --ensemble member's (or a --distill_from teacher's) state dict against the resumed (the trained) model's: a vocabulary of
+    another size (the embedding, the vocabulary head) or any other tensor of another shape ends the run with a message"""
     for k in ("embed.0.weight", "logit.weight"):
         if k in state and k in reference and tuple(state[k].shape) != tuple(reference[k].shape):
-            raise SystemExit("--ensemble: %s has a different vocabulary: %s is %s, the resumed checkpoint's %s (the members choose one "
-                             "word from one vocabulary)" % (path, k, tuple(state[k].shape), tuple(reference[k].shape)))
+            raise SystemExit("%s: %s has a different vocabulary: %s is %s, the resumed checkpoint's %s (the members choose one "
+                             "word from one vocabulary)" % (flag, path, k, tuple(state[k].shape), tuple(reference[k].shape)))
     bad = sorted(k for k in reference if k not in state or tuple(state[k].shape) != tuple(reference[k].shape))
     if bad:
-        raise SystemExit("--ensemble: %s does not fit a model built from these options: %s" % (path, ", ".join(bad[:4])))
+        raise SystemExit("%s: %s does not fit a model built from these options: %s" % (flag, path, ", ".join(bad[:4])))
 
 
 def check_val_diversity_flag(opt):
@@ -223,6 +283,7 @@ def main(argv=None, sample=None, score=None):
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
     ensemble = check_ensemble_flags(opt)
+    distill = check_distill_flags(opt)
     if ensemble is not None and score is not None and score.get("ground_gt"):
         raise SystemExit("--ensemble and --ground_gt exclude each other: the grounding on GT sentences reads one model's frame-masked "
                          "attention and grounder")
@@ -347,6 +408,24 @@ def main(argv=None, sample=None, score=None):
         trainer.ensemble = CaptionEnsemble(members, weights=ensemble[1], combine=ensemble[2])
         if rank == 0:
             print("ensemble of %d checkpoints (%s)" % (len(members), ensemble[2]))
+    if distill is not None and not opt.inference_only and sample is None and score is None:
+        # the teacher: frozen checkpoints behind one CaptionEnsemble, on the trained model (Trainer._kd_step_prepared reads it there)
+        from .model.ensemble import CaptionEnsemble
+        core = getattr(model, "module", model)
+        teachers = []
+        for p in distill["paths"]:
+            state = torch.load(p, map_location=device)
+            check_member_state(p, state, core.state_dict(), flag="--distill_from")
+            member = build_model(opt, device)
+            member.load_state_dict(state)
+            member = getattr(member, "module", member).eval()
+            member.requires_grad_(False)
+            teachers.append(member)
+        core.distill = dict(teacher=CaptionEnsemble(teachers, weights=distill["weights"], combine=distill["combine"]),
+                            alpha=distill["alpha"], tau=distill["tau"])
+        if rank == 0:
+            print("distilling from %d checkpoints (%s), alpha %g, temperature %g" % (len(teachers), distill["combine"], distill["alpha"],
+                                                                                      distill["tau"]))
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
@@ -400,7 +479,8 @@ def main(argv=None, sample=None, score=None):
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
                          "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history),
-                         "nll_history": dict(trainer.nll_history), "entropy_history": dict(trainer.entropy_history)}
+                         "nll_history": dict(trainer.nll_history), "entropy_history": dict(trainer.entropy_history),
+                         **({"kd_history": dict(trainer.kd_history)} if distill is not None else {})}
             with open(os.path.join(save_dir, "infos_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(infos, f)
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:

@@ -87,15 +87,40 @@ def _masked_nll_mean(txt_input, target, label_smoothing=0.0):
     return (total / count).reshape(())
 
 
+def _distill_rows(distill, target, t_major, row_weight):
+    """a criterion's distill=(teacher_rows [T, B, V], alpha, tau) as cvc.functional takes it for rows in the criterion's order: the
+    teacher's rows are t-major (row t * B + b, the order the forced decode engine writes them in), so a b-major criterion gets the
+    int32 row map b * T + t -> t * B + b"""
+    if row_weight is not None:
+        raise ValueError("distill cannot be combined with row_weight: a self-critical step is not distilled")
+    if not isinstance(distill, (tuple, list)) or len(distill) != 3:
+        raise ValueError(f"distill: expected (teacher_rows, alpha, tau), got {type(distill).__name__}")
+    rows, alpha, tau = distill
+    B, T = target.shape
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 3 or tuple(rows.shape[:2]) != (T, B):
+        raise ValueError(f"distill: teacher_rows must be [T = {T}, B = {B}, V], got "
+                         f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+    if t_major:
+        return rows, alpha, tau
+    row_map = torch.arange(B * T, device=target.device, dtype=torch.int32).view(T, B).t().reshape(-1)
+    return rows, alpha, tau, row_map
+
+
 def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None, label_smoothing=0.0, want_nll=False,
-                                 entropy_beta=None, want_entropy=False):
+                                 entropy_beta=None, want_entropy=False, distill=None):
     """Same value as _masked_nll_mean(log_softmax(logits), target), plus the per-row argmax, from one fused pass.
     t_major: the rows of `logits` are ordered t * B + b (the C-driven training loops' outputs) instead of b * T + t.
-    row_weight, label_smoothing, want_nll, entropy_beta, want_entropy: see _masked_nll_mean_from_head."""
+    row_weight, label_smoothing, want_nll, entropy_beta, want_entropy, distill: see _masked_nll_mean_from_head."""
     w = _text_mask(target).to(torch.float32)
     count = w.sum()
     ent = ()
-    if entropy_beta is not None or want_entropy:
+    if distill is not None:
+        kd = _distill_rows(distill, target, t_major, row_weight)
+        tf, wf = (target.t().reshape(-1), w.t().reshape(-1)) if t_major else (target.reshape(-1), w.reshape(-1))
+        total, argmax, nll, k = F_.vocab_nll(logits, tf, wf, label_smoothing=label_smoothing, return_nll=True, entropy_beta=entropy_beta,
+                                             return_entropy=want_entropy, distill=kd, return_kd=True)
+        ent = ((k / count).reshape(()),)
+    elif entropy_beta is not None or want_entropy:
         tf, wf = (target.t().reshape(-1), w.t().reshape(-1)) if t_major else (target.reshape(-1), w.reshape(-1))
         total, argmax, nll, h = F_.vocab_nll(logits, tf, wf if row_weight is None else row_weight.reshape(-1),
                                              label_smoothing=0.0 if row_weight is not None else label_smoothing, return_nll=True,
@@ -114,7 +139,7 @@ def _masked_nll_mean_from_logits(logits, target, t_major=False, row_weight=None,
 
 
 def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None, compute_only=False, row_weight=None,
-                               label_smoothing=0.0, want_nll=False, entropy_beta=None, want_entropy=False):
+                               label_smoothing=0.0, want_nll=False, entropy_beta=None, want_entropy=False, distill=None):
     """_masked_nll_mean_from_logits(x W^T + b, target) with the criterion folded into the vocabulary head's GEMM finish: the logits
     are never materialised (cvc.functional.vocab_head_nll); falls back to the two-step form for shapes that kernel does not take.
     row_weight: a real weight per row of x (in x's row order, any sign, 0 where the loss mask is 0) in place of the 0 / 1 loss mask:
@@ -128,13 +153,19 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
     bonus with row_weight, a confidence penalty without.  The entropy weight is always the loss mask of `target`, in x's row
     order; it applies with row_weight too (label smoothing does not).  None: today's launches; 0: the entropy is computed and
     nothing else changes.
-    want_entropy: a last result, the mean entropy sum_r mask[r] H[r] / sum(mask) as a scalar without a graph."""
+    want_entropy: a last result, the mean entropy sum_r mask[r] H[r] / sum(mask) as a scalar without a graph.
+    distill = (teacher_rows [T, B, V] fp32 log-scale scores in the forced decode engine's t-major order, alpha, tau): word-level
+    distillation, the loss (1 - alpha) x the mean NLL + alpha tau^2 x the mean masked KL(teacher || student) at temperature tau
+    (cvc.functional.vocab_head_nll); refused with row_weight, label_smoothing > 0 or entropy_beta (ValueError).  With it want_nll is the
+    UNMIXED mean NLL and the last result is the unmixed mean tau^2 KL, a scalar without a graph.  None: today's launches."""
+    if distill is not None:
+        distill = (*_distill_rows(distill, target, True, row_weight)[:3],)       # (checked once; the row map is made where it is needed)
     if row_weight is not None:
         label_smoothing = 0.0
     if not F_.vocab_head_nll_ok(x, weight):
         return _masked_nll_mean_from_logits(F_.linear(x, weight, bias), target, t_major, row_weight=row_weight,
                                             label_smoothing=label_smoothing, want_nll=want_nll, entropy_beta=entropy_beta,
-                                            want_entropy=want_entropy)
+                                            want_entropy=want_entropy, distill=distill)
     # the loss mask, its count and the t-major copies depend on the target alone: both heads of a cyclical pass (decode,
     # reconstruction) score against the same target tensor, so they are formed once and kept on it
     pre = getattr(target, "_cvc_nll_pre", None)
@@ -145,12 +176,17 @@ def _masked_nll_mean_from_head(x, weight, bias, target, t_major=False, done=None
         target._cvc_nll_pre = pre
     _, tf, wf, count = pre
     ent = dict(entropy_beta=entropy_beta, entropy_weight=wf, return_entropy=True) if entropy_beta is not None or want_entropy else {}
+    if distill is not None:
+        ent = dict(ent, entropy_beta=entropy_beta, return_entropy=want_entropy, distill=_distill_rows(distill, target, t_major, None))
+        want_entropy = True                      # (the last result below: the KD mean in the entropy's place -- never both)
     if row_weight is not None:
         wf = row_weight.reshape(-1).contiguous()
     if compute_only:       # -> (opaque result for a later call with done=, the argmax words)
         done = F_.vocab_head_nll_compute(x, weight, bias, tf, wf, label_smoothing=label_smoothing, **ent)
         argmax = done[1]
         return done, (argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
+    if distill is not None:
+        ent["return_kd"] = True
     total, argmax, nll, *h = F_.vocab_head_nll(x, weight, bias, tf, wf, done, label_smoothing=label_smoothing, return_nll=True, **ent)
     res = ((total / count).reshape(()), argmax.view(target.shape[1], target.shape[0]).t() if t_major else argmax.view(target.shape))
     return (*res, *(((nll / count).reshape(()),) if want_nll else ()), *(((h[0] / count).reshape(()),) if want_entropy else ()))
@@ -189,13 +225,15 @@ class LMCriterion(nn.Module):
         self.confidence_penalty = _opt_confidence_penalty(opt, confidence_penalty)
         self.last_nll = None
         self.last_entropy = None
+        self.last_kd = None
 
-    def _keep(self, res):
-        """(loss, argmax[, unsmoothed mean -- asked for when smoothing is on][, mean entropy -- when the penalty is not None]) ->
-        (loss, argmax); the others stay on the module"""
+    def _keep(self, res, distill=None):
+        """(loss, argmax[, unsmoothed / unmixed mean -- asked for when smoothing is on or a teacher is given][, mean entropy -- when the
+        penalty is not None][, mean KD -- when a teacher is given]) -> (loss, argmax); the others stay on the module"""
         rest = list(res[2:])
-        self.last_nll = rest.pop(0) if self.label_smoothing > 0 else None
-        self.last_entropy = rest.pop(0) if self.confidence_penalty is not None else None
+        self.last_nll = rest.pop(0) if self.label_smoothing > 0 or distill is not None else None
+        self.last_entropy = rest.pop(0) if self.confidence_penalty is not None and distill is None else None
+        self.last_kd = rest.pop(0) if distill is not None else None
         return res[0], res[1]
 
     def _ent(self):
@@ -207,33 +245,40 @@ class LMCriterion(nn.Module):
         loss = _masked_nll_mean(txt_input, target, self.label_smoothing)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target))
 
-    def from_logits(self, logits, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False):
+    def from_logits(self, logits, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, distill=None):
         """forward() fed raw logits instead of log-probs: -> (lm_loss, att2_loss, ground_loss, argmax [B, T]).
-        SURVEY section 8(f) rank 2: the criterion folded into the vocabulary head's epilogue pass."""
+        SURVEY section 8(f) rank 2: the criterion folded into the vocabulary head's epilogue pass.
+        distill = (teacher_rows [T, B, V], alpha, tau): see from_head."""
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
         loss, argmax = self._keep(_masked_nll_mean_from_logits(logits, target, t_major, label_smoothing=self.label_smoothing,
-                                                               want_nll=self.label_smoothing > 0, **self._ent()))
+                                                               want_nll=self.label_smoothing > 0 or distill is not None, distill=distill,
+                                                               **self._ent()), distill)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
-    def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None, row_weight=None):
+    def from_head(self, x, head, att2_weights, ground_weights, target, att2_target, input_seq, t_major=False, done=None, row_weight=None,
+                  distill=None):
         """from_logits() fed the vocabulary head's INPUT x [rows, R] and the head module (nn.Linear): the head's GEMM and the
         criterion run as one op, no logits tensor.  done: head_words()'s first result for the same x (the arithmetic then is not
-        repeated).  row_weight: the self-critical loss, which ignores label smoothing (_masked_nll_mean_from_head)."""
+        repeated).  row_weight: the self-critical loss, which ignores label smoothing (_masked_nll_mean_from_head).
+        distill = (teacher_rows [T, B, V], alpha, tau): word-level distillation (_masked_nll_mean_from_head); last_nll and last_kd then
+        are the unmixed mean NLL and the unmixed mean tau^2 KL of the call.  Refused with row_weight, label smoothing or the confidence
+        penalty (ValueError)."""
         if not torch.cuda.is_current_stream_capturing():
             assert torch.sum(target >= self.vocab_size) == 0
         loss, argmax = self._keep(_masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, done=done, row_weight=row_weight,
-                                                             label_smoothing=self.label_smoothing, want_nll=self.label_smoothing > 0,
-                                                             **self._ent()))
+                                                             label_smoothing=self.label_smoothing,
+                                                             want_nll=self.label_smoothing > 0 or distill is not None, distill=distill,
+                                                             **self._ent()), distill)
         return (loss, *self.attention_losses(att2_weights, ground_weights, att2_target), argmax)
 
-    def head_words(self, x, head, target, t_major=False):
+    def head_words(self, x, head, target, t_major=False, distill=None):
         """the head + criterion arithmetic of from_head() ahead of its graph node: -> (done, argmax words [B, T]), or None for
-        shapes the fused head does not take"""
+        shapes the fused head does not take.  distill: as from_head (the `done` carries its alpha and tau)"""
         if not F_.vocab_head_nll_ok(x, head.weight):
             return None
         return _masked_nll_mean_from_head(x, head.weight, head.bias, target, t_major, compute_only=True,
-                                          label_smoothing=self.label_smoothing, entropy_beta=self.confidence_penalty)
+                                          label_smoothing=self.label_smoothing, entropy_beta=self.confidence_penalty, distill=distill)
 
     @staticmethod
     def attention_losses(att2_weights, ground_weights, att2_target):

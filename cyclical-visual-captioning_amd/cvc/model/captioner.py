@@ -99,6 +99,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # With it not None a training pass leaves loop A's mean masked entropy of the word distribution here, and scst_loss with
         # entropy_beta not None the rollouts' (a device scalar, no graph), else None.  Evaluation passes carry no penalty.
         self.last_entropy = None
+        # word-level distillation: dict(teacher=CaptionEnsemble, alpha=, tau=) or None.  forward(soft_targets=rows) then trains loop A
+        # against the teacher's rows (teacher.soft_targets(batch)[0]) mixed with the one-hot loss; the pass leaves loop A's UNMIXED
+        # mean NLL in last_nll and its unmixed mean tau^2 KL(teacher || student) in last_kd (device scalars, no graph), else None.
+        # The reconstruction loss, loops B / C, the attention criteria, the self-critical loss and evaluation are not distilled.
+        self.distill: Optional[dict] = None
+        self.last_kd = None
+        self._soft_targets = None
         self.beam_size = int(getattr(opts, "beam_size", 1))
         self.use_hip_graph = bool(getattr(opts, "hip_graph", False))
         # decoding rule of _sample: sample_max = 1 takes the arg-max word (greedy / beam); sample_max = 0 samples from
@@ -209,10 +216,27 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask,
-                sample_idx, pnt_mask, lang_eval=False, teacher_forcing=False, ss_inputs=None):
+                sample_idx, pnt_mask, lang_eval=False, teacher_forcing=False, ss_inputs=None, soft_targets=None):
         """reference :175-194.  ss_inputs [B * seq_per_img, T] int64 (column 0 = BOS; ss_rollout's result): loop A embeds these words
         instead of gt_caption[:, :T] -- scheduled sampling; targets, label glue, the grounder's class inputs and loops B / C are the
-        ground truth's.  None: teacher forcing, as always."""
+        ground truth's.  None: teacher forcing, as always.
+        soft_targets [T, B * seq_per_img, V] fp32 (CaptionEnsemble.soft_targets' rows): loop A's criterion is distilled against them
+        with self.distill's alpha and tau -- a training pass only, not with ss_inputs (the student would be fed words the teacher
+        never saw), label smoothing or the confidence penalty.  None: today's launches."""
+        if soft_targets is not None:
+            if lang_eval or ss_inputs is not None:
+                raise RuntimeError("forward: soft_targets are a teacher-forced training pass's (lang_eval=False, no ss_inputs)")
+            if self.distill is None:
+                raise RuntimeError("forward: soft_targets need model.distill = dict(teacher=, alpha=, tau=)")
+            if self.label_smoothing > 0 or self.confidence_penalty is not None:
+                raise ValueError("forward: soft_targets cannot be combined with label_smoothing > 0 or the confidence penalty")
+            hip.check_distill_scalars(self.distill["alpha"], self.distill["tau"], "model.distill")
+            self._soft_targets = soft_targets
+            try:
+                return self.forward(segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask,
+                                    sample_idx, pnt_mask)
+            finally:
+                self._soft_targets = None
         F_.new_step()
         if lang_eval and teacher_forcing and (self.label_smoothing > 0 or self.confidence_penalty is not None):
             # an evaluation pass reports the model's true log-probs: label smoothing and the confidence penalty are the training
@@ -343,9 +367,11 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         target = gt_caption[:, 1:T + 1].clone()
         # criteria fused with log_softmax and the argmax cut of :313 (one pass over the logits, no [B,T,V] log-probs)
         lm_loss, att2_loss, ground_loss, output_seq = self.critLM.from_logits(
-            lang_logits, att2_weights, ground_weights, target, roi_labels[:, :T, :].clone(), input_seq[:, 1:T + 1, 0].clone())
+            lang_logits, att2_weights, ground_weights, target, roi_labels[:, :T, :].clone(), input_seq[:, 1:T + 1, 0].clone(),
+            **({} if self._soft_targets is None else dict(distill=self._kd())))
         self.last_nll = self.critLM.last_nll
         self.last_entropy = self.critLM.last_entropy
+        self.last_kd = self.critLM.last_kd
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
 
@@ -374,6 +400,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         lm_recon_loss = self.xe_criterion.from_logits(self._logits(torch.stack(rec_outputs, 1).view(B * T, -1)), target)
         return (lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1),
                 lm_recon_loss.reshape(1))
+
+    def _kd(self):
+        """loop A's distill= of this pass: (teacher rows, alpha, tau), or None"""
+        if self._soft_targets is None:
+            return None
+        return self._soft_targets, self.distill["alpha"], self.distill["tau"]
 
     @property
     def label_smoothing(self) -> float:
@@ -453,7 +485,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         fm = join_t([p_[1] for p_ in parts])
         target = gt_caption[:, 1:T + 1].clone()
         out_c, done = None, None
-        head = self.critLM.head_words(out_a.view(T * B, R), self.logit, target, t_major=True) if all(a.joint_ok() for a in arenas) else None
+        kd = {} if self._soft_targets is None else dict(distill=self._kd())
+        head = self.critLM.head_words(out_a.view(T * B, R), self.logit, target, t_major=True, **kd) if all(a.joint_ok() for a in arenas) else None
         if head is not None:
             # A group's two loops fit the joint back-propagation (64 + 64 rows: config 3; 32 + 32: the shares of the 8-GPU job): loops B
             # and C come FIRST, fed the argmax words of the head's arithmetic, and loop A's outputs pass through loop C's graph node
@@ -477,9 +510,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # vocabulary head + criterion + the argmax cut of :313 as one op on the t-major rows (no logits tensor)
         lm_loss, att2_loss, ground_loss, output_seq = self.critLM.from_head(
             out_a.view(T * B, R), self.logit, att2_weights, ground_weights, target, roi_labels[:, :T, :], input_seq[:, 1:T + 1, 0],
-            t_major=True, done=done)
+            t_major=True, done=done, **kd)
         self.last_nll = self.critLM.last_nll
         self.last_entropy = self.critLM.last_entropy
+        self.last_kd = self.critLM.last_kd
         if self.opts.train_decoder_only:                                              # reference :297-307
             return lm_loss.reshape(1), att2_loss.reshape(1), ground_loss.reshape(1), cls_loss.reshape(1)
         if out_c is None:

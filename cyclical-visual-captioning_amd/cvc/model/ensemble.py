@@ -7,6 +7,7 @@ from typing import Optional
 
 import torch
 
+from .. import functional as F_
 from ..decode.ensemble import EnsembleEngine, EnsembleOptions
 from .captioner import DecodeAndGroundCaptionerGVDROI
 
@@ -34,7 +35,7 @@ class CaptionEnsemble:
         self.last_consensus: Optional[dict] = None
         self.last_stochastic: Optional[dict] = None
         self.consensus_table = None
-        self._engine_cache = self._score_cache = None
+        self._engine_cache = self._score_cache = self._soft_cache = None
         self._encoded = None
 
     def __getattr__(self, name):
@@ -103,6 +104,27 @@ class CaptionEnsemble:
     # ---- the surface
 
     _sample = DecodeAndGroundCaptionerGVDROI._sample
+
+    @torch.no_grad()
+    def soft_targets(self, segs_feat, input_seq, gt_caption, num, proposals, gt_boxes, mask_boxes, region_feats, frm_mask, sample_idx,
+                     pnt_mask):
+        """The ensemble as a TEACHER (word-level distillation; DESIGN section 7, "Distillation"): forward's 11 tensors -> (rows, logprob).
+        The members follow the batch's ground-truth captions gt_caption[:, :seq_per_img] on a cached forced engine that keeps the
+        combined row of every step (EnsembleEngine keep_rows=True): rows [T, B * seq_per_img, V] is the ensemble's log-scale next-word
+        distribution at every position, in the t-major row order of the training loops' vocabulary head; logprob [B * seq_per_img, T]
+        the given words' log-probs.  Both are VIEWS of the engine's buffers: valid until the next call.  eval() semantics, no
+        autograd, no host read-back.  A one-member ensemble is a single-checkpoint teacher."""
+        self.eval()
+        T, n = self.seq_length, self.seq_per_img
+        captions = gt_caption[:, :n, :T].reshape(-1, T).contiguous()
+        if captions.dtype != torch.int64:
+            raise RuntimeError(f"CaptionEnsemble.soft_targets: the captions must be int64, got {captions.dtype}")
+        F_.new_step()
+        self._encode(segs_feat, proposals, num, mask_boxes, region_feats, gt_boxes, frm_mask, sample_idx, pnt_mask)
+        engine = self._decode_engine("_soft_cache", self._encoded[0], T, forced_n=n, weights_dtype="fp32", keep_rows=True,
+                                     prepare=lambda e: e.load_captions(captions))
+        _seq, _att, logprob, _rank = engine.run()
+        return engine.combined, logprob
 
     def score(self, *batch, captions: Optional[torch.Tensor] = None, grounding: bool = False, decode_weights: Optional[str] = None):
         """DecodeAndGroundCaptionerGVDROI.score over the ensemble: logprob / seq_logprob are the ensemble's log-probs of the given words, rank the

@@ -165,6 +165,12 @@ class Trainer:
             beta = 0.0
         self.scst_entropy = None if beta is None else _hip.check_entropy_beta(beta, "scst_entropy")
         self.entropy_history = {}     # epoch -> the mean entropy of every display interval (a coefficient that is not None)
+        # ---- word-level distillation (model.distill = dict(teacher=CaptionEnsemble, alpha=, tau=); cvc.main --distill_from): the
+        # cross-entropy steps run eagerly with the teacher's forced pass in front (_kd_step_prepared); their result carries two more
+        # elements at its end, loop A's unmixed mean NLL and its unmixed mean tau^2 KL(teacher || student).  Self-critical steps are
+        # not distilled
+        self.kd_history = {}          # epoch -> the mean KD of every display interval (distilled steps)
+        self.last_kd = None
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -256,12 +262,42 @@ class Trainer:
         if self.opts.att_model != 'cyclical':
             raise ValueError('Unknown att_model: {}'.format(self.opts.att_model))
         if float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0:
+            if self._distilling():
+                raise RuntimeError("Trainer: model.distill together with scheduled sampling (model.ss_prob > 0) is refused: the student "
+                                   "would be fed words the teacher never saw")
             return self._ss_step_prepared(b)
+        if self._distilling():
+            return self._kd_step_prepared(b)
         out = self._call(b)
         loss, lm, att2, cls, rec = self.loss_mix(out)
         self._backward_and_update(loss)
         self._weights_changed()
         return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), *self._nll_tail(), *self._ent_tail())
+
+    def _distilling(self) -> bool:
+        return getattr(getattr(self.model, "module", self.model), "distill", None) is not None
+
+    def _kd_step_prepared(self, b):
+        """The distillation step (Hinton et al. 2015; Kim & Rush 2016, word level; model.distill set): the teacher -- a CaptionEnsemble
+        of frozen checkpoints -- follows the batch's ground-truth captions on its cached forced engine and leaves its next-word
+        distribution of every position (teacher.soft_targets: eval mode, no autograd), then the ordinary cyclical pass with loop A's
+        criterion (1 - alpha) NLL + alpha tau^2 KL(teacher || student) at temperature tau, and the update.  Runs eagerly; no host
+        read-back between the teacher pass and optimizer.step().  -> (loss, lm, att2, cls, recon, loop A's unmixed mean NLL, its unmixed
+        mean KD); self.last_kd keeps the teacher's log-probs of the given words and the step's KD (device tensors)."""
+        model = getattr(self.model, "module", self.model)
+        if self.label_smoothing > 0 or self.confidence_penalty is not None:
+            raise ValueError("Trainer: model.distill cannot be combined with label_smoothing > 0 or a confidence penalty (the teacher's "
+                             "row is the target distribution)")
+        rows, t_logprob = model.distill["teacher"].soft_targets(
+            b["segs_feat"], b["input_seqs"], b["gt_seqs"], b["num"], b["ppls"], b["gt_bboxs"], b["mask_bboxs"], b["ppls_feat"],
+            b["mask_frms"], b["sample_idx"], b["pnt_mask"])
+        out = self._call(b, soft_targets=rows)
+        loss, lm, att2, cls, rec = self.loss_mix(out)
+        nll, kd = model.last_nll.detach().reshape(()), model.last_kd.detach().reshape(())
+        self._backward_and_update(loss)
+        self._weights_changed()
+        self.last_kd = dict(teacher_logprob=t_logprob, kd=kd, nll=nll)
+        return (loss.detach(), lm.detach(), att2.detach(), cls.detach(), rec.detach(), nll, kd)
 
     def _ss_step_prepared(self, b):
         """The scheduled-sampling step (Bengio et al. 2015; model.ss_prob > 0): the encoder once in eval mode without autograd, one
@@ -667,17 +703,20 @@ class Trainer:
 
     # ------------------------------------------------------------------ epoch loops
     def train(self, epoch, tb_logger=None):
-        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled", "nll", "entropy")}
+        meters = {k: AverageMeter() for k in ("batch", "data", "lm", "attn", "cls", "recon", "reward", "sampled", "nll", "entropy", "kd")}
         self.model.train()
         end = time.time()
         n_steps = len(self.train_loader) - 1                 # the reference drops the last batch (:55)
         scst = self.scst_after >= 0 and epoch >= self.scst_after     # self-critical epochs: eager steps (scst_step_prepared)
         # scheduled-sampling epochs (model.ss_prob > 0, set per epoch by cvc.main): eager steps with a rollout in front
         ss = not scst and float(getattr(getattr(self.model, "module", self.model), "ss_prob", 0.0)) > 0
-        graphed = self.graph_capable() and not scst and not ss
-        smooth = self.label_smoothing > 0 and not scst       # (a last element of every step's result: the unsmoothed NLL)
+        # distilled epochs (model.distill set; not the self-critical ones): eager steps with the teacher's pass in front, two more
+        # elements at the end of every step's result: the unmixed NLL and the KD
+        kd = not scst and self._distilling()
+        graphed = self.graph_capable() and not scst and not ss and not kd
+        smooth = (self.label_smoothing > 0 or kd) and not scst       # (a last element of every step's result: the unsmoothed NLL)
         ent = (self.scst_entropy if scst else self.confidence_penalty) is not None     # (the very last element: the mean entropy)
-        i_nll = -2 if ent else -1
+        i_nll = -2 if (ent or kd) else -1
         self._active_buckets = self.shape_buckets if graphed else 0       # (read by _prepare, which the prefetcher calls)
         # batch k+1 is staged into HBM on a side stream while step k runs
         batches = DevicePrefetcher(self.train_loader, lambda raw: self._prepare(raw, True), self.device, limit=n_steps)
@@ -734,6 +773,10 @@ class Trainer:
                 meters["entropy"].update(sums[-1] / pending, n * pending)
                 meters["entropy"].val = cur[-1]
                 self.entropy_history.setdefault(epoch, []).append(sums[-1] / pending)
+            if kd:                                    # (the very last element: loop A's mean tau^2 KL(teacher || student))
+                meters["kd"].update(sums[-1] / pending, n * pending)
+                meters["kd"].val = cur[-1]
+                self.kd_history.setdefault(epoch, []).append(sums[-1] / pending)
             for name, i in (("lm", 1), ("attn", 2), ("cls", 3), ("recon", 4)):
                 meters[name].update(sums[i] / pending, n * pending)
                 meters[name].val = cur[i]
@@ -775,7 +818,8 @@ class Trainer:
                           ('\tReward {r.val:.4f} ({r.avg:.4f})'.format(r=meters["reward"]) if scst else '') +
                           ('\tSampled {s.val:.3f} ({s.avg:.3f})'.format(s=meters["sampled"]) if ss else '') +
                           ('\tNLL {s.val:.4f} ({s.avg:.4f})'.format(s=meters["nll"]) if smooth else '') +
-                          ('\tH {s.val:.4f} ({s.avg:.4f})'.format(s=meters["entropy"]) if ent else ''))
+                          ('\tH {s.val:.4f} ({s.avg:.4f})'.format(s=meters["entropy"]) if ent else '') +
+                          ('\tKD {s.val:.4f} ({s.avg:.4f})'.format(s=meters["kd"]) if kd else ''))
                 else:
                     if deferred and pending >= KEEP_MAX:
                         flush()
@@ -794,6 +838,8 @@ class Trainer:
                 tb_logger.add_scalar('train/lm_nll', meters["nll"].avg, epoch)
             if ent:
                 tb_logger.add_scalar('train/entropy', meters["entropy"].avg, epoch)
+            if kd:
+                tb_logger.add_scalar('train/kd', meters["kd"].avg, epoch)
 
     def _segment_timestamps(self):
         """{video: {segment: [start, end]}} of the validation segments: the reference reads them from the ANet-Entities

@@ -754,6 +754,36 @@ int cvc_ensemble_logprobs(const cvc_ensemble_src* src, int M, const float* logw,
  * of M device pointers, logw: HOST memory; both travel in the kernel's arguments.  out may not alias a source other than src[0]. */
 int cvc_ensemble_mix(const float* const* src, int M, const float* logw, long long n, float* out, cvc_stream_t stream);
 
+/* ---- word-level distillation in the vocabulary criterion (csrc/distill.hip; cvc.functional.vocab_head_nll / vocab_nll distill=):
+ * the criterion against a dense target row, a teacher's next-word distribution (Hinton et al. 2015; Kim & Rush 2016), mixed with the
+ * one-hot loss.  Per row m with student logits z (the slabs summed in cvc_vocab_head_nll_fwd's order), teacher scores
+ * s = teacher + map[m] * ld_t (any log-scale row, normalised or not; row_map NULL: map[m] = m; int32, device memory), alpha in [0, 1]
+ * and tau > 0, with p = softmax(z), p_tau = softmax(z / tau), q = softmax(s / tau):
+ *   row_nll  = w (lse(z) - z[t])                              unmixed
+ *   row_kd   = w tau^2 sum_v q[v] (log q[v] - log p_tau[v])   unmixed; a teacher entry at -inf adds an exact 0
+ *   row_loss = (1 - alpha) row_nll + alpha row_kd
+ *   pre[v] / d_logits[v] = (g[0]) w ((1 - alpha) (p[v] - [v == t]) + alpha tau (p_tau[v] - q[v]))
+ * loss_sum / nll_sum / kd_sum: the rows added in a fixed order, one launch behind the row kernel.  w == 0: an exactly zero row
+ * whatever the teacher row holds.  A mapped teacher row outside [0, t_rows) is not read: that row's loss, kd and pre are NaN.
+ * The fused form keeps both rows in registers (V <= 8192) and `pre` may alias slab 0; the two-step form takes any V and leaves
+ * stats [5, M] for its backward (contents are the forward's own business).  On equal fp32 logits the two forms agree bit for bit.
+ * fp32 only: the row values and their sums are carried as an fp32 value plus an fp32 remainder (error-free sums, fma products, a
+ * split logarithm) and rounded once -- a row's KL is a small difference of large sums; pre / d_logits are plain fp32.  Fixed-order
+ * reductions, no atomics, no workspace: capturable, bitwise deterministic.
+ * Null pointers (but bias, argmax, row_map), alpha outside [0, 1], tau not finite or <= 0, ld_t < V (ld, ld_pre likewise), t_rows < 1,
+ * the fused form's V > 8192: CVC_E_BADARG, before any launch. */
+int cvc_vocab_head_nll_kd_fwd(const float* parts, int nparts, long long part_stride, int ld, const float* bias,
+                              const int64_t* target, const float* w, const float* teacher, int ld_t, const int* row_map, int t_rows,
+                              int M, int V, float alpha, float tau, float* pre, int ld_pre, int64_t* argmax, float* row_loss,
+                              float* loss_sum, float* row_nll, float* nll_sum, float* row_kd, float* kd_sum, cvc_stream_t stream);
+int cvc_vocab_nll_kd_fwd(const float* logits, const int64_t* target, const float* w, const float* teacher, int ld_t,
+                         const int* row_map, int t_rows, int M, int V, float alpha, float tau, float* stats, int64_t* argmax,
+                         float* row_loss, float* loss_sum, float* row_nll, float* nll_sum, float* row_kd, float* kd_sum,
+                         cvc_stream_t stream);
+int cvc_vocab_nll_kd_bwd(const float* logits, const float* stats, const int64_t* target, const float* w, const float* teacher,
+                         int ld_t, const int* row_map, int t_rows, const float* g, int M, int V, float alpha, float tau,
+                         float* d_logits, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
