@@ -1,7 +1,7 @@
 """fp64 restatement of the recurrent half of nn.LSTM(batch_first=True, bias=True) with h0 = c0 = 0 (gate order i, f, g, o; direction 1
 walks the sequence from the end): the forward keeping every step's activated gates and c_t, and the backward written out from those
 saved tensors.  tests/test_lstm_seq_cpu.py proves it against nn.LSTM(...).double() and its autograd; the GPU tests use it as their
-reference (tests/test_gpu_lstm_seq.py)."""
+reference (tests/test_gpu_lstm_seq.py, tests/test_gpu_lstm_seq_kernels.py through tests/lstm_seq_cases.py)."""
 import torch
 
 
@@ -9,22 +9,28 @@ def _sfx(bidir):
     return ["", "_reverse"] if bidir else [""]
 
 
-def lstm_layer_forward(x, w_ih, w_hh, b_ih, b_hh, reverse):
-    """x [B, F, in] (fp64) -> y [B, F, H], gates [B, F, 4, H] (activated i, f, g, o), c [B, F, H]"""
-    B, F, _ = x.shape
+def lstm_recurrence(gi, w_hh, b_ih, b_hh, reverse):
+    """the recurrence alone, from the input projections gi = x W_ih^T [B, F, 4H] (fp64, no bias) -> y [B, F, H], gates [B, F, 4, H]
+    (activated i, f, g, o), c [B, F, H]"""
+    B, F, _ = gi.shape
     H = w_hh.shape[1]
-    h = x.new_zeros(B, H)
-    c = x.new_zeros(B, H)
-    y, gates, cs = x.new_zeros(B, F, H), x.new_zeros(B, F, 4, H), x.new_zeros(B, F, H)
+    h = gi.new_zeros(B, H)
+    c = gi.new_zeros(B, H)
+    y, gates, cs = gi.new_zeros(B, F, H), gi.new_zeros(B, F, 4, H), gi.new_zeros(B, F, H)
     for s in range(F):
         t = F - 1 - s if reverse else s
-        z = (x[:, t] @ w_ih.T + b_ih + h @ w_hh.T + b_hh).view(B, 4, H)
+        z = (gi[:, t] + b_ih + h @ w_hh.T + b_hh).view(B, 4, H)
         i, f, g, o = torch.sigmoid(z[:, 0]), torch.sigmoid(z[:, 1]), torch.tanh(z[:, 2]), torch.sigmoid(z[:, 3])
         c = f * c + i * g
         h = o * torch.tanh(c)
         y[:, t], cs[:, t] = h, c
         gates[:, t] = torch.stack((i, f, g, o), 1)
     return y, gates, cs
+
+
+def lstm_layer_forward(x, w_ih, w_hh, b_ih, b_hh, reverse):
+    """x [B, F, in] (fp64) -> y [B, F, H], gates [B, F, 4, H] (activated i, f, g, o), c [B, F, H]"""
+    return lstm_recurrence(x @ w_ih.T, w_hh, b_ih, b_hh, reverse)
 
 
 def lstm_layer_backward(dy, x, y, gates, cs, w_ih, w_hh, reverse):
@@ -91,6 +97,12 @@ def lstm_backward(dy, saved, params, layers, bidir, masks=None):
     return d_out, grads
 
 
-def make_lstm(inp, H, layers, bidir, seed, dropout=0.0):
+def make_lstm(inp, H, layers, bidir, seed, dropout=0.0, scale=1.0):
+    """nn.LSTM at its own initialisation; scale = 1.5 (as gru_ref.make_gru has it) takes the gates out of their linear region"""
     torch.manual_seed(seed)
-    return torch.nn.LSTM(inp, H, layers, dropout=dropout, bidirectional=bidir, batch_first=True)
+    lstm = torch.nn.LSTM(inp, H, layers, dropout=dropout, bidirectional=bidir, batch_first=True)
+    if scale != 1.0:
+        with torch.no_grad():
+            for p in lstm.parameters():
+                p.mul_(scale)
+    return lstm

@@ -5,7 +5,11 @@ nn.LSTM in tests/test_lstm_seq_cpu.py), the building blocks by name, and the enc
 
 Tolerances are the GRU's (tests/test_encoder.py): 5e-5 max-abs / rtol 1e-4 on outputs, 1e-4 relative norm on gradients; they were
 not widened for the LSTM.  Measured on an MI355X: outputs 1.0e-7 .. 1.9e-7 from fp64 at the shapes below (saved gates and c
-1.9e-7), the two forms 0 .. 1.8e-7 from each other, 5.5e-7 from fp32 nn.LSTM on the host at config-2 size (F = 480, |y| <= 0.28)."""
+1.9e-7), the two forms 0 .. 1.8e-7 from each other, 5.5e-7 from fp32 nn.LSTM on the host at config-2 size (F = 480, |y| <= 0.28).
+
+This file is the path as the product runs it, at the workload's sizes, with gradients checked by norm.  The kernels themselves --
+every entry point of csrc/lstm_seq.hip by name, isolated from the tile GEMM, every instantiation, strided layouts, poisoned
+padding and workspaces, gradients element-wise -- are pinned in tests/test_gpu_lstm_seq_kernels.py."""
 import ctypes
 
 import numpy as np

@@ -1174,7 +1174,10 @@ def test_product_path_has_no_cpu_fallback(lib):
     x = torch.zeros(4, 8)
     w = torch.zeros(8, 8)
     with pytest.raises(RuntimeError, match="GPU"):
-        F_.linear(x, w, None)@pytest.mark.gpu
+        F_.linear(x, w, None)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("M,R,widths", [(64, 64, (32, 64, 32)), (20, 128, (64, 128, 96)), (3, 40, (20, 36)), (64, 1024, (512, 1024, 512))])
 def test_lstm_train_form_of_packed_gemm(dev, lib, M, R, widths):
     """Training forward of nn.LSTMCell on the decode engine's packed gate GEMM (cvc_pack_lstm_weights + cvc_pack_quad_segs +
