@@ -102,12 +102,15 @@ __global__ __launch_bounds__(OPT_WG) void optim_adam_kernel(const OptSeg* segs, 
     const float bc1 = 1.0f - powf(beta1, t), bc2 = 1.0f - powf(beta2, t);
     const float step_size = s.lr / bc1, inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
     const float wd = s.weight_decay, omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
+    // Every product-and-sum is an explicit fmaf: left to the compiler's contraction, the float4 loop fused g + wd * p and
+    // beta2 * v + ... while the scalar loops (a misaligned operand, the < 4 tail elements of an aligned one) rounded the products
+    // first, and the same values gave other bits depending on where the allocator had put them.  These are the float4 loop's bits.
     auto upd = [&](float& p, float& g, float& m, float& v) __attribute__((always_inline)) {
         g *= coef;
-        const float ge = wd != 0.f ? g + wd * p : g;
-        m = m + (ge - m) * omb1;
-        v = beta2 * v + omb2 * ge * ge;
-        p -= step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps));
+        const float ge = wd != 0.f ? fmaf(wd, p, g) : g;
+        m = fmaf(ge - m, omb1, m);
+        v = fmaf(beta2, v, (omb2 * ge) * ge);
+        p = fmaf(-step_size, m / fmaf(sqrtf(v), inv_sqrt_bc2, eps), p);
     };
     const bool al = ((((uintptr_t)s.p) | ((uintptr_t)s.g) | ((uintptr_t)s.m) | ((uintptr_t)s.v)) & 15) == 0;
     if (al) {
