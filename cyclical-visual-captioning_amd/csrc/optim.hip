@@ -11,6 +11,11 @@
 //     m   = m + (g - m) * (1 - beta1)           v = beta2 * v + (1 - beta2) * g * g
 //     p  -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)          t = the segment's step count after this step
 // Sums of squares are taken chunk by chunk and combined in chunk order: the norm is the same bits run to run.
+//
+// The reference's other two optimizers (main.py:182-191: sgd with momentum 0.9, adamax) take the same first two launches and their
+// own update kernel in the third (cvc_sgd_clip_step, cvc_adamax_clip_step: building blocks, include/cvc_hip_blocks.h):
+//     buf = mom * buf + g                       p -= lr * buf                                    torch.optim.SGD, dampening 0
+//     m   = m + (g - m) * (1 - beta1)           u = max(beta2 * u, |g| + eps)    p -= (lr / (1 - beta1^t)) * m / u     torch.optim.Adamax
 #include "cvc_common.h"
 #include <math.h>
 
@@ -81,7 +86,9 @@ __global__ __launch_bounds__(OPT_WG) void optim_finalize_kernel(const OptSeg* se
         // a NaN norm poisons every gradient, as torch's clip_grad_norm_ does (clamp(NaN, max=1) = NaN; fminf would return 1)
         out[1] = max_norm > 0.f ? (total != total ? total : fminf(max_norm / (total + 1e-6f), 1.0f) * inv) : inv;
     }
-    for (int s = threadIdx.x; s < nseg; s += OPT_WG) segs[s].step[0] += 1.0f;
+    // (a rule without a step count -- SGD -- leaves the segment's `step` NULL)
+    for (int s = threadIdx.x; s < nseg; s += OPT_WG)
+        if (segs[s].step) segs[s].step[0] += 1.0f;
 }
 
 __global__ __launch_bounds__(OPT_WG) void optim_adam_kernel(const OptSeg* segs, const OptChunk* chunks, const float* norm_coef, float beta1,
@@ -143,6 +150,106 @@ __global__ __launch_bounds__(OPT_WG) void optim_adam_kernel(const OptSeg* segs, 
     }
 }
 
+// ---- SGD with momentum and Adamax: the same three launches, another third kernel.  One chunk of one segment under `upd`, with
+// NS state arrays next to p and g (0: none, 1: m, 2: m and v): optim_adam_kernel's loops -- float4 when every operand the rule
+// has is 16-byte aligned, scalar for the < 4 tail elements and for a misaligned operand -- and its write_grad / void-step rules.
+template <int NS, class Upd>
+__device__ __forceinline__ void optim_rule_pass(const OptSeg& s, long long start, long long end, int write_grad, bool is_void, Upd upd) {
+    if (is_void) {                             // p and the state stay as they are; write_grad == 2 still leaves the gradients zero
+        if (write_grad == 2)
+            for (long long i = start + threadIdx.x; i < end; i += OPT_WG) s.g[i] = 0.f;
+        return;
+    }
+    auto one = [&](long long i) __attribute__((always_inline)) {
+        float p = s.p[i], g = s.g[i], m = 0.f, v = 0.f;
+        if constexpr (NS >= 1) m = s.m[i];
+        if constexpr (NS >= 2) v = s.v[i];
+        upd(p, g, m, v);
+        s.p[i] = p;
+        if constexpr (NS >= 1) s.m[i] = m;
+        if constexpr (NS >= 2) s.v[i] = v;
+        if (write_grad) s.g[i] = write_grad == 2 ? 0.f : g;
+    };
+    uintptr_t addr = ((uintptr_t)s.p) | ((uintptr_t)s.g);
+    if constexpr (NS >= 1) addr |= (uintptr_t)s.m;
+    if constexpr (NS >= 2) addr |= (uintptr_t)s.v;
+    if ((addr & 15) == 0) {
+        long long i = start + (long long)threadIdx.x * 4;
+        for (; i + 4 <= end; i += OPT_WG * 4) {
+            f32x4 p = ld4(s.p + i), g = ld4(s.g + i), m = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (NS >= 1) m = ld4(s.m + i);
+            if constexpr (NS >= 2) v = ld4(s.v + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = p[e], ge = g[e], me = m[e], ve = v[e];
+                upd(pe, ge, me, ve);
+                p[e] = pe; g[e] = ge; m[e] = me; v[e] = ve;
+            }
+            st4(s.p + i, p);
+            if constexpr (NS >= 1) st4(s.m + i, m);
+            if constexpr (NS >= 2) st4(s.v + i, v);
+            if (write_grad == 1) st4(s.g + i, g);
+            else if (write_grad == 2) st4(s.g + i, f32x4{0.f, 0.f, 0.f, 0.f});
+        }
+        for (; i < end; ++i) one(i);
+    } else {
+        for (long long i = start + threadIdx.x; i < end; i += OPT_WG) one(i);
+    }
+}
+
+// torch.optim.SGD (dampening 0, no Nesterov, no maximize).  m = momentum_buffer; a zero buffer gives torch's first step (buf = ge)
+// exactly.  A segment whose m is NULL has no buffer (momentum 0, as torch keeps none): p -= lr ge.
+__global__ __launch_bounds__(OPT_WG) void optim_sgd_kernel(const OptSeg* segs, const OptChunk* chunks, const float* norm_coef, float mom,
+                                                           int write_grad, const int* skip) {
+    const OptChunk c = chunks[blockIdx.x];
+    const OptSeg s = segs[c.seg];
+    const long long end = c.start + OPT_CHUNK < s.n ? c.start + OPT_CHUNK : s.n;
+    const bool is_void = skip && *skip != 0;
+    const float coef = norm_coef[1], wd = s.weight_decay, nlr = -s.lr;
+    // The same bits in every form, as in optim_adam_kernel: contraction is off, so what is fused is what is spelled fmaf.  One
+    // operation is deliberately NOT fused, the buffer's update below.
+    if (s.m != nullptr) {
+        optim_rule_pass<1>(s, c.start, end, write_grad, is_void, [&](float& p, float& g, float& m, float&) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+            g *= coef;
+            const float ge = wd != 0.f ? fmaf(wd, p, g) : g;
+            // Product rounded, then the sum, as torch's buf.mul_(mom).add_(g): where mom buf and g cancel (a buffer of 9, a gradient
+            // of -8) an fma differs from torch by an ulp of the PRODUCT, and the buffer is state, so the difference is carried into
+            // every later step.  Rounded as torch rounds it, the buffer follows torch's.
+            m = mom * m + ge;
+            p = fmaf(nlr, m, p);
+        });
+    } else {
+        optim_rule_pass<0>(s, c.start, end, write_grad, is_void, [&](float& p, float& g, float&, float&) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+            g *= coef;
+            const float ge = wd != 0.f ? fmaf(wd, p, g) : g;
+            p = fmaf(nlr, ge, p);
+        });
+    }
+}
+
+// torch.optim.Adamax (no maximize).  m = exp_avg, v = exp_inf, t = the segment's step count after the finalize launch's += 1.
+__global__ __launch_bounds__(OPT_WG) void optim_adamax_kernel(const OptSeg* segs, const OptChunk* chunks, const float* norm_coef, float beta1,
+                                                              float beta2, float eps, int write_grad, const int* skip) {
+    const OptChunk c = chunks[blockIdx.x];
+    const OptSeg s = segs[c.seg];
+    const long long end = c.start + OPT_CHUNK < s.n ? c.start + OPT_CHUNK : s.n;
+    const bool is_void = skip && *skip != 0;
+    const float coef = norm_coef[1], wd = s.weight_decay, omb1 = 1.0f - beta1;
+    const float nclr = -(s.lr / (1.0f - powf(beta1, s.step[0])));           // bias correction as torch computes it (fp32 pow)
+    optim_rule_pass<2>(s, c.start, end, write_grad, is_void, [&](float& p, float& g, float& m, float& u) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+        g *= coef;
+        const float ge = wd != 0.f ? fmaf(wd, p, g) : g;
+        m = fmaf(ge - m, omb1, m);
+        // torch.maximum: a NaN on either side is the result (fmaxf would drop it and a NaN gradient would leave no trace in u)
+        const float a = beta2 * u, b = fabsf(ge) + eps;
+        u = a != a ? a : (b != b ? b : fmaxf(a, b));
+        p = fmaf(nclr, m / u, p);
+    });
+}
+
 }  // namespace
 
 extern "C" int cvc_optim_chunk_elems(void) { return OPT_CHUNK; }
@@ -160,5 +267,41 @@ extern "C" int cvc_adam_clip_step(const cvc_optim_seg* segs, int nseg, const cvc
     hipLaunchKernelGGL(optim_sumsq_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, partial);
     hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(OPT_WG), 0, st, s, nseg, partial, nchunk, max_norm, inv_world, norm_coef, skip);
     hipLaunchKernelGGL(optim_adam_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, norm_coef, beta1, beta2, eps, write_grad, skip);
+    return cvc_launch_status();
+}
+
+namespace {
+bool optim_tables_ok(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float inv_world, const float* partial,
+                     const float* norm_coef) {
+    return segs && chunks && partial && norm_coef && nseg >= 1 && nchunk >= 1 && inv_world > 0.f;
+}
+}  // namespace
+
+// building blocks (include/cvc_hip_blocks.h): cvc_adam_clip_step's three launches with another update rule in the third
+extern "C" int cvc_sgd_clip_step(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                                 float inv_world, float momentum, int write_grad, float* partial, float* norm_coef, const int* skip,
+                                 cvc_stream_t stream) {
+    if (!optim_tables_ok(segs, nseg, chunks, nchunk, inv_world, partial, norm_coef) || !(momentum >= 0.f && momentum < 1.f)) return CVC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const OptSeg* s = reinterpret_cast<const OptSeg*>(segs);
+    const OptChunk* c = reinterpret_cast<const OptChunk*>(chunks);
+    hipLaunchKernelGGL(optim_sumsq_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, partial);
+    hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(OPT_WG), 0, st, s, nseg, partial, nchunk, max_norm, inv_world, norm_coef, skip);
+    hipLaunchKernelGGL(optim_sgd_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, norm_coef, momentum, write_grad, skip);
+    return cvc_launch_status();
+}
+
+extern "C" int cvc_adamax_clip_step(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                                    float inv_world, float beta1, float beta2, float eps, int write_grad, float* partial,
+                                    float* norm_coef, const int* skip, cvc_stream_t stream) {
+    if (!optim_tables_ok(segs, nseg, chunks, nchunk, inv_world, partial, norm_coef) || !(beta1 >= 0.f && beta1 < 1.f) ||
+        !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f))
+        return CVC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const OptSeg* s = reinterpret_cast<const OptSeg*>(segs);
+    const OptChunk* c = reinterpret_cast<const OptChunk*>(chunks);
+    hipLaunchKernelGGL(optim_sumsq_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, partial);
+    hipLaunchKernelGGL(optim_finalize_kernel, dim3(1), dim3(OPT_WG), 0, st, s, nseg, partial, nchunk, max_norm, inv_world, norm_coef, skip);
+    hipLaunchKernelGGL(optim_adamax_kernel, dim3(nchunk), dim3(OPT_WG), 0, st, s, c, norm_coef, beta1, beta2, eps, write_grad, skip);
     return cvc_launch_status();
 }

@@ -1,4 +1,5 @@
-"""Adam with the gradient clip folded into its step -- the optimizer side of the training path on the HIP kernels.
+"""The reference's three optimizers (main.py:182-191: adam, sgd, adamax) with the gradient clip folded into their step -- the
+optimizer side of the training path on the HIP kernels.
 
 `ClipAdam` IS a torch.optim.Adam (same constructor arguments, param groups, `state_dict()` layout: per-parameter `step`,
 `exp_avg`, `exp_avg_sq`), so checkpoints, LR schedulers and resume code see nothing new.  What changes is how a step is taken
@@ -7,8 +8,14 @@ trainer (trainer.py:116-122) in three launches of csrc/optim.hip (norm partials,
 p / g / m / v) with nothing read back by the host -- the library path takes a norm reduction per gradient bucket, a multiply
 over every gradient and the fused Adam's own pass.  `step()` alone is the unclipped update on the same kernel.
 
-Parameters whose .grad is None are skipped, as torch.optim.Adam skips them (no state, no step count, no weight decay).
-amsgrad / maximize / differentiable are not taken: the reference never sets them (main.py:171-191)."""
+`ClipSGD` IS a torch.optim.SGD (state `momentum_buffer`; dampening 0, no Nesterov) and `ClipAdamax` a torch.optim.Adamax (state
+`step`, `exp_avg`, `exp_inf`) in the same way: the same first two launches, their own update kernel in the third
+(cvc_sgd_clip_step, cvc_adamax_clip_step of include/cvc_hip_blocks.h).  What is not the update rule -- the segment and chunk
+tables keyed on the tensors' addresses, the in-place rewrite of lr / weight_decay, the tables a rebuild retires, clip_and_step's
+arguments, last_norm -- is `_ClipStep`, shared by the three.
+
+Parameters whose .grad is None are skipped, as the torch optimizers skip them (no state, no step count, no weight decay).
+amsgrad / nesterov / dampening / maximize / differentiable are not taken: the reference never sets them (main.py:171-191)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,53 +30,48 @@ _SEG_DT = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("st
 _CHUNK_DT = np.dtype([("seg", "<i4"), ("pad", "<i4"), ("start", "<i8")])
 
 
-class ClipAdam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kw):
-        for k in ("amsgrad", "maximize", "differentiable"):
-            if kw.pop(k, False):
-                raise ValueError(f"ClipAdam: {k} is not supported")
-        kw.pop("fused", None); kw.pop("foreach", None); kw.pop("capturable", None)
-        # capturable=True: the step counters are float32 tensors on the parameters' device, which is what the kernel increments
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=True, foreach=False, fused=False)
-        self._table = None          # (key, device segment table, chunk table, scratch, norm_coef, ...)
+def _refuse(name, kw, keys):
+    for k in keys:
+        if kw.pop(k, False):
+            raise ValueError(f"{name}: {k} is not supported")
+
+
+class _ClipStep:
+    """What the three optimizers share.  A subclass gives
+         _rule()            the scalars every param group must share (a tuple; raises ValueError when the groups differ)
+         _state(p, group)   (m, v, step) of one parameter with a gradient: its state tensors, created on first use; None = the rule
+                            has no such operand
+         _launch(...)       the C entry's return code"""
+
+    def _init_clip(self):
+        self._table = None          # (key, device segment table, chunk table, scratch, norm_coef, nseg, nchunk, *rule)
         self._seg_host = None       # host copy of the segment table (lr / weight_decay are rewritten in place when they change)
         self._retired = []          # tables replaced by a rebuild: kept alive, a captured HIP graph may still replay on them
         self.last_norm: Optional[torch.Tensor] = None       # device scalar: norm of the (averaged) gradient of the last clipped step
 
-    # ------------------------------------------------------------------ state, exactly as torch.optim.Adam lays it out
-    def _ensure_state(self, p):
-        st = self.state[p]
-        if len(st) == 0:
-            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return st
+    def _device_step(self, st, p):
+        """the state's `step` as a float32 scalar on the parameter's device (a state_dict loaded from a CPU-step checkpoint is moved)"""
+        if not (st["step"].is_cuda and st["step"].dtype == torch.float32):
+            st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=p.device)
+        return st["step"]
 
     def _build_table(self):
-        segs, keep, key = [], [], []
-        betas = eps = None
+        name = type(self).__name__
+        segs, key = [], []
+        rule = self._rule()
         for group in self.param_groups:
-            b = tuple(float(x) for x in group["betas"])
-            e = float(group["eps"])
-            if betas is None:
-                betas, eps = b, e
-            elif (betas, eps) != (b, e):
-                raise ValueError("ClipAdam: all param groups must share betas and eps (they do in the reference, main.py:171-191)")
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()
                         and p.grad.dtype == torch.float32):
-                    raise RuntimeError("ClipAdam: contiguous float32 GPU parameters and gradients only (no CPU fallback)")
-                st = self._ensure_state(p)
-                if not (st["step"].is_cuda and st["step"].dtype == torch.float32):      # a state_dict loaded from a CPU-step checkpoint
-                    st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=p.device)
-                lr = group["lr"]
-                segs.append((p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"], float(lr), float(group["weight_decay"])))
-                key.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()))
+                    raise RuntimeError(f"{name}: contiguous float32 GPU parameters and gradients only (no CPU fallback)")
+                m, v, step = self._state(p, group)
+                segs.append((p, p.grad, m, v, step, float(group["lr"]), float(group["weight_decay"])))
+                key.append((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in (m, v, step)))
         if not segs:
             return None
-        key = (tuple(key), betas, eps)
+        key = (tuple(key),) + rule
         if self._table is not None and self._table[0] == key:
             # same tensors: only the learning rates / weight decays may have moved (a scheduler).  They live in the device table,
             # rewritten IN PLACE so that a captured graph replaying this table honours them
@@ -84,7 +86,10 @@ class ClipAdam(torch.optim.Adam):
         seg_np = np.zeros(len(segs), dtype=_SEG_DT)
         assert seg_np.itemsize == C.sizeof(hip.OptimSeg) and _CHUNK_DT.itemsize == C.sizeof(hip.OptimChunk)
         for i, (p, g, m, v, step, lr, wd) in enumerate(segs):
-            seg_np[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(), p.numel(), lr, wd)
+            for t in (g, m, v):            # (the kernels index every operand with the parameter's element count)
+                if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()):
+                    raise RuntimeError(f"{name}: contiguous float32 GPU parameters and gradients only (no CPU fallback)")
+            seg_np[i] = (p.data_ptr(), g.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in (m, v, step)) + (p.numel(), lr, wd)
         counts = np.array([(p.numel() + chunk - 1) // chunk for p, *_ in segs], dtype=np.int64)
         chunk_np = np.zeros(int(counts.sum()), dtype=_CHUNK_DT)
         chunk_np["seg"] = np.repeat(np.arange(len(segs), dtype=np.int32), counts)
@@ -97,7 +102,7 @@ class ClipAdam(torch.optim.Adam):
         if self._table is not None:
             self._retired.append(self._table)
         self._seg_host = seg_np
-        self._table = (key, seg_t, chunk_t, partial, norm_coef, len(segs), len(chunk_np), betas, eps)
+        self._table = (key, seg_t, chunk_t, partial, norm_coef, len(segs), len(chunk_np)) + rule
         return self._table
 
     def sync_hyperparameters(self):
@@ -116,15 +121,16 @@ class ClipAdam(torch.optim.Adam):
         norm as a device scalar.  skip: a device int32 word (cvc.hip.step_status); non-zero when the pass executes = the step is void,
         nothing but the gradients' zeroing happens (see include/cvc_hip.h)."""
         if skip is not None and not (skip.is_cuda and skip.dtype == torch.int32 and skip.numel() >= 1):
-            raise TypeError("ClipAdam.clip_and_step: skip must be an int32 tensor on the GPU")
+            raise TypeError(f"{type(self).__name__}.clip_and_step: skip must be an int32 tensor on the GPU")
         t = self._build_table()
         if t is None:
             return None
-        _key, seg_t, chunk_t, partial, norm_coef, nseg, nchunk, betas, eps = t
-        hip._check(hip.lib().cvc_adam_clip_step(seg_t.data_ptr(), nseg, chunk_t.data_ptr(), nchunk, float(max_norm), float(inv_world),
-                                                betas[0], betas[1], eps, 2 if zero_grad else (1 if write_grad else 0), partial.data_ptr(),
-                                                norm_coef.data_ptr(), skip.data_ptr() if skip is not None else None, hip._stream()),
-                   "cvc_adam_clip_step")
+        _key, seg_t, chunk_t, partial, norm_coef, nseg, nchunk = t[:7]
+        entry, rule_args = self._launch(t)
+        hip._check(getattr(hip.lib(), entry)(seg_t.data_ptr(), nseg, chunk_t.data_ptr(), nchunk, float(max_norm), float(inv_world),
+                                             *rule_args, 2 if zero_grad else (1 if write_grad else 0), partial.data_ptr(),
+                                             norm_coef.data_ptr(), skip.data_ptr() if skip is not None else None, hip._stream()),
+                   entry)
         self.last_norm = norm_coef[0]
         return self.last_norm
 
@@ -136,3 +142,104 @@ class ClipAdam(torch.optim.Adam):
                 loss = closure()
         self.clip_and_step(0.0, 1.0, write_grad=False)
         return loss
+
+    def _shared(self, what, pick):
+        """the one value of pick(group) over the param groups"""
+        vals = {pick(g) for g in self.param_groups}
+        if len(vals) != 1:
+            raise ValueError(f"{type(self).__name__}: all param groups must share {what} (they do in the reference, main.py:171-191)")
+        return vals.pop()
+
+
+class ClipAdam(_ClipStep, torch.optim.Adam):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kw):
+        _refuse("ClipAdam", kw, ("amsgrad", "maximize", "differentiable"))
+        kw.pop("fused", None); kw.pop("foreach", None); kw.pop("capturable", None)
+        # capturable=True: the step counters are float32 tensors on the parameters' device, which is what the kernel increments
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=True, foreach=False, fused=False)
+        self._init_clip()
+
+    # ------------------------------------------------------------------ state, exactly as torch.optim.Adam lays it out
+    def _ensure_state(self, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def _rule(self):
+        return self._shared("betas and eps", lambda g: (tuple(float(x) for x in g["betas"]), float(g["eps"])))
+
+    def _state(self, p, group):
+        st = self._ensure_state(p)
+        return st["exp_avg"], st["exp_avg_sq"], self._device_step(st, p)
+
+    def _launch(self, t):
+        betas, eps = t[7:]
+        return "cvc_adam_clip_step", (betas[0], betas[1], eps)
+
+
+class ClipSGD(_ClipStep, torch.optim.SGD):
+    """torch.optim.SGD(momentum=...) behind the clip: dampening 0, no Nesterov (what the reference builds, main.py:183)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, **kw):
+        _refuse("ClipSGD", kw, ("maximize", "differentiable"))
+        if nesterov:
+            raise ValueError("ClipSGD: nesterov is not supported")
+        if dampening != 0:
+            raise ValueError("ClipSGD: dampening is not supported")
+        kw.pop("fused", None); kw.pop("foreach", None)
+        if kw:
+            raise TypeError(f"ClipSGD: unexpected arguments {sorted(kw)}")
+        super().__init__(params, lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False, foreach=False, fused=False)
+        self._init_clip()
+
+    def _rule(self):
+        for g in self.param_groups:
+            if g.get("nesterov") or g.get("dampening", 0) != 0 or g.get("maximize"):
+                raise ValueError("ClipSGD: nesterov / dampening / maximize are not supported")
+        mom = self._shared("momentum", lambda g: float(g["momentum"]))
+        if not 0.0 <= mom < 1.0:
+            raise ValueError(f"ClipSGD: momentum must lie in [0, 1), got {mom}")
+        return (mom,)
+
+    def _state(self, p, group):
+        if group["momentum"] == 0:
+            return None, None, None                      # no buffer, as torch keeps none
+        st = self.state[p]
+        if st.get("momentum_buffer") is None:            # first use, or a state saved before torch's first step (its buffer is None):
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)     # buf = mom 0 + ge is torch's first step
+        return st["momentum_buffer"], None, None
+
+    def _launch(self, t):
+        return "cvc_sgd_clip_step", (t[7],)
+
+
+class ClipAdamax(_ClipStep, torch.optim.Adamax):
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kw):
+        _refuse("ClipAdamax", kw, ("maximize", "differentiable"))
+        kw.pop("foreach", None); kw.pop("capturable", None)
+        if kw:
+            raise TypeError(f"ClipAdamax: unexpected arguments {sorted(kw)}")
+        # capturable=True: the step counters are float32 tensors on the parameters' device, which is what the kernel increments
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=False, capturable=True)
+        self._init_clip()
+
+    def _rule(self):
+        betas, eps = self._shared("betas and eps", lambda g: (tuple(float(x) for x in g["betas"]), float(g["eps"])))
+        if any(g.get("maximize") for g in self.param_groups):
+            raise ValueError("ClipAdamax: maximize is not supported")
+        return betas, eps
+
+    def _state(self, p, group):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_inf"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st["exp_avg"], st["exp_inf"], self._device_step(st, p)
+
+    def _launch(self, t):
+        betas, eps = t[7:]
+        return "cvc_adamax_clip_step", (betas[0], betas[1], eps)

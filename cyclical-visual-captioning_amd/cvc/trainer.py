@@ -1327,7 +1327,7 @@ def write_grounding_json(grd_output, o, stem='attn-gen-sent-results', eval_mode=
     return path
 
 
-CLIP_ADAM = os.environ.get("CVC_CLIP_ADAM", "1") != "0"      # False: torch.optim.Adam (fused) + the library's clip (A/B)
+CLIP_ADAM = os.environ.get("CVC_CLIP_ADAM", "1") != "0"      # False: torch.optim.Adam (fused) / SGD / Adamax + the library's clip (A/B)
 
 
 def build_optimizer(model, opt, capturable: bool = False):
@@ -1339,8 +1339,15 @@ def build_optimizer(model, opt, capturable: bool = False):
             continue
         lr = opt.learning_rate * (0.1 if ('ctx2pool_grd' in key or 'vis_embed' in key) else 1.0)
         params.append({'params': [value], 'lr': lr, 'weight_decay': opt.weight_decay, 'betas': (opt.optim_alpha, opt.optim_beta)})
+    # every parameter on the GPU and CVC_CLIP_ADAM != 0: clip_grad_norm_ + step in one pass (cvc.optim, csrc/optim.hip), for all
+    # three of the reference's optimizers -- which is also what lets --hip_graph and deferred error words take the step
+    clip_step = CLIP_ADAM and all(p['params'][0].is_cuda for p in params)
     if opt.optim == 'sgd':
-        return torch.optim.SGD([{k: v for k, v in p.items() if k != 'betas'} for p in params], lr=opt.learning_rate, momentum=0.9)
+        groups = [{k: v for k, v in p.items() if k != 'betas'} for p in params]
+        if clip_step:
+            from .optim import ClipSGD
+            return ClipSGD(groups, lr=opt.learning_rate, momentum=0.9)
+        return torch.optim.SGD(groups, lr=opt.learning_rate, momentum=0.9)
     if opt.optim == 'adam':
         # fused = one pass over (p, g, m, v) per tensor instead of the foreach path's ~9 passes (Adam was 8 % of the step)
         fused = all(p['params'][0].is_cuda for p in params)
@@ -1349,5 +1356,8 @@ def build_optimizer(model, opt, capturable: bool = False):
             return ClipAdam(params)
         return torch.optim.Adam(params, capturable=capturable, fused=fused)
     if opt.optim == 'adamax':
-        return torch.optim.Adamax(params)
+        if clip_step:
+            from .optim import ClipAdamax
+            return ClipAdamax(params)
+        return torch.optim.Adamax(params, capturable=capturable)
     raise ValueError('Unknown optimizer: {}'.format(opt.optim))

@@ -797,6 +797,8 @@ CVC_API int cvc_train_loop_profile_read(int* kind, int* loop, float* ms, int cap
 typedef struct {
     float *p, *g, *m, *v;     /* parameter, gradient, exp_avg, exp_avg_sq: n floats each */
     float* step;              /* the parameter's step count, one float32 on the device (torch's `step` state) */
+                              /* (the SGD and Adamax blocks of cvc_hip_blocks.h read the same table: there m / v are the rule's
+                                 state arrays, and what a rule does not have -- SGD's v and step -- is NULL) */
     long long n;
     float lr, weight_decay;
 } cvc_optim_seg;

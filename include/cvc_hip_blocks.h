@@ -784,6 +784,35 @@ int cvc_vocab_nll_kd_bwd(const float* logits, const float* stats, const int64_t*
                          int ld_t, const int* row_map, int t_rows, const float* g, int M, int V, float alpha, float tau,
                          float* d_logits, cvc_stream_t stream);
 
+/* ---- SGD with momentum and Adamax behind the clip (csrc/optim.hip; cvc.optim.ClipSGD / ClipAdamax): the reference's other two
+ * optimizers (main.py:182-191).  cvc_adam_clip_step (include/cvc_hip.h) with another update rule in its third launch: the same
+ * segment and chunk tables, the same norm (chunk sums combined in chunk order), the same coefficient
+ * coef = min(1, max_norm / (inv_world * norm + 1e-6)) * inv_world (max_norm <= 0: inv_world; a NaN norm: NaN), the same write_grad
+ * (0 leave the gradients, 1 store g * coef, 2 store zero), `skip`, `partial` and `norm_coef`.  Per element, as written below:
+ * what is spelled fma is one rounding, nothing else is contracted by the compiler, so that the float4 form (every operand of
+ * the rule 16-byte aligned) and the scalar form give the same bits.  SGD's buffer is the one product-and-sum that is not fused.
+ *   both      g = grad * coef;   ge = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *   SGD       torch.optim.SGD, dampening 0, no Nesterov, no maximize.  m of the segment = momentum_buffer; v and step are NULL
+ *             (the second launch increments only the step counts that are there).
+ *               buf = round(momentum * buf) + ge;   p = fma(-lr, buf, p)
+ *             The buffer's product is rounded before the sum, as torch's buf.mul_(momentum).add_(g) rounds it: under
+ *             cancellation of momentum * buf against g an fma differs from torch's buffer by an ulp of the product, and the
+ *             buffer is state that carries the difference into every later step.  A zero buffer gives torch's first step
+ *             (buf = ge).  A segment whose m is NULL has no buffer: p = fma(-lr, ge, p), torch's momentum == 0.
+ *   Adamax    torch.optim.Adamax, no maximize.  m = exp_avg, v = exp_inf, step = the step count (one float32 on the device, never
+ *             NULL), t its value after the second launch's += 1.
+ *               m = fma(ge - m, 1 - beta1, m);   u = max(beta2 * u, |ge| + eps);   p = fma(-(lr / (1 - powf(beta1, t))), m / u, p)
+ *             The max is torch.maximum's: a NaN on either side gives NaN, so a NaN gradient element leaves NaN in u and p.
+ * A void step (*skip != 0 when the launches execute) moves no parameter, state or step count and writes norm_coef = [0, 0];
+ * write_grad == 2 still leaves the gradients zero.  Three launches, nothing read back by the host: capturable.
+ * CVC_E_BADARG before any launch: a NULL segs / chunks / partial / norm_coef, nseg < 1, nchunk < 1, inv_world <= 0; momentum outside
+ * [0, 1); beta1 or beta2 outside [0, 1), eps <= 0 (u = |ge| + eps must not be 0 where m / u is formed). */
+int cvc_sgd_clip_step(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm, float inv_world,
+                      float momentum, int write_grad, float* partial, float* norm_coef, const int* skip, cvc_stream_t stream);
+int cvc_adamax_clip_step(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                         float inv_world, float beta1, float beta2, float eps, int write_grad, float* partial, float* norm_coef,
+                         const int* skip, cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
