@@ -78,11 +78,13 @@ def up_to_date() -> bool:
 # indexes its by-value member table at run time -- neither may end up in scratch)
 # (distill.hip: the soft-target criterion keeps the student's and the teacher's row in registers, two arrays of up to 32 per thread)
 # (optim.hip: the three update kernels are one memory-bound pass over every parameter, four float4 operands in registers -- a spill
-# there is silent and costs the pass its bandwidth; profiles/optim_rules.md records them as free of scratch)
+# there is silent and costs the pass its bandwidth; profiles/optim_rules.md records them as free of scratch.  Their weight-averaging
+# forms carry a fifth, the shadow; the swap two: profiles/ema.md)
 NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",),
                       "mix.hip": ("sample_select_kernel",), "ensemble.hip": ("ensemble_logprobs_kernel",),
                       "distill.hip": ("vocab_kd_fwd_kernel", "vocab_kd_bwd_kernel"),
-                      "optim.hip": ("optim_adam_kernel", "optim_sgd_kernel", "optim_adamax_kernel")}
+                      "optim.hip": ("optim_adam_kernel", "optim_sgd_kernel", "optim_adamax_kernel", "optim_adam_ema_kernel", "optim_sgd_ema_kernel",
+                                    "optim_adamax_ema_kernel", "ema_swap_kernel")}
 
 
 def check_no_scratch(src: str, remarks: str):

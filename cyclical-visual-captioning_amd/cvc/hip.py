@@ -331,6 +331,11 @@ SIGNATURES = {
     "cvc_adam_clip_step": [_P, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P],
     "cvc_sgd_clip_step": [_P, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P],
     "cvc_adamax_clip_step": [_P, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P],
+    # weight averaging inside the step: the plain entry's arguments, then ema (device pointer array), ema_state, decay, warmup
+    "cvc_adam_clip_step_ema": [_P, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _F, _I, _P],
+    "cvc_sgd_clip_step_ema": [_P, _I, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _F, _I, _P],
+    "cvc_adamax_clip_step_ema": [_P, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _F, _I, _P],
+    "cvc_ema_swap": [_P, _I, _P, _I, _P, _P],
     "cvc_comm_unique_id": [_P],
     "cvc_comm_init": [_I, _I, _P, C.POINTER(C.c_void_p)],
     "cvc_allreduce_grads": [_P, _P, _LL, _P],
@@ -355,7 +360,8 @@ BLOCKS = {
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
     "cvc_caption_set_stats", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
     "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix",
-    "cvc_vocab_head_nll_kd_fwd", "cvc_vocab_nll_kd_fwd", "cvc_vocab_nll_kd_bwd", "cvc_sgd_clip_step", "cvc_adamax_clip_step"}
+    "cvc_vocab_head_nll_kd_fwd", "cvc_vocab_nll_kd_fwd", "cvc_vocab_nll_kd_bwd", "cvc_sgd_clip_step", "cvc_adamax_clip_step",
+    "cvc_adam_clip_step_ema", "cvc_sgd_clip_step_ema", "cvc_adamax_clip_step_ema", "cvc_ema_swap"}
 EXPERIMENTAL = {
     "cvc_gsk_plan", "cvc_gsk_gemm", "cvc_attn_scores_qslab", "cvc_top2_slab", "cvc_packed_lstm_ks_slices", "cvc_packed_lstm_ks_fwd",
     "cvc_packed_lstm_ksf_fwd", "cvc_packed_lstm_ksx_local", "cvc_packed_lstm_ksx_fwd", "cvc_packed_lstm_wg_blocks",

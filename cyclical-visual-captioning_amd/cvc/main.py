@@ -148,7 +148,29 @@ def build_parser():
                         help="the soft loss's share in [0, 1] (default 0.5): loss = (1 - alpha) NLL + alpha tau^2 KL(teacher || student)")
     parser.add_argument("--distill_temperature", type=float, default=argparse.SUPPRESS,
                         help="tau > 0 (default 1.0): both distributions are softmax(. / tau)")
+    # weight averaging (Trainer(ema=...); cvc.optim._ClipStep.attach_ema): absent, they add no key and change no launch
+    parser.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS,
+                        help="keep an exponential moving average of the weights with this decay, inside the native optimizer step; "
+                             "validation, model-best.pth and the LR plateau schedule then use the averaged weights, model-ema.pth "
+                             "holds them and model.pth stays the live ones; in [0, 1), 0 = off")
+    parser.add_argument("--ema_warmup", action="store_true", default=argparse.SUPPRESS,
+                        help="with --ema_decay: the decay of step n is min(decay, (1 + n) / (10 + n))")
     return parser
+
+
+def check_ema_flags(opt):
+    """--ema_decay lies in [0, 1) (a NaN does not) and needs the native optimizer step; --ema_warmup needs --ema_decay: anything
+    else ends the run with a message, before any set-up"""
+    d = getattr(opt, "ema_decay", None)
+    if d is not None and not 0.0 <= d < 1.0:
+        raise SystemExit("--ema_decay must lie in [0, 1), got %r" % (d,))
+    if getattr(opt, "ema_warmup", False) and not d:
+        raise SystemExit("--ema_warmup shapes the decay of --ema_decay: it needs --ema_decay d with 0 < d < 1")
+    if d:
+        from .trainer import CLIP_ADAM
+        if not CLIP_ADAM:
+            raise SystemExit("--ema_decay needs the native optimizer step (cvc.optim): the average is kept inside its update launch "
+                             "and CVC_CLIP_ADAM=0 selects the library optimizers, which get none")
 
 
 def check_distill_flags(opt):
@@ -280,6 +302,7 @@ def main(argv=None, sample=None, score=None):
     check_label_smoothing_flag(opt.label_smoothing)
     check_entropy_flags(opt)
     check_val_diversity_flag(opt)
+    check_ema_flags(opt)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)
     ensemble = check_ensemble_flags(opt)
@@ -390,12 +413,27 @@ def main(argv=None, sample=None, score=None):
     ss_prob_history = histories.get("ss_prob_history", {})
 
     optimizer = build_optimizer(model, opt)
+    # the weight average is a training matter: an evaluation-only run (--inference_only, cvc.sample, cvc.score) decodes the checkpoint
+    # it resumed, as without the flags
+    ema = None
+    if getattr(opt, "ema_decay", 0) and not (opt.inference_only or sample is not None or score is not None):
+        ema = (opt.ema_decay, bool(getattr(opt, "ema_warmup", False)))
     # flat gradient arenas; exchanges only when world > 1 -- on the package's own RCCL communicator (--dist_backend rccl, the
     # default: torch.distributed on gloo is the control plane only), whose collectives are captured into the step's HIP graph
     comm = exchange_comm() if (world > 1 and opt.dist_backend == "rccl") else None
     reducer = GradReducer(model.named_parameters(), comm=comm)
     trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device",
-                      **(dict(val_diversity=True) if getattr(opt, "val_diversity", False) else {}))
+                      **(dict(val_diversity=True) if getattr(opt, "val_diversity", False) else {}),
+                      **(dict(ema=ema or False) if hasattr(opt, "ema_decay") else {}))       # (False: none, whatever opt says)
+    if ema is not None and opt.resume:
+        # the shadows and their step count go on from model-ema.pth; a run directory from before the average has none
+        ema_path = os.path.join(save_dir, "model-ema.pth")
+        if os.path.isfile(ema_path):
+            optimizer.load_ema_state_dict(model, torch.load(ema_path, map_location=device))
+            if rank == 0:
+                print("resumed %s (%d averaged steps)" % (ema_path, optimizer.ema_updates))
+        elif rank == 0:
+            print("no %s: the weight average starts from the resumed weights" % ema_path)
     if ensemble is not None:                                   # evaluation, cvc.sample and cvc.score decode through the ensemble
         from .model.ensemble import CaptionEnsemble
         members = [getattr(model, "module", model)]
@@ -472,11 +510,16 @@ def main(argv=None, sample=None, score=None):
             best_flag = score is not None and (best is None or score > best)
             if best_flag:
                 best = score
-            torch.save(model.state_dict(), os.path.join(save_dir, "model.pth"))
+            torch.save(model.state_dict(), os.path.join(save_dir, "model.pth"))         # the live weights: what training resumes from
+            ema_sd = optimizer.ema_state_dict(model) if trainer.ema_active else None
+            if ema_sd is not None:
+                torch.save(ema_sd, os.path.join(save_dir, "model-ema.pth"))
             val_result_history[epoch] = dict(stats)
             lr_history[epoch] = optimizer.param_groups[0]["lr"]
             infos = {"iter": (epoch + 1) * max(len(loader) - 1, 0), "epoch": epoch, "best_val_score": best, "vocab": full.itow,
                      "opt": {k: v for k, v in vars(opt).items() if _picklable(v)}}
+            if ema_sd is not None:
+                infos.update(ema_updates=ema_sd["updates"], ema_decay=ema[0], ema_warmup=ema[1])
             histories = {"val_result_history": val_result_history, "loss_history": {}, "lr_history": lr_history,
                          "ss_prob_history": dict(ss_prob_history), "reward_history": dict(trainer.reward_history),
                          "nll_history": dict(trainer.nll_history), "entropy_history": dict(trainer.entropy_history),
@@ -486,7 +529,9 @@ def main(argv=None, sample=None, score=None):
             with open(os.path.join(save_dir, "histories_" + opt.id + ".pkl"), "wb") as f:
                 pickle.dump(histories, f)
             if best_flag or not os.path.isfile(os.path.join(save_dir, "model-best.pth")):
-                torch.save(model.state_dict(), os.path.join(save_dir, "model-best.pth"))
+                # (the weights that were scored: the averaged ones when there is an average)
+                torch.save(model.state_dict() if ema_sd is None else {k: v for k, v in ema_sd.items() if k != "updates"},
+                           os.path.join(save_dir, "model-best.pth"))
                 with open(os.path.join(save_dir, "infos_" + opt.id + "-best.pkl"), "wb") as f:
                     pickle.dump(infos, f)
     if comm is not None:

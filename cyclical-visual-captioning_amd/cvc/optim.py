@@ -14,10 +14,15 @@ over every gradient and the fused Adam's own pass.  `step()` alone is the unclip
 tables keyed on the tensors' addresses, the in-place rewrite of lr / weight_decay, the tables a rebuild retires, clip_and_step's
 arguments, last_norm -- is `_ClipStep`, shared by the three.
 
+Weight averaging: `attach_ema(decay, warmup)` keeps an exponential moving average of every stepped parameter, updated INSIDE the
+update launch from the new value still in registers (the `_ema` entries of include/cvc_hip_blocks.h); `averaged()` exchanges the
+averages with the parameters' own storage and back.  The shadows are not optimizer state: `state_dict()` stays torch's.
+
 Parameters whose .grad is None are skipped, as the torch optimizers skip them (no state, no step count, no weight decay).
 amsgrad / nesterov / dampening / maximize / differentiable are not taken: the reference never sets them (main.py:171-191)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -48,6 +53,13 @@ class _ClipStep:
         self._seg_host = None       # host copy of the segment table (lr / weight_decay are rewritten in place when they change)
         self._retired = []          # tables replaced by a rebuild: kept alive, a captured HIP graph may still replay on them
         self.last_norm: Optional[torch.Tensor] = None       # device scalar: norm of the (averaged) gradient of the last clipped step
+        # ---- weight averaging (attach_ema): off = None, and nothing below this line is touched by a step
+        self._ema = None            # (decay, warmup)
+        self._ema_shadow = {}       # parameter -> its average (NOT in self.state: state_dict() stays torch's layout)
+        self._ema_state = None      # device float32[2]: [averaged steps so far, d_eff of the current step] (the kernels keep it)
+        self._ema_updates0 = 0.0    # the count _ema_state starts from (load_ema_state_dict before the first step)
+        self._ema_ptrs = None       # device array of the step table's shadow addresses, built and retired with the table
+        self._swap = None           # (key, segment table, chunk table, shadow addresses, nseg, nchunk) of swap_ema
 
     def _device_step(self, st, p):
         """the state's `step` as a float32 scalar on the parameter's device (a state_dict loaded from a CPU-step checkpoint is moved)"""
@@ -69,6 +81,8 @@ class _ClipStep:
                 m, v, step = self._state(p, group)
                 segs.append((p, p.grad, m, v, step, float(group["lr"]), float(group["weight_decay"])))
                 key.append((p.data_ptr(), p.grad.data_ptr()) + tuple(0 if t is None else t.data_ptr() for t in (m, v, step)))
+                if self._ema is not None:
+                    key[-1] += (self._shadow(p).data_ptr(),)
         if not segs:
             return None
         key = (tuple(key),) + rule
@@ -101,6 +115,13 @@ class _ClipStep:
         norm_coef = torch.zeros(2, dtype=torch.float32, device=dev)
         if self._table is not None:
             self._retired.append(self._table)
+            if self._ema_ptrs is not None:
+                self._retired.append(self._ema_ptrs)
+        self._ema_ptrs = None
+        if self._ema is not None:
+            self._ema_ptrs = torch.tensor([self._ema_shadow[p].data_ptr() for p, *_ in segs], dtype=torch.int64).to(dev)
+            if self._ema_state is None:
+                self._ema_state = torch.tensor([self._ema_updates0, 0.0], dtype=torch.float32).to(dev)
         self._seg_host = seg_np
         self._table = (key, seg_t, chunk_t, partial, norm_coef, len(segs), len(chunk_np)) + rule
         return self._table
@@ -127,9 +148,14 @@ class _ClipStep:
             return None
         _key, seg_t, chunk_t, partial, norm_coef, nseg, nchunk = t[:7]
         entry, rule_args = self._launch(t)
+        ema_args = ()
+        if self._ema is not None:
+            entry += "_ema"
+            ema_args = (self._ema_ptrs.data_ptr(), self._ema_state.data_ptr(), self._ema[0], int(self._ema[1]))
         hip._check(getattr(hip.lib(), entry)(seg_t.data_ptr(), nseg, chunk_t.data_ptr(), nchunk, float(max_norm), float(inv_world),
                                              *rule_args, 2 if zero_grad else (1 if write_grad else 0), partial.data_ptr(),
-                                             norm_coef.data_ptr(), skip.data_ptr() if skip is not None else None, hip._stream()),
+                                             norm_coef.data_ptr(), skip.data_ptr() if skip is not None else None, *ema_args,
+                                             hip._stream()),
                    entry)
         self.last_norm = norm_coef[0]
         return self.last_norm
@@ -142,6 +168,123 @@ class _ClipStep:
                 loss = closure()
         self.clip_and_step(0.0, 1.0, write_grad=False)
         return loss
+
+    # ------------------------------------------------------------------ weight averaging
+    @property
+    def ema_active(self) -> bool:
+        return self._ema is not None
+
+    def attach_ema(self, decay: float, warmup: bool = False):
+        """Keep e = e + (p_new - e) (1 - d_eff) of every stepped parameter from the next step on, inside the update launch.
+        d_eff = decay, or min(decay, (1 + n) / (10 + n)) over the n averaged steps so far under `warmup`.  A parameter's shadow is a
+        copy of its value when it first enters the step table.  Attach before a step is captured into a graph."""
+        name = type(self).__name__
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:                   # (NaN fails both comparisons)
+            raise ValueError(f"{name}.attach_ema: decay must lie in [0, 1), got {decay}")
+        for group in self.param_groups:
+            for p in group["params"]:
+                if not (p.is_cuda and p.dtype == torch.float32):
+                    raise RuntimeError(f"{name}.attach_ema: the average is kept by the HIP step, float32 GPU parameters only "
+                                       "(no CPU fallback)")
+        self._ema = (decay, bool(warmup))
+
+    def detach_ema(self):
+        """Stop averaging and forget the shadows (a graph captured while attached keeps replaying on them: they stay alive)."""
+        if self._ema is not None:
+            self._retired.append((dict(self._ema_shadow), self._ema_state, self._swap))
+        self._ema, self._ema_state, self._ema_updates0, self._swap = None, None, 0.0, None
+        self._ema_shadow = {}
+
+    def _shadow(self, p):
+        e = self._ema_shadow.get(p)
+        if e is None:
+            e = self._ema_shadow[p] = p.detach().clone(memory_format=torch.contiguous_format)
+        return e
+
+    @property
+    def ema_updates(self) -> int:
+        """averaged (non-void) steps so far: one host read of the device's counter"""
+        return int(self._ema_updates0 if self._ema_state is None else float(self._ema_state[0]))
+
+    def _swap_table(self):
+        """segment / chunk tables over EVERY shadowed parameter, with or without a gradient at the moment (p and n alone are read)"""
+        ps = [p for group in self.param_groups for p in group["params"] if p in self._ema_shadow]
+        if not ps:
+            return None
+        key = tuple((p.data_ptr(), self._ema_shadow[p].data_ptr()) for p in ps)
+        if self._swap is not None and self._swap[0] == key:
+            return self._swap
+        for p in ps:
+            e = self._ema_shadow[p]
+            if not (p.is_contiguous() and e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == p.numel()):
+                raise RuntimeError(f"{type(self).__name__}: contiguous float32 GPU parameters and shadows only (no CPU fallback)")
+        dev = ps[0].device
+        chunk = int(hip.lib().cvc_optim_chunk_elems())
+        seg_np = np.zeros(len(ps), dtype=_SEG_DT)
+        seg_np["p"], seg_np["n"] = [p.data_ptr() for p in ps], [p.numel() for p in ps]
+        counts = (seg_np["n"] + chunk - 1) // chunk
+        chunk_np = np.zeros(int(counts.sum()), dtype=_CHUNK_DT)
+        chunk_np["seg"] = np.repeat(np.arange(len(ps), dtype=np.int32), counts)
+        first = np.concatenate(([0], np.cumsum(counts)[:-1]))
+        chunk_np["start"] = (np.arange(len(chunk_np), dtype=np.int64) - np.repeat(first, counts)) * chunk
+        if self._swap is not None:
+            self._retired.append(self._swap)
+        self._swap = (key, torch.from_numpy(seg_np.view(np.uint8)).to(dev), torch.from_numpy(chunk_np.view(np.uint8)).to(dev),
+                      torch.tensor([e for _p, e in key], dtype=torch.int64).to(dev), len(ps), len(chunk_np))
+        return self._swap
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """p <-> e of every shadowed parameter, in the parameters' own storage (one launch; twice is the identity).  Whoever caches
+        anything derived from the weights is told by the caller (Trainer.averaged_weights)."""
+        if self._ema is None:
+            raise RuntimeError(f"{type(self).__name__}.swap_ema: no average is attached (attach_ema)")
+        t = self._swap_table()
+        if t is None:
+            return
+        _key, seg_t, chunk_t, ptrs, nseg, nchunk = t
+        hip._check(hip.lib().cvc_ema_swap(seg_t.data_ptr(), nseg, chunk_t.data_ptr(), nchunk, ptrs.data_ptr(), hip._stream()), "cvc_ema_swap")
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """the averaged weights in the parameters' storage while the block runs; the live ones come back bit for bit"""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self, model) -> dict:
+        """model.state_dict() with every shadowed parameter replaced by its average (copies; buffers and shadow-less parameters are
+        the live model's), plus `updates`, the averaged steps so far"""
+        if self._ema is None:
+            raise RuntimeError(f"{type(self).__name__}.ema_state_dict: no average is attached (attach_ema)")
+        sd = {}
+        for name, t in model.state_dict(keep_vars=True).items():
+            e = self._ema_shadow.get(t) if isinstance(t, torch.nn.Parameter) else None
+            sd[name] = (t if e is None else e.view_as(t)).detach().clone()
+        assert "updates" not in sd
+        sd["updates"] = self.ema_updates
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, model, sd):
+        """the inverse of ema_state_dict: every parameter of this optimizer named in `sd` gets that value as its shadow (created
+        where there is none yet), the counter gets `updates`"""
+        if self._ema is None:
+            raise RuntimeError(f"{type(self).__name__}.load_ema_state_dict: no average is attached (attach_ema)")
+        mine = {p for group in self.param_groups for p in group["params"]}
+        for name, p in model.named_parameters():
+            if p not in mine or name not in sd:
+                continue
+            v = sd[name]
+            if tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict: {name} has shape {tuple(v.shape)}, the parameter {tuple(p.shape)}")
+            self._shadow(p).view_as(p).copy_(v)
+        self._ema_updates0 = float(sd.get("updates", 0))
+        if self._ema_state is not None:
+            self._ema_state.copy_(torch.tensor([self._ema_updates0, 0.0]))
 
     def _shared(self, what, pick):
         """the one value of pick(group) over the param groups"""

@@ -11,6 +11,8 @@ beside it, the grounding F1 of the generated captions (cvc.metrics.GroundingScor
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 import json
 import os
 import time
@@ -79,13 +81,26 @@ def _copy_into(static, b):
             static[k] = v
 
 
+def _averaged_by_default(fn):
+    """eval / sample / score / ground_gt take `weights="ema" | "live"`: on the averaged weights (Trainer.averaged_weights) when the
+    weight average is attached, unless told otherwise; without an average the method is what it was"""
+    @functools.wraps(fn)
+    def wrapper(self, *a, weights=None, **kw):
+        if self._use_ema(weights):
+            with self.averaged_weights():
+                return fn(self, *a, **kw)
+        return fn(self, *a, **kw)
+    return wrapper
+
+
 class Trainer:
     # a cvc.model.CaptionEnsemble over the model (member 0) and further checkpoints, set by whoever builds the trainer (cvc.main
     # --ensemble): eval(), sample() and score() then decode through it; training steps never see it.  None: every decode is the model's
     ensemble = None
+    _averaged = 0                     # depth of averaged_weights(): non-zero while the parameters hold the weight averages
 
     def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False,
-                 val_diversity=False):
+                 val_diversity=False, ema=None):
         self.opts = opts
         self.dataset = dataset
         self.model = model
@@ -171,6 +186,19 @@ class Trainer:
         # not distilled
         self.kd_history = {}          # epoch -> the mean KD of every display interval (distilled steps)
         self.last_kd = None
+        # ---- weight averaging (ema=(decay, warmup), or opts.ema_decay / opts.ema_warmup: cvc.main --ema_decay): an exponential moving
+        # average of every stepped parameter, kept INSIDE the optimizer pass (cvc.optim._ClipStep.attach_ema) and therefore by every
+        # step kind, captured or eager, and by no void step.  Attached here, before anything is captured: a captured step holds the
+        # entry it launches.  eval / sample / score then run on the averaged weights (averaged_weights)
+        if ema is None and getattr(opts, "ema_decay", 0):
+            ema = (float(opts.ema_decay), bool(getattr(opts, "ema_warmup", False)))
+        if ema:                       # (ema=False: none, whatever the options say)
+            attach = getattr(optimizer, "attach_ema", None)
+            if attach is None:
+                raise RuntimeError("Trainer: the weight average is kept by the native optimizer step (cvc.optim.ClipAdam / ClipSGD / "
+                                   "ClipAdamax); %s is a library optimizer (CVC_CLIP_ADAM=0, or parameters on the CPU) and gets "
+                                   "none -- it is not emulated" % type(optimizer).__name__)
+            attach(float(ema[0]), bool(ema[1]))
 
     # ------------------------------------------------------------------ batch plumbing
     def _prepare(self, batch, train: bool):
@@ -336,6 +364,8 @@ class Trainer:
     def _backward_and_update(self, loss, set_to_none=True):
         """zero_grad -> backward -> [gradient exchange] -> clip_grad_norm_ -> step (trainer.py:116-122).  With a GradReducer
         the gradients live in flat arenas: one fill to zero them, the exchange in place, one multiply to clip (1/G folded in)."""
+        if self._averaged:
+            raise RuntimeError("Trainer: a training step inside averaged_weights() would update the averages in the parameters' place")
         red = self.grad_reducer
         fused = getattr(self.optimizer, "clip_and_step", None)     # cvc.optim.ClipAdam: norm + clip + Adam in three launches
         if red is None:
@@ -371,6 +401,40 @@ class Trainer:
         else:
             from . import hip
             hip.bump_weights_generation()
+
+    # ------------------------------------------------------------------ weight averaging
+    @property
+    def ema_active(self) -> bool:
+        return bool(getattr(getattr(self, "optimizer", None), "ema_active", False))
+
+    def _use_ema(self, weights) -> bool:
+        if weights not in (None, "ema", "live"):
+            raise ValueError("weights must be 'ema' or 'live', got %r" % (weights,))
+        if weights == "ema" and not self.ema_active:
+            raise RuntimeError("weights='ema': no weight average is attached (Trainer(ema=...), cvc.main --ema_decay)")
+        return self.ema_active if weights is None else weights == "ema"
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """The averaged weights in the parameters' OWN storage while the block runs (optimizer.averaged(): one exchange launch in,
+        one out, the live values back bit for bit).  Everything keyed on the parameters' addresses -- the decode engine's packs,
+        the encoder's operands, the optimizer's tables, captured graphs -- stays valid; what caches VALUES is told on the way in
+        and out (_weights_changed).  Re-entrant: an inner block changes nothing.  No training step may run inside."""
+        if self._averaged:
+            self._averaged += 1
+            try:
+                yield
+            finally:
+                self._averaged -= 1
+            return
+        with self.optimizer.averaged():
+            self._averaged = 1
+            self._weights_changed()
+            try:
+                yield
+            finally:
+                self._averaged = 0
+        self._weights_changed()
 
     # ------------------------------------------------------------------ self-critical training step
     def cider(self):
@@ -858,6 +922,7 @@ class Trainer:
             self._timestamps = src['annotations']
         return self._timestamps
 
+    @_averaged_by_default
     def eval(self, epoch, tb_logger=None):
         """Greedy (or beam) decode of the validation split -> predictions in the densecap JSON
         layout (trainer.py:254-286: {'sentence', 'timestamp': [start, end]} per segment) -> optional external scorer.
@@ -1023,6 +1088,7 @@ class Trainer:
         return model.score(b["segs_feat"], b["input_seqs"], b["gt_seqs"], b["num"], b["ppls"], b["gt_bboxs"], b["mask_bboxs"],
                            b["ppls_feat"], b["mask_frms"], b["sample_idx"], b["pnt_mask"], **kw)
 
+    @_averaged_by_default
     def score(self, stem: str = None):
         """Teacher-forced scoring of the validation split's GT captions (model.score: the decode engine's forced mode).
         Writes <results_dir>/<stem>_scores.json (rank 0, after the merge of the ranks' shards, as sample does; stem defaults to
@@ -1055,6 +1121,7 @@ class Trainer:
                 json.dump(scores, f)
         return stats
 
+    @_averaged_by_default
     def ground_gt(self, stem: str = None):
         """Grounding on the GT sentences (--eval_obj_grounding_gt; the reference parses the flag and raises NotImplementedError,
         trainer.py:352-353): model.score(grounding=True) over the validation split, then per annotated object word the proposal
@@ -1102,6 +1169,7 @@ class Trainer:
                                        write_grounding_json(grd_grd, o, stem=(stem or 'grd') + '-gt-sent-results', eval_mode='GT'))
         return stats
 
+    @_averaged_by_default
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
                constraints: dict = None, consensus: bool = False, without_replacement: bool = False, diversity: bool = False):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)

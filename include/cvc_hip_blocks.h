@@ -813,6 +813,32 @@ int cvc_adamax_clip_step(const cvc_optim_seg* segs, int nseg, const cvc_optim_ch
                          float inv_world, float beta1, float beta2, float eps, int write_grad, float* partial, float* norm_coef,
                          const int* skip, cvc_stream_t stream);
 
+/* ---- Weight averaging (EMA) inside the optimizer step (csrc/optim.hip; cvc.optim._ClipStep.attach_ema).  The three clip + step
+ * entries with a shadow per segment: ema[seg] (a device array of nseg device pointers, the segment's n floats each) is the
+ * exponential moving average of that parameter, updated in the third launch from the p the rule has just produced, still in
+ * registers:
+ *     e = fma(p_new - e, 1 - d_eff, e)                       (1 - d_eff formed in fp32)
+ * The lerp form: p_new == e leaves e's bits alone.  cvc_optim_seg's layout is unchanged; p, g, the state, the step counts, `partial`
+ * and `norm_coef` get the bits of the plain entry.  ema[seg] == NULL: the segment has no shadow and is stepped exactly as the plain
+ * entry steps it.  e counts as an operand of the float4 form (16-byte aligned with the rule's others, else the segment's scalar loop).
+ * ema_state: two floats on the device, [0] = averaged steps so far, [1] = d_eff of the current step.  The second launch sets
+ *     d_eff = warmup ? min(decay, (1 + n) / (10 + n)) : decay     (n = ema_state[0] before this step; the TensorFlow / timm warm-up)
+ * and then ema_state[0] += 1.  A void step (*skip != 0) writes neither e nor ema_state.  Three launches, capturable.
+ * CVC_E_BADARG before any launch: whatever the plain entry refuses, a NULL ema or ema_state, decay outside [0, 1) (NaN included).
+ * cvc_ema_swap: p[i] <-> e[i] over the same tables (segments with a NULL shadow stay): the averaged weights in the parameters' own
+ * storage and out again, bit for bit; twice is the identity.  One launch.  BADARG: a NULL table or ema, nseg < 1, nchunk < 1. */
+int cvc_adam_clip_step_ema(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                           float inv_world, float beta1, float beta2, float eps, int write_grad, float* partial, float* norm_coef,
+                           const int* skip, float* const* ema, float* ema_state, float decay, int warmup, cvc_stream_t stream);
+int cvc_sgd_clip_step_ema(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                          float inv_world, float momentum, int write_grad, float* partial, float* norm_coef, const int* skip,
+                          float* const* ema, float* ema_state, float decay, int warmup, cvc_stream_t stream);
+int cvc_adamax_clip_step_ema(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float max_norm,
+                             float inv_world, float beta1, float beta2, float eps, int write_grad, float* partial, float* norm_coef,
+                             const int* skip, float* const* ema, float* ema_state, float decay, int warmup, cvc_stream_t stream);
+int cvc_ema_swap(const cvc_optim_seg* segs, int nseg, const cvc_optim_chunk* chunks, int nchunk, float* const* ema,
+                 cvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,7 @@ GRAD_CLIP = 0.1                                          # opts.grad_clip's defa
 TRAFFIC = {"adam": (4, 4), "sgd": (3, 3), "adamax": (4, 4)}
 
 
-def compiler_report():
+def compiler_report(kernels=r"optim_\w+?_kernel"):
     """csrc/optim.hip compiled as the library's build compiles it, with hipcc's resource remarks -> {kernel: {VGPRs, SGPRs, LDS,
     scratch, sgpr_spills, vgpr_spills, occupancy}} of the source this run measures (None where hipcc is not at hand)"""
     import re
@@ -51,7 +51,7 @@ def compiler_report():
               "sgpr_spills": "SGPRs Spill", "vgpr_spills": "VGPRs Spill", "occupancy": r"Occupancy \[waves/SIMD\]"}
     out = {}
     for block in err.split("remark: Function Name: ")[1:]:
-        name = re.search(r"optim_\w+?_kernel", block.split()[0])
+        name = re.search(kernels, block.split()[0])
         if name:
             out[name.group(0)] = {k: int(re.search(r"remark:\s+%s: (\d+)" % pat, block).group(1)) for k, pat in fields.items()}
     return out
