@@ -148,3 +148,10 @@ class CiderD:
             raise RuntimeError(f"CiderD.consensus: {int(per_clip)} candidates per clip; the selection takes at most per_clip = {MAX_PER_CLIP}")
         return hip.consensus_cider(cand.contiguous(), int(per_clip), self.keys, self.idf, self.idf_unseen, self.sigma,
                                    live=None if live is None else live.to(torch.int32).contiguous())
+
+    def self_cider(self, cand: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None) -> dict:
+        """Self-CIDEr diversity of every clip's candidate set over this table (cvc.metrics.set_spectrum in mode cider: plain CIDEr
+        similarity -- no clipping, no length term, the end mark is no word).  -> dict(lam [clips, 32] fp64, score [clips, 2] fp32,
+        info [clips, 2] int32); score[:, 0] is the clip's Self-CIDEr."""
+        from . import metrics
+        return metrics.set_spectrum(cand, per_clip, live, cider=self)

@@ -726,6 +726,16 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         cand, n, live = self.candidates("set_diversity")
         return metrics.set_diversity(cand, n, live)
 
+    def set_spectrum(self, cider=None):
+        """Spectral diversity of every clip's candidate set after run() (DESIGN section 7, "Spectral set diversity";
+        csrc/spectrum.hip): cvc.metrics.set_spectrum on exactly the candidates and live mask consensus() and set_diversity() use,
+        with the same refusals.  cider: a cvc.cider.CiderD (Self-CIDEr over its table) or None (LSA).  -> dict(lam [B, 32] fp64,
+        score [B, 2], info [B, 2] int32), new tensors on the device; the engine's state and launch lists are not touched, no host
+        read-back."""
+        from .. import metrics
+        cand, n, live = self.candidates("set_spectrum")
+        return metrics.set_spectrum(cand, n, live, cider=cider)
+
     def _python_launches(self):
         if self._launches is None:
             self._keep = []

@@ -291,6 +291,8 @@ SIGNATURES = {
     "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
     # caption-set diversity: distinct n-grams, mBLEU statistics, distinct captions per clip (csrc/diversity.hip; building block)
     "cvc_caption_set_stats": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
+    # spectral caption-set diversity: similarity matrix, its eigenvalues, Self-CIDEr / LSA scores (csrc/spectrum.hip; building block)
+    "cvc_caption_set_spectrum": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P],
     # grounding F1 of generated captions: picks per object word and frame, per-class counters (csrc/grounding.hip; building block)
     "cvc_grounding_f1": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # label smoothing in the vocabulary criterion: the fused head, the two-step form and its backward (csrc/vocab.hip; building blocks)
@@ -358,7 +360,7 @@ BLOCKS = {
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
     "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
-    "cvc_caption_set_stats", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
+    "cvc_caption_set_stats", "cvc_caption_set_spectrum", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
     "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix",
     "cvc_vocab_head_nll_kd_fwd", "cvc_vocab_nll_kd_fwd", "cvc_vocab_nll_kd_bwd", "cvc_sgd_clip_step", "cvc_adamax_clip_step",
     "cvc_adam_clip_step_ema", "cvc_sgd_clip_step_ema", "cvc_adamax_clip_step_ema", "cvc_ema_swap"}
@@ -1504,6 +1506,44 @@ def caption_set_stats(cand: torch.Tensor, per_clip: int, live: Optional[torch.Te
                                        _dev(set_stats, torch.int32), _dev(mbleu_stats, torch.int32), _dev(mbleu), _stream()),
            "cvc_caption_set_stats")
     return set_stats, mbleu_stats, mbleu
+
+
+# --------------------------------------------------------------------------- spectral caption-set diversity (csrc/spectrum.hip)
+SPECTRUM_MODES = {"cider": 0, "lsa": 1}
+SPECTRUM_SLOTS = 32          # the padded side of gram and the length of lam, whatever per_clip is
+
+
+def caption_set_spectrum(cand: torch.Tensor, per_clip: int, mode: str, keys: Optional[torch.Tensor] = None,
+                         idf: Optional[torch.Tensor] = None, idf_unseen: float = 0.0, live: Optional[torch.Tensor] = None,
+                         want_gram: bool = False):
+    """cand [rows, T] int64, per_clip consecutive candidates per clip; mode "cider" (keys [G] int64 holding the table's unsigned 64-bit
+    keys, idf [G], idf_unseen) or "lsa" (no table); live [rows] int32 or None (every row is live).
+    -> gram [clips, 32, 32] fp32 (None unless want_gram), lam [clips, 32] fp64 (descending, zeros behind the m eigenvalues), score
+    [clips, 2] fp32, info [clips, 2] int32 (m, sweeps or -1)."""
+    per_clip = int(per_clip)
+    if mode not in SPECTRUM_MODES:
+        raise RuntimeError(f"cvc.hip.caption_set_spectrum: mode {mode!r}; it is one of {sorted(SPECTRUM_MODES)}")
+    cider = mode == "cider"
+    if cider and (keys is None or idf is None):
+        raise RuntimeError("cvc.hip.caption_set_spectrum: mode 'cider' needs the idf table (keys, idf)")
+    if cand.dim() != 2 or per_clip < 1 or cand.shape[0] < 1 or cand.shape[0] % per_clip != 0 \
+            or (live is not None and live.numel() != cand.shape[0]) or (cider and idf.numel() != keys.numel()):
+        raise RuntimeError(f"cvc.hip.caption_set_spectrum: cand {tuple(cand.shape)}, per_clip {per_clip}, live "
+                           f"{None if live is None else tuple(live.shape)}"
+                           + (f", keys {tuple(keys.shape)}, idf {tuple(idf.shape)}" if cider else "") + " do not fit")
+    rows, T = cand.shape
+    clips = rows // per_clip
+    G = int(keys.numel()) if cider else 0
+    gram = torch.empty(clips, SPECTRUM_SLOTS, SPECTRUM_SLOTS, device=cand.device, dtype=torch.float32) if want_gram else None
+    lam = torch.empty(clips, SPECTRUM_SLOTS, device=cand.device, dtype=torch.float64)
+    score = torch.empty(clips, 2, device=cand.device, dtype=torch.float32)
+    info = torch.empty(clips, 2, device=cand.device, dtype=torch.int32)
+    _check(lib().cvc_caption_set_spectrum(_dev(cand, torch.int64, "cand"), _dev(live, torch.int32, "live"), rows, T, per_clip,
+                                          SPECTRUM_MODES[mode], _dev(keys, torch.int64, "keys") if G else None,
+                                          _dev(idf, name="idf") if G else None, G, float(idf_unseen), _dev(gram),
+                                          _dev(lam, torch.float64), _dev(score), _dev(info, torch.int32), _stream()),
+           "cvc_caption_set_spectrum")
+    return gram, lam, score, info
 
 
 # --------------------------------------------------------------------------- grounding F1 of generated captions (csrc/grounding.hip)

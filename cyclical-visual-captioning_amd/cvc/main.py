@@ -123,6 +123,9 @@ def build_parser():
     parser.add_argument("--val_diversity", action="store_true", default=argparse.SUPPRESS,
                         help="score the diversity of every clip's candidate set in validation (Div_1, Div_2, mBLEU_4, Unique and the "
                              "oracle CIDEr-D, on the GPU); needs --val_metrics device and a candidate set, i.e. --consensus samples|beam")
+    parser.add_argument("--val_self_cider", action="store_true", default=argparse.SUPPRESS,
+                        help="with --val_diversity: also score Self_CIDEr and LSA, the spectral diversity of every clip's candidate "
+                             "set (cvc.metrics.SpectrumScorer, on the GPU)")
     # ensemble decoding (cvc.model.CaptionEnsemble): off by default and then no key in the options, no launch changes
     parser.add_argument("--ensemble", type=str, default=argparse.SUPPRESS,
                         help="comma-separated checkpoint files (state dicts of models built from the same options): evaluation, "
@@ -268,6 +271,8 @@ def check_member_state(path, state, reference, flag="--ensemble"):
 def check_val_diversity_flag(opt):
     """--val_diversity needs the device metrics and an evaluation that decodes a candidate set per clip: anything else ends the run
     with a message, before any set-up"""
+    if getattr(opt, "val_self_cider", False) and not getattr(opt, "val_diversity", False):
+        raise SystemExit("--val_self_cider needs --val_diversity (it scores the same candidate sets)")
     if not getattr(opt, "val_diversity", False):
         return
     if opt.val_metrics != "device":
@@ -293,7 +298,7 @@ def check_entropy_flags(opt):
 
 
 def main(argv=None, sample=None, score=None):
-    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) or (..., without_replacement, diversity) -- set up as for evaluation (checkpoint loading included), then write the validation split's
+    """sample: (n, temperature, seed), (n, temperature, seed, top_k, top_p), (n, temperature, seed, top_k, top_p, consensus) or (..., consensus, without_replacement) or (..., without_replacement, diversity) or (..., diversity, self_cider) -- set up as for evaluation (checkpoint loading included), then write the validation split's
     sampled captions (Trainer.sample) instead of the epoch loop (python -m cvc.sample).
     score: dict(ground_gt=bool) -- the same set-up, then the teacher-forced scores of the validation split's GT captions
     (Trainer.score) and, if asked for, the grounding on the GT sentences (Trainer.ground_gt) (python -m cvc.score)."""
@@ -424,6 +429,7 @@ def main(argv=None, sample=None, score=None):
     reducer = GradReducer(model.named_parameters(), comm=comm)
     trainer = Trainer(opt, full, model, optimizer, loader, val_loader, grad_reducer=reducer, device_metrics=opt.val_metrics == "device",
                       **(dict(val_diversity=True) if getattr(opt, "val_diversity", False) else {}),
+                      **(dict(val_self_cider=True) if getattr(opt, "val_self_cider", False) else {}),
                       **(dict(ema=ema or False) if hasattr(opt, "ema_decay") else {}))       # (False: none, whatever opt says)
     if ema is not None and opt.resume:
         # the shadows and their step count go on from model-ema.pth; a run directory from before the average has none
@@ -467,7 +473,7 @@ def main(argv=None, sample=None, score=None):
     global LAST_TRAINER
     LAST_TRAINER = trainer                                     # (tests and notebooks: graph / deferred-error statistics of the run)
     if sample is not None:
-        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus", "without_replacement", "diversity"), sample[3:])))
+        path = trainer.sample(*sample[:3], **dict(zip(("top_k", "top_p", "consensus", "without_replacement", "diversity", "self_cider"), sample[3:])))
         if rank == 0:
             print("samples written to %s" % path)
         if comm is not None:

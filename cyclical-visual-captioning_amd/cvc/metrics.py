@@ -21,7 +21,8 @@ CIDEr-D counts the end mark, METEOR and SPICE are not attempted.
 Further down: the grounding scores of the generated captions (csrc/grounding.hip; grounding, grounding_result, GroundingScorer) --
 F1_all / F1_loc in the manner of ActivityNet-Entities, for Trainer.eval with the device metrics and --eval_obj_grounding both on.
 At the end: the diversity of a clip's caption SET (csrc/diversity.hip; set_diversity, DiversityScorer) -- Div-1, Div-2, mBLEU, distinct
-captions, next to the set's oracle and mean CIDEr-D.
+captions, next to the set's oracle and mean CIDEr-D -- and the set's spectral diversity (csrc/spectrum.hip; set_spectrum,
+SpectrumScorer): Self-CIDEr and LSA-based diversity from the eigenvalues of the captions' similarity matrix.
 """
 from __future__ import annotations
 
@@ -390,3 +391,111 @@ def diversity_from_sums(int_sums, float_sums) -> dict:
         out["oracle_CIDEr"] = f[3] / f[4] if f[4] > 0 else 0.0
         out["mean_CIDEr"] = f[5] / f[6]
     return out
+
+
+# --------------------------------------------------------------------------- spectral caption-set diversity (csrc/spectrum.hip)
+# Definitions (what the kernel computes and tests/spectrum_ref.py restates; DESIGN section 7, "Spectral set diversity"):
+# * sets, words and live rows as above; m = the clip's live rows, indexed 0 .. m - 1 in ascending row order.
+# * mode cider -- plain CIDEr similarity, NOT CIDEr-D: v_n^a[g] = count_a(g) * idf(g), n = 1..4, idf from a CiderD's table (idf_unseen
+#   for an absent key); s_n(a, b) = <v_n^a, v_n^b> / (|v_n^a| |v_n^b|), 0 when a norm is 0; K[a, b] = 1/4 sum_n s_n.  No clipping, no
+#   length Gaussian, no factor 10: every s_n is a cosine kernel, K is positive semi-definite, K[a, a] = min(L, 4) / 4.
+# * mode lsa: K[a, b] = sum_w count_a(w) count_b(w) over unigrams -- the Gram matrix of the bag-of-words matrix, lambda_i = sigma_i^2.
+# * lam: the eigenvalues of the m x m matrix, descending, zeros behind them (fp64 Jacobi on the device).  With tr = sum_a K[a, a]:
+#     score[:, 0] = -log(min(lam_1 / tr, 1)) / log(m);  score[:, 1] = -log(sqrt(lam_1) / sum_i sqrt(max(lam_i, 0))) / log(m);
+#   both 0 where m < 2 or tr = 0.  0: every caption says the same; 1: no two captions share anything.  Higher is more diverse.
+# * Self_CIDEr = the mean of score[:, 0] in mode cider, LSA = the mean of score[:, 1] in mode lsa, both over the clips with m >= 2 and
+#   tr > 0;  Spectrum_sets: the clips with m >= 2.
+# These two forms are this project's definitions, scores by word id over the dataset's tokens and NOT a toolkit's numbers: neither
+# the paper's code nor its tokenizer is pinned against.  lam is returned so that any other form can be computed from it.
+SPECTRUM_KEYS = ("Self_CIDEr", "LSA", "Spectrum_sets")
+
+
+def set_spectrum(cand: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None, cider=None, want_gram: bool = False) -> dict:
+    """cand [rows, T] int64 on the device, per_clip consecutive candidates per clip; live [rows] (None: every row counts); cider: a
+    cvc.cider.CiderD (mode cider over its idf table) or None (mode lsa).
+    -> dict(lam [clips, 32] fp64, score [clips, 2] fp32, info [clips, 2] int32 (m, sweeps) (, gram [clips, 32, 32] fp32)), all on the
+    device: one launch, no host read."""
+    from . import hip
+    from .cider import MAX_T, MAX_PER_CLIP
+    if cand.dim() != 2 or cand.shape[1] > MAX_T:
+        raise RuntimeError(f"metrics.set_spectrum: cand {tuple(cand.shape)}; the kernel takes rows of at most T = {MAX_T} words")
+    if int(per_clip) > MAX_PER_CLIP:
+        raise RuntimeError(f"metrics.set_spectrum: {int(per_clip)} candidates per clip; the kernel takes at most per_clip = {MAX_PER_CLIP}")
+    live = None if live is None else live.to(torch.int32).contiguous()
+    if cider is None:
+        gram, lam, score, info = hip.caption_set_spectrum(cand.contiguous(), int(per_clip), "lsa", live=live, want_gram=want_gram)
+    else:
+        if cider.keys is None or cider.keys.device != cand.device:
+            cider.to(cand.device)
+        gram, lam, score, info = hip.caption_set_spectrum(cand.contiguous(), int(per_clip), "cider", cider.keys, cider.idf,
+                                                          cider.idf_unseen, live=live, want_gram=want_gram)
+    out = dict(lam=lam, score=score, info=info)
+    if want_gram:
+        out["gram"] = gram
+    return out
+
+
+class SpectrumScorer:
+    """Self-CIDEr and LSA diversity of a pass over the data without a host read per batch: add() runs the kernel on a batch's candidate
+    sets in mode cider (with a table), mode lsa, or both, and adds to five fp64 sums on the device; sums() reads them once; result()
+    is fp64 on the host.  A scorer of its own: DiversityScorer's sums are not touched."""
+
+    def __init__(self, cider=None, lsa: bool = True):
+        if cider is None and not lsa:
+            raise RuntimeError("SpectrumScorer: nothing to score -- give a CiderD table (Self_CIDEr), lsa=True (LSA), or both")
+        self.table = cider
+        self.lsa = bool(lsa)
+        self.float_sums = None         # [5] fp64: sum score_0 (cider), its clips, sum score_1 (lsa), its clips, clips with m >= 2
+
+    def _ensure(self, device):
+        if self.float_sums is None:
+            self.float_sums = torch.zeros(5, dtype=torch.float64, device=device)
+
+    @staticmethod
+    def _part(out, col):
+        counted = (out["info"][:, 0] >= 2) & (out["lam"][:, 0] > 0)          # (K is positive semi-definite: tr > 0 iff lam_1 > 0)
+        s = out["score"][:, col].to(torch.float64)
+        return [torch.where(counted, s, torch.zeros((), dtype=torch.float64, device=s.device)).sum(), counted.sum().to(torch.float64)]
+
+    def add(self, seq: torch.Tensor, per_clip: int, live: Optional[torch.Tensor] = None) -> dict:
+        """seq [rows, T] int64 on the device, per_clip consecutive candidates per clip, live [rows] or None.  No host read.
+        -> dict(cider=set_spectrum()'s dict in mode cider, lsa=... in mode lsa), the modes this scorer runs"""
+        self._ensure(seq.device)
+        zero = torch.zeros((), dtype=torch.float64, device=seq.device)
+        outs, fl, info = {}, [], None
+        if self.table is not None:
+            outs["cider"] = set_spectrum(seq, per_clip, live, cider=self.table)
+            fl += self._part(outs["cider"], 0)
+            info = outs["cider"]["info"]
+        else:
+            fl += [zero, zero]
+        if self.lsa:
+            outs["lsa"] = set_spectrum(seq, per_clip, live)
+            fl += self._part(outs["lsa"], 1)
+            info = outs["lsa"]["info"]
+        else:
+            fl += [zero, zero]
+        fl.append((info[:, 0] >= 2).sum().to(torch.float64))
+        self.float_sums += torch.stack(fl)
+        return outs
+
+    def add_sums(self, float_sums):
+        """precomputed sums (another rank's, or a test's), as sums() returns them"""
+        float_sums = torch.as_tensor(float_sums, dtype=torch.float64)
+        self._ensure(float_sums.device)
+        self.float_sums += float_sums.reshape(5).to(self.float_sums.device)
+
+    def sums(self):
+        """-> list of 5 floats on the host: ONE read"""
+        if self.float_sums is None:
+            return [0.0] * 5
+        return self.float_sums.tolist()
+
+    def result(self) -> dict:
+        return spectrum_from_sums(self.sums())
+
+
+def spectrum_from_sums(float_sums) -> dict:
+    """SpectrumScorer.sums() -> the scores of SPECTRUM_KEYS, fp64 on the host; empty sums (or a mode that never ran) give zeros"""
+    f = [float(x) for x in float_sums]
+    return {"Self_CIDEr": f[0] / f[1] if f[1] > 0 else 0.0, "LSA": f[2] / f[3] if f[3] > 0 else 0.0, "Spectrum_sets": int(f[4])}

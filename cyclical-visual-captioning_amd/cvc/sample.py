@@ -10,8 +10,10 @@ temperature) without UNK, written to <results_dir>/densecap-<val_split>-<id>_sam
                                                                           stochastic beam search, with each one's logq and G)
   python -m cvc.sample --sample_n 5 --diversity ...                      (also every segment's Div-1, Div-2, mBLEU-4 and distinct
                                                                           captions, and the split's summary with the oracle CIDEr-D)
+  python -m cvc.sample --sample_n 5 --diversity --self_cider ...         (also every segment's Self-CIDEr and LSA diversity, and
+                                                                          their means in the summary)
 
---temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus / --without_replacement / --diversity are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
+--temperature / --sample_n / --sample_seed / --top_k / --top_p / --consensus / --without_replacement / --diversity / --self_cider are this module's own; every other flag is cvc.main's (options, YAML overlay, dataset,
 --resume with --load_best_score: the same checkpoint loading as an --inference_only evaluation).
 """
 from __future__ import annotations
@@ -40,7 +42,12 @@ def parse(argv=None):
                    help="add to every segment the diversity of its --sample_n captions (Div-1, Div-2, mBLEU-4, distinct captions; "
                         "cvc.metrics.set_diversity) and to the file the split's summary with the oracle and mean CIDEr-D; needs "
                         "--sample_n > 1")
+    p.add_argument("--self_cider", action="store_true",
+                   help="with --diversity: add to every segment's diversity the Self-CIDEr and LSA diversity of its captions "
+                        "(cvc.metrics.set_spectrum) and to the summary their means over the split")
     own, rest = p.parse_known_args(argv)
+    if own.self_cider and not own.diversity:
+        raise SystemExit("--self_cider needs --diversity (it adds to the diversity of every segment's captions)")
     if own.diversity and own.sample_n < 2:
         raise SystemExit("--diversity needs --sample_n > 1 (the diversity of a set of one caption says nothing)")
     if own.without_replacement and own.sample_n < 2:
@@ -64,7 +71,7 @@ def main(argv=None):
     own, rest = parse(argv)
     if "--inference_only" not in rest:
         rest = rest + ["--inference_only"]
-    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus, own.without_replacement, own.diversity))
+    return cvc_main.main(rest, sample=(own.sample_n, own.temperature, own.sample_seed, own.top_k, own.top_p, own.consensus, own.without_replacement, own.diversity) + ((True,) if own.self_cider else ()))
 
 
 if __name__ == "__main__":

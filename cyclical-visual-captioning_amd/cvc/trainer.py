@@ -100,7 +100,7 @@ class Trainer:
     _averaged = 0                     # depth of averaged_weights(): non-zero while the parameters hold the weight averages
 
     def __init__(self, opts, dataset, model, optimizer, train_loader, val_loader, scorer=None, grad_reducer=None, device_metrics=False,
-                 val_diversity=False, ema=None):
+                 val_diversity=False, ema=None, val_self_cider=False):
         self.opts = opts
         self.dataset = dataset
         self.model = model
@@ -115,6 +115,11 @@ class Trainer:
         # eval(): the diversity of every clip's candidate set (cvc.metrics.DiversityScorer over model.last_consensus) next to the
         # device metrics; off: eval is what it was
         self.val_diversity = bool(val_diversity)
+        # eval(): Self-CIDEr and LSA diversity of the same candidate sets (cvc.metrics.SpectrumScorer) next to the set diversity;
+        # off: eval is what it was
+        self.val_self_cider = bool(val_self_cider)
+        if self.val_self_cider and not self.val_diversity:
+            raise RuntimeError("Trainer: val_self_cider scores the candidate sets of val_diversity -- it needs val_diversity=True")
         self._val_cider = None        # cvc.cider.CiderD over the validation loader's captions, built at the first eval
         self._word_cls = None         # word id -> detection class (utils.word_class_table), built at the first eval that grounds
         self.device = next(model.parameters()).device
@@ -950,6 +955,10 @@ class Trainer:
                                    "beam): the candidates it scores are those of the consensus selection")
             from .metrics import DiversityScorer
             div_scorer = DiversityScorer()
+        spec_scorer = None
+        if div_scorer is not None and self.val_self_cider:
+            from .metrics import SpectrumScorer
+            spec_scorer = SpectrumScorer(self._val_cider)
         with torch.no_grad():
             for b in DevicePrefetcher(self.val_loader, lambda raw: self._prepare(raw, False), self.device):
                 seq, att2_weights, _ = self._call(b, True)
@@ -962,6 +971,8 @@ class Trainer:
                         per = cand.size(0) // seq.size(0) if cand.dim() == 2 else cand.size(1)
                         div_scorer.add(cand.reshape(-1, cand.size(-1)), per, None if last.get("live") is None else last["live"].reshape(-1),
                                        b["gt_seqs"][:, :, :T].contiguous(), b["num"][:, 0].to(torch.int32), self._val_cider)
+                        if spec_scorer is not None:         # the same sets and live mask; no host read
+                            spec_scorer.add(cand.reshape(-1, cand.size(-1)), per, None if last.get("live") is None else last["live"].reshape(-1))
                 if getattr(o, "eval_obj_grounding", False):
                     assert o.beam_size == 1, 'only support beam_size is 1'
                     if grd_scorer is not None:
@@ -983,6 +994,9 @@ class Trainer:
         if div_scorer is not None:                          # ONE read per validation pass
             res = self._merged_diversity(div_scorer)
             lang_stats = {**lang_stats, **{k: res[k] for k in ("Div_1", "Div_2", "mBLEU_4", "Unique", "oracle_CIDEr") if k in res}}
+        if spec_scorer is not None:                         # ONE read per validation pass
+            res = self._merged_spectrum(spec_scorer)
+            lang_stats = {**lang_stats, "Self_CIDEr": res["Self_CIDEr"], "LSA": res["LSA"]}
         if getattr(o, "eval_obj_grounding_gt", False):        # (every rank: its shards are merged like the predictions)
             self._eval_ground_gt(epoch, tb_logger)
         self.submission_file = self.attn_file = None
@@ -1036,6 +1050,22 @@ class Trainer:
         parts = [None] * dist.get_world_size()
         dist.all_gather_object(parts, mine)
         return diversity_from_sums([sum(p[0][i] for p in parts) for i in range(13)], [sum(p[1][i] for p in parts) for i in range(7)])
+
+    @staticmethod
+    def _merged_spectrum(spec_scorer):
+        """one host read of this rank's sums; with several ranks the sums are exchanged host-side and merged through add_sums on
+        every rank, in rank order (more than one rank: untested)"""
+        import torch.distributed as dist
+        from .metrics import SpectrumScorer, spectrum_from_sums
+        mine = spec_scorer.sums()
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return spectrum_from_sums(mine)
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+        merged = SpectrumScorer()
+        for p in parts:
+            merged.add_sums(p)
+        return merged.result()
 
     def _grounding_scorer(self):
         """a fresh cvc.metrics.GroundingScorer; the word -> detection class table is built once, at the first eval"""
@@ -1171,7 +1201,8 @@ class Trainer:
 
     @_averaged_by_default
     def sample(self, n: int, temperature: float, seed: int = 0, stem: str = None, top_k: int = 0, top_p: float = 1.0,
-               constraints: dict = None, consensus: bool = False, without_replacement: bool = False, diversity: bool = False):
+               constraints: dict = None, consensus: bool = False, without_replacement: bool = False, diversity: bool = False,
+               self_cider: bool = False):
         """Sampled decode of the validation split: n captions per segment, every word drawn from softmax(logits / temperature)
         without UNK (DecodeEngine's sampling mode; the engine is seeded once with `seed`, later batches draw fresh noise);
         top_k / top_p truncate that distribution (0 / 1.0 = off; the log-probs stay the model's, over the full vocabulary).
@@ -1193,11 +1224,16 @@ class Trainer:
         others, the number of different sentences), and the file gains the top-level key "diversity": the split's summary
         (cvc.metrics.DiversityScorer.result(), with oracle_CIDEr and mean_CIDEr against the validation references), which is also
         logged and kept in self.sample_diversity.  Off: the file is what it was.
+        self_cider=True (with diversity=True): every entry's "diversity" gains "selfcider" and "lsa" -- the set's Self-CIDEr over the
+        validation captions' table and its LSA diversity (cvc.metrics.set_spectrum, score 0 in mode cider and score 1 in mode lsa) --
+        and the summary gains Self_CIDEr and LSA (cvc.metrics.SpectrumScorer.result()).  Off: the file is what it was.
         Returns the path (None on the other ranks)."""
         model = self._decoder()
         n = int(n)
         if diversity and n < 2:
             raise RuntimeError(f"Trainer.sample: diversity is that of a set of n > 1 captions per segment, got n = {n}")
+        if self_cider and not diversity:
+            raise RuntimeError("Trainer.sample: self_cider adds to the diversity of every set -- it needs diversity=True")
         model.eval()
         o, ds = self.opts, self.dataset
         timestamps = self._segment_timestamps()
@@ -1207,6 +1243,10 @@ class Trainer:
             from .metrics import DiversityScorer, corpus_bleu
             div_scorer = DiversityScorer()
             self._device_scorer()                           # (builds the validation captions' CIDEr-D table once)
+        spec_scorer = None
+        if self_cider:
+            from .metrics import SpectrumScorer
+            spec_scorer = SpectrumScorer(self._val_cider)
         if without_replacement:
             if n < 2:
                 raise RuntimeError(f"Trainer.sample: without_replacement draws n > 1 distinct captions per segment, got n = {n}")
@@ -1241,6 +1281,9 @@ class Trainer:
                     div_l = dv["div"].tolist()
                     set_l = dv["stats"].tolist()
                     mb_l = dv["mbleu_stats"].view(-1, n, 10).sum(1).tolist()
+                    if spec_scorer is not None:
+                        sp = spec_scorer.add(seq.contiguous(), n, live)
+                        sc_l, lsa_l = sp["cider"]["score"][:, 0].tolist(), sp["lsa"]["score"][:, 1].tolist()
                 sents = utils.decode_sequence(ds.itow, getattr(ds, "itod", None), getattr(ds, "ltow", None),
                                               getattr(ds, "itoc", None), getattr(ds, "wtod", None), seq.data, o.vocab_size, o)
                 # sequence log-prob: the steps up to and including the first EOS (word 0)
@@ -1260,10 +1303,15 @@ class Trainer:
                     if diversity:
                         samples[vid_idx][-1]["diversity"] = {"div1": div_l[k][0], "div2": div_l[k][1],
                                                              "mbleu4": float(corpus_bleu(mb_l[k])[3]), "unique": set_l[k][9]}
+                        if spec_scorer is not None:
+                            samples[vid_idx][-1]["diversity"].update(selfcider=sc_l[k], lsa=lsa_l[k])
         samples, _ = gather_eval_outputs(samples, {})
         self.samples = samples
         if diversity:
             self.sample_diversity = self._merged_diversity(div_scorer)
+            if spec_scorer is not None:
+                res = self._merged_spectrum(spec_scorer)
+                self.sample_diversity = {**self.sample_diversity, "Self_CIDEr": res["Self_CIDEr"], "LSA": res["LSA"]}
             samples = dict(samples)
             samples["diversity"] = self.sample_diversity
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:

@@ -654,6 +654,30 @@ int cvc_consensus_cider(const int64_t* cand, const int32_t* live, int rows, int 
 int cvc_caption_set_stats(const int64_t* cand, const int32_t* live, int rows, int T, int per_clip, int32_t* set_stats,
                           int32_t* mbleu_stats, float* mbleu, cvc_stream_t stream);
 
+/* ---- spectral caption-set diversity: the eigenvalues of a clip's m x m caption-similarity matrix and the two scores formed from
+ * them (Self-CIDEr, LSA-based diversity; Wang & Chan 2019), one launch (csrc/spectrum.hip; cvc.metrics.set_spectrum,
+ * DecodeEngine.set_spectrum).
+ *   cand [rows, T] int64, per_clip, live [rows] int32 (nullable: every row is live) and a caption's words as cvc_caption_set_stats.
+ *   m = the clip's live rows; they are indexed 0 .. m - 1 in ascending row order.
+ *   mode 0 (cider): v_n^a[g] = count_a(g) * idf(g), n = 1..4, idf from the sorted table keys / idf [G] as cvc_consensus_cider
+ *     (idf_unseen for an absent key); s_n(a, b) = <v_n^a, v_n^b> / (|v_n^a| |v_n^b|), 0 when a norm is 0; K[a, b] = 1/4 sum_n s_n.
+ *     Plain CIDEr similarity: no clipping, no length term, no factor 10; K[a, a] = min(L, 4) / 4 exactly where the idf are > 0.
+ *   mode 1 (lsa): K[a, b] = sum_w count_a(w) count_b(w) over unigrams, exact; keys / idf / G / idf_unseen are not read.
+ *   gram [clips, 32, 32] fp32 (nullable): K at the live rows' indices, exactly symmetric, 0 at indices >= m.
+ *   lam [clips, 32] fp64: the eigenvalues of the m x m matrix in descending order, zeros behind them (two-sided Jacobi in fp64, a
+ *     fixed parallel round-robin ordering; a rotation is skipped when |K_pq| <= 4 * 2^-53 * trace, a sweep without a rotation ends
+ *     the solve, at most 16 sweeps).
+ *   score [clips, 2] fp32, formed in fp64 and rounded once, tr = the trace taken before the solve:
+ *     0: -log(min(lam_1 / tr, 1)) / log(m);   1: -log(sqrt(lam_1) / sum_i sqrt(max(lam_i, 0))) / log(m);   both 0 where m < 2 or tr = 0.
+ *   info [clips, 2] int32: m; the sweeps run, -1 if the 16th still rotated.
+ * One workgroup per clip, one wave solves.  No atomics, no workspace: a clip's outputs are bit-reproducible and independent of the
+ * other clips.  Launch only (no host read, no allocation): capturable in a HIP graph.
+ * Null pointers (but live and gram; keys / idf in mode 1 or with G = 0), rows < 1, rows % per_clip != 0, per_clip < 1 or > 32,
+ * T < 1 or > 63, a mode other than 0 or 1, G < 0 in mode 0: CVC_E_BADARG, before any launch. */
+int cvc_caption_set_spectrum(const int64_t* cand, const int32_t* live, int rows, int T, int per_clip, int mode,
+                             const unsigned long long* keys, const float* idf, int G, float idf_unseen, float* gram, double* lam,
+                             float* score, int32_t* info, cvc_stream_t stream);
+
 /* ---- grounding F1 of generated captions: per object word the most attended proposal of every sampled frame, tested against the
  * clip's annotated boxes and counted per detection class, one launch (csrc/grounding.hip; cvc.metrics.grounding, Trainer.eval).
  *   seq [rows, T] int64: row r belongs to clip r / per_clip; its words are the ids before the first 0 (all T without one).
