@@ -82,8 +82,10 @@ def up_to_date() -> bool:
 # forms carry a fifth, the shadow; the swap two: profiles/ema.md)
 # (spectrum.hip: the build pass keeps four keys, counts and search bounds per lane, the solve fp64 2 x 2 blocks -- scratch there
 # would turn the one wave that solves into the launch's whole cost; the entry covers both instantiations)
+# (consensus_mix.hip: the pair walk keeps four counts, the LCS bit vector and six metrics per lane next to the build pass's four
+# keys and search bounds -- scratch in the inner walk would multiply a launch that runs n (n - 1) of them per clip; both instantiations)
 NO_SCRATCH_KERNELS = {"gemm_nn.hip": ("skinny_gemm_nn_split128_kernel",), "gemm_packed.hip": ("skinny_gemm_packed_kernel",),
-                      "spectrum.hip": ("caption_set_spectrum_kernel",),
+                      "spectrum.hip": ("caption_set_spectrum_kernel",), "consensus_mix.hip": ("consensus_mix_kernel",),
                       "mix.hip": ("sample_select_kernel",), "ensemble.hip": ("ensemble_logprobs_kernel",),
                       "distill.hip": ("vocab_kd_fwd_kernel", "vocab_kd_bwd_kernel"),
                       "optim.hip": ("optim_adam_kernel", "optim_sgd_kernel", "optim_adamax_kernel", "optim_adam_ema_kernel", "optim_sgd_ema_kernel",

@@ -21,69 +21,19 @@
 //   LDS per workgroup: 1820 bytes per row + 4352; the kernel is instantiated for <= 8 and <= 32 rows per clip (18 912 / 62 592 bytes).
 #include "cvc_common.h"
 #include "caption_ngrams.h"
+#include "caption_windows.h"
 #include <math.h>
 
 namespace {
 
 using cvc_caption::MAXT;
 using cvc_caption::ngram_key;
+using cvc_windows::lane_key;
+using cvc_windows::lead_words;
+using cvc_windows::idf_of4;
 
 constexpr int MAX_PER_CLIP = 32;
 constexpr int MAX_WAVES = 16;
-
-// lane p's value in every lane (p is wave-uniform)
-__device__ __forceinline__ unsigned long long lane_key(unsigned long long v, int p) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, p);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), p);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// on how many leading 16-bit words two windows agree, given their exclusive or (4: on all) -- the n-grams of order n that start
-// at the two positions are the same one iff this is >= n, provided one of them is an n-gram at all (its n words are non-zero)
-__device__ __forceinline__ int lead_words(unsigned long long x) { return x != 0ull ? (int)__builtin_clzll(x) >> 4 : 4; }
-
-// idf of key[n] where own[n], from the sorted table (cider_d_kernel's idf_of: the same binary search, hence the same entry) -- the
-// four searches advance together, so that their dependent loads overlap; a lane that owns nothing re-reads keys[0]
-__device__ __forceinline__ void idf_of4(const unsigned long long* keys, const float* idf, int G, float idf_unseen,
-                                        const unsigned long long (&key)[4], const bool (&own)[4], float (&w)[4]) {
-    int lo[4], hi[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        lo[n] = 0;
-        hi[n] = own[n] ? G : 0;
-    }
-    int steps = 0;                                 // [0, G) is empty after floor(log2 G) + 1 halvings
-    while (steps < 31 && (1u << steps) <= (unsigned)G) ++steps;
-    for (int s = 0; s < steps; ++s) {
-        unsigned long long k[4];
-        int mid[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            mid[n] = (int)(((unsigned)lo[n] + (unsigned)hi[n]) >> 1);
-            k[n] = keys[lo[n] < hi[n] ? mid[n] : 0];
-        }
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-            if (lo[n] < hi[n]) {
-                if (k[n] < key[n]) lo[n] = mid[n] + 1; else hi[n] = mid[n];
-            }
-    }
-#pragma unroll
-    for (int n = 0; n < 4; ++n) w[n] = idf_unseen;
-    if (G > 0) {
-        unsigned long long k[4];
-        float v[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const int at = lo[n] < G ? lo[n] : 0;
-            k[n] = keys[at];
-            v[n] = idf[at];
-        }
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-            if (lo[n] < G && k[n] == key[n]) w[n] = v[n];
-    }
-}
 
 template <int NMAX>
 __global__ __launch_bounds__(64 * MAX_WAVES) void consensus_cider_kernel(const int64_t* cand, const int32_t* live, int T, int per_clip,

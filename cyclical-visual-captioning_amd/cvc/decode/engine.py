@@ -675,22 +675,57 @@ class DecodeEngine(PackedPath, TilePath, RingPath, ExperimentalPaths):
         return (seq.gather(1, o.unsqueeze(2).expand(B, beam, T)), score.gather(1, o), self.norm.gather(1, o),
                 self.final_nmet.gather(1, o) if self.forcing else o // (beam // self.groups))
 
-    def consensus(self, table):
+    def consensus(self, table, utility=None, weights: str = "uniform", alpha: float = 1.0, want_pairs: bool = False):
         """Consensus (minimum-Bayes-risk) selection among the candidates of the last run() ("Consensus
         selection"): per clip the candidate with the highest mean CIDEr-D against the clip's other candidates as stand-in
         references, over `table` (a cvc.cider.CiderD; csrc/consensus.hip).  A sampling engine with sample_n > 1: the n samples of
         a clip.  A beam engine with beam_history=True: its hypotheses(), live where the score is finite.
+        utility: None, or a mix {name: weight} over cvc.metrics.REWARD_NAMES -- the pair utility is then the weighted sum of CIDEr-D,
+        BLEU-1..4 and ROUGE-L of the candidate against ONE other candidate.  weights: "uniform", or "model" -- every other candidate
+        counts as a reference with weight exp(alpha * score), score the model's log-prob of the hypothesis (hypotheses()); a history
+        beam only (diverse and forced beams included): the candidates of a sampling engine and of a stochastic beam are draws, their
+        uniform mean is the expectation already, and both refuse "model".  alpha: finite, >= 0 (0: uniform again).
+        With utility None or CIDEr-D alone at weight 1 AND uniform weights the launch is cvc_consensus_cider, as ever; anything else
+        is one launch of cvc_consensus_mix (csrc/consensus_mix.hip; cvc.metrics.consensus), and self.consensus_logw keeps the
+        log-weights it used (None: uniform); want_pairs=True forces that launch and keeps its raw pair metrics [B, n, n, 6] in
+        self.consensus_pairs.
         -> (seq [B, T], att2_weights [B, T, N], logprob [B, T] or None for a beam, pick [B] int32 -- the index of the kept sample /
         the kept slot --, utility [B * n] fp32), new tensors, everything selected on the device with pick (a beam's attention rows
         by cvc_beam_backtrack_from the picked slot); no host read-back."""
+        from .. import metrics
+        if weights not in ("uniform", "model"):
+            raise RuntimeError(f"DecodeEngine.consensus: weights must be 'uniform' or 'model', got {weights!r}")
+        alpha = float(alpha)
+        if not (alpha >= 0.0) or alpha == float("inf"):
+            raise RuntimeError(f"DecodeEngine.consensus: alpha must be a finite number >= 0, got {alpha!r}")
+        if weights == "model" and self.sampling:
+            raise RuntimeError("DecodeEngine.consensus: weights='model' on a sampling engine -- its candidates are draws from the model, "
+                               "the uniform mean over them is the expectation already; use weights='uniform'")
+        if weights == "model" and self.stoch:
+            raise RuntimeError("DecodeEngine.consensus: weights='model' on a stochastic beam -- its candidates are draws without "
+                               "replacement (importance weights for them are not implemented); use weights='uniform'")
+        mix = None if (weights == "uniform" and metrics.is_cider_only(utility) and not want_pairs) else metrics.utility_coefficients(
+            utility or {"cider": 1.0}, "DecodeEngine.consensus")
         cand, n, live = self.candidates("consensus")
         self.consensus_live = live          # (the mask this selection used: None = every sample counts; model.last_consensus keeps it)
+        self.consensus_logw = self.consensus_pairs = None
+        if mix is not None:
+            if weights == "model":
+                self.consensus_logw = (self.hypotheses()[1].reshape(-1) * alpha).contiguous()
+            mix = dict(zip(metrics.REWARD_NAMES, mix))
+
+            def select(cand, n, live=None):
+                out = metrics.consensus(cand, n, mix, table, self.consensus_logw, live, want_pairs=want_pairs)
+                self.consensus_pairs = out.get("pairs")
+                return out["utility"], out["pick"], out["best"]
+        else:
+            select = table.consensus
         B, T, N = self.B, self.T, self.N
         if self.sampling:
-            utility, pick, best = table.consensus(cand, n)
+            utility, pick, best = select(cand, n)
             at = torch.arange(B, device=cand.device) * n + pick
             return (best, self.att_steps.permute(1, 0, 2).index_select(0, at), self.logprob.t().index_select(0, at), pick, utility)
-        utility, pick, _ = table.consensus(cand, n, live=live)
+        utility, pick, _ = select(cand, n, live=live)
         start = pick.to(torch.int64)
         bt_seq = torch.empty(B, T, dtype=torch.int64, device=start.device)
         bt_att = torch.empty(B, T, N, dtype=torch.float32, device=start.device)

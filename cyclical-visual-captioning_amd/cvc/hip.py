@@ -289,6 +289,7 @@ SIGNATURES = {
     "cvc_caption_overlap": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     # consensus caption selection: pairwise CIDEr-D among a clip's candidates, pick and picked row (csrc/consensus.hip; building block)
     "cvc_consensus_cider": [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P],
+    "cvc_consensus_mix": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     # caption-set diversity: distinct n-grams, mBLEU statistics, distinct captions per clip (csrc/diversity.hip; building block)
     "cvc_caption_set_stats": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
     # spectral caption-set diversity: similarity matrix, its eigenvalues, Self-CIDEr / LSA scores (csrc/spectrum.hip; building block)
@@ -359,7 +360,7 @@ BLOCKS = {
     "cvc_lstm_persistent_sync_words", "cvc_lstm_seq_persistent_fwd", "cvc_lstm_seq_persistent_train_fwd", "cvc_lstm_seq_fwd", "cvc_lstm_seq_train_fwd", "cvc_lstm_seq_bwd_work", "cvc_lstm_seq_bwd",
     "cvc_packed_lstm_bf16w_fwd", "cvc_packed_linear_bf16w_fwd",
     "cvc_packed_linear_keys_fwd", "cvc_packed_lstm_embgate_keys_fwd", "cvc_keys_finalize",
-    "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider",
+    "cvc_cider_d", "cvc_scst_weights", "cvc_scst_weights_wor", "cvc_mixed_select_parts", "cvc_caption_overlap", "cvc_consensus_cider", "cvc_consensus_mix",
     "cvc_caption_set_stats", "cvc_caption_set_spectrum", "cvc_grounding_f1", "cvc_vocab_head_nll_ls_fwd", "cvc_vocab_nll_ls_fwd", "cvc_vocab_nll_ls_bwd",
     "cvc_vocab_head_nll_ent_fwd", "cvc_vocab_nll_ent_fwd", "cvc_vocab_nll_ent_bwd", "cvc_ensemble_logprobs", "cvc_ensemble_mix",
     "cvc_vocab_head_nll_kd_fwd", "cvc_vocab_nll_kd_fwd", "cvc_vocab_nll_kd_bwd", "cvc_sgd_clip_step", "cvc_adamax_clip_step",
@@ -1486,6 +1487,46 @@ def consensus_cider(cand: torch.Tensor, per_clip: int, keys: torch.Tensor, idf: 
                                      float(idf_unseen), float(sigma), _dev(utility), _dev(pick, torch.int32), _dev(best, torch.int64),
                                      _stream()), "cvc_consensus_cider")
     return utility, pick, best
+
+
+# --------------------------------------------------------------------------- consensus under a utility mix (csrc/consensus_mix.hip)
+CONSENSUS_METRICS = 6        # cider, bleu1..4, rougel: the order of cvc.metrics.REWARD_NAMES
+
+
+def consensus_mix(cand: torch.Tensor, per_clip: int, coef, keys: Optional[torch.Tensor] = None, idf: Optional[torch.Tensor] = None,
+                  idf_unseen: float = 0.0, sigma: float = 6.0, live: Optional[torch.Tensor] = None,
+                  logw: Optional[torch.Tensor] = None, want_pairs: bool = False):
+    """cand [rows, T] int64, per_clip consecutive candidates per clip; coef: six numbers >= 0 (cider, bleu1..4, rougel), not all 0;
+    keys [G] int64 holding the table's unsigned 64-bit keys and idf [G] (needed with coef[0] > 0 only); live [rows] int32 or None (every
+    row is live); logw [rows] fp32 log-weights or None (uniform).  -> utility [rows] fp32 (the weighted mean over the clip's other
+    live rows j of sum_k coef[k] metric_k(row; j)), pick [clips] int32, best [clips, T] int64, pairs [clips, per_clip, per_clip, 6]
+    fp32 (None unless want_pairs)."""
+    per_clip = int(per_clip)
+    coef = [float(c) for c in coef]
+    if len(coef) != CONSENSUS_METRICS:
+        raise RuntimeError(f"cvc.hip.consensus_mix: coef holds {len(coef)} numbers; it takes {CONSENSUS_METRICS} (cider, bleu1..4, rougel)")
+    cider = coef[0] > 0.0
+    if cider and (keys is None or idf is None):
+        raise RuntimeError("cvc.hip.consensus_mix: a CIDEr coefficient needs the idf table (keys, idf)")
+    if cand.dim() != 2 or per_clip < 1 or cand.shape[0] < 1 or cand.shape[0] % per_clip != 0 \
+            or (live is not None and live.numel() != cand.shape[0]) or (logw is not None and logw.numel() != cand.shape[0]) \
+            or (cider and idf.numel() != keys.numel()):
+        raise RuntimeError(f"cvc.hip.consensus_mix: cand {tuple(cand.shape)}, per_clip {per_clip}, live "
+                           f"{None if live is None else tuple(live.shape)}, logw {None if logw is None else tuple(logw.shape)}"
+                           + (f", keys {tuple(keys.shape)}, idf {tuple(idf.shape)}" if cider else "") + " do not fit")
+    rows, T = cand.shape
+    clips = rows // per_clip
+    G = int(keys.numel()) if cider else 0
+    utility = torch.empty(rows, device=cand.device, dtype=torch.float32)
+    pick = torch.empty(clips, device=cand.device, dtype=torch.int32)
+    best = torch.empty(clips, T, device=cand.device, dtype=torch.int64)
+    pairs = torch.empty(clips, per_clip, per_clip, CONSENSUS_METRICS, device=cand.device, dtype=torch.float32) if want_pairs else None
+    c_coef = (C.c_float * CONSENSUS_METRICS)(*coef)          # read on the host before the launch
+    _check(lib().cvc_consensus_mix(_dev(cand, torch.int64, "cand"), _dev(live, torch.int32, "live"), _dev(logw, name="logw"), rows, T,
+                                   per_clip, _dev(keys, torch.int64, "keys") if G else None, _dev(idf, name="idf") if G else None, G,
+                                   float(idf_unseen), float(sigma), C.addressof(c_coef), _dev(utility), _dev(pick, torch.int32),
+                                   _dev(best, torch.int64), _dev(pairs), _stream()), "cvc_consensus_mix")
+    return utility, pick, best, pairs
 
 
 # --------------------------------------------------------------------------- caption-set diversity (csrc/diversity.hip)

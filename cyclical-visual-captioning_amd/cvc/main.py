@@ -112,6 +112,20 @@ def build_parser():
     parser.add_argument("--consensus_samples", type=int, default=16, help="sampled candidates per clip (2 .. 32)")
     parser.add_argument("--consensus_temperature", type=float, default=1.0, help="temperature of the sampled candidates")
     parser.add_argument("--consensus_seed", type=int, default=1, help="seed of the sampled candidates' noise")
+    # the selection's utility and the candidates' weights (DecodeEngine.consensus; csrc/consensus_mix.hip): absent by default and
+    # then no key in the options, no launch changes
+    parser.add_argument("--consensus_utility", type=str, default=argparse.SUPPRESS,
+                        help="the utility of the consensus selection, a mix in --scst_reward's form over cider, bleu1..bleu4, rougel "
+                             "(e.g. cider:1,bleu4:0.5,rougel:0.5): each of a clip's other candidates is ONE reference, the pick has "
+                             "the highest (weighted) mean; default: CIDEr-D alone.  Needs --consensus samples|beam (cvc.sample: "
+                             "its --consensus)")
+    parser.add_argument("--consensus_weights", choices=("uniform", "model"), default=argparse.SUPPRESS,
+                        help="how much each other candidate counts as a reference: uniform (default), or model = by "
+                             "exp(--consensus_alpha x the model's log-prob of the hypothesis); model needs --consensus beam without "
+                             "--stochastic_beam (sampled candidates are draws: their uniform mean is the expectation already)")
+    parser.add_argument("--consensus_alpha", type=float, default=argparse.SUPPRESS,
+                        help="with --consensus_weights model: the exponent on the hypotheses' probabilities, finite and >= 0 "
+                             "(default 1; 0 = uniform)")
     # stochastic beam search at evaluation (model._sample(stochastic_beam=...); DecodeEngine stochastic)
     parser.add_argument("--stochastic_beam", action="store_true",
                         help="beam search by Gumbel-perturbed keys: the --beam_size hypotheses are distinct samples drawn without "
@@ -281,6 +295,34 @@ def check_val_diversity_flag(opt):
         raise SystemExit("--val_diversity needs a candidate set per clip in evaluation: --consensus samples or --consensus beam")
 
 
+def check_consensus_mix_flags(opt, sample=None):
+    """--consensus_utility / --consensus_weights / --consensus_alpha refine a consensus selection: given without one (--consensus
+    samples|beam; under cvc.sample its own --consensus), with a mix that does not parse, with model weights over sampled candidates,
+    or with an alpha that is not a finite number >= 0, the run ends with a message, before any set-up.  The parsed mix replaces the
+    string in opt.consensus_utility ({name: weight}, what the model reads)."""
+    import math
+    given = [k for k in ("consensus_utility", "consensus_weights", "consensus_alpha") if hasattr(opt, k)]
+    if not given:
+        return
+    selecting = (len(sample) > 5 and bool(sample[5])) if sample is not None else opt.consensus != "off"
+    if not selecting:
+        raise SystemExit("--%s refines the consensus selection: it needs --consensus samples or --consensus beam (python -m cvc.sample: "
+                         "--consensus)" % given[0])
+    if hasattr(opt, "consensus_utility"):
+        from .metrics import parse_reward_weights
+        opt.consensus_utility = parse_reward_weights(opt.consensus_utility, "--consensus_utility")
+        if not any(w > 0 for w in opt.consensus_utility.values()):
+            raise SystemExit("--consensus_utility: every weight is 0 -- the utility would weigh nothing")
+    if getattr(opt, "consensus_weights", "uniform") == "model":
+        if sample is not None or opt.consensus != "beam" or opt.stochastic_beam:
+            raise SystemExit("--consensus_weights model weights the hypotheses of a beam by the model's probability: it needs "
+                             "--consensus beam without --stochastic_beam (the candidates of --consensus samples, of cvc.sample and of "
+                             "a stochastic beam are draws, whose uniform mean is the expectation already)")
+    alpha = getattr(opt, "consensus_alpha", None)
+    if alpha is not None and not (math.isfinite(alpha) and alpha >= 0):
+        raise SystemExit("--consensus_alpha must be a finite number >= 0, got %r" % (alpha,))
+
+
 def check_label_smoothing_flag(eps):
     """--label_smoothing lies in [0, 1) (a NaN does not): anything else ends the run with a message, before any set-up"""
     if not 0.0 <= eps < 1.0:
@@ -307,6 +349,7 @@ def main(argv=None, sample=None, score=None):
     check_label_smoothing_flag(opt.label_smoothing)
     check_entropy_flags(opt)
     check_val_diversity_flag(opt)
+    check_consensus_mix_flags(opt, sample)
     check_ema_flags(opt)
     if not opt.no_cfg:
         opt = cvc_opts.load_cfg(opt)

@@ -69,9 +69,10 @@ def corpus_bleu(stats_sum) -> np.ndarray:
     return out
 
 
-def parse_reward_weights(spec: str) -> dict:
+def parse_reward_weights(spec: str, flag: str = "--scst_reward") -> dict:
     """"cider:1,bleu4:0.5,rougel:0.5" -> {name: weight} in the fixed order of REWARD_NAMES (names that are not given: absent).  An
-    unknown name, a repeated name, a weight that is no number or negative, or an empty mix is a SystemExit that says so."""
+    unknown name, a repeated name, a weight that is no number or negative, or an empty mix is a SystemExit that says so, naming
+    `flag`, the switch the spec came from (--consensus_utility is parsed here too)."""
     got = {}
     for item in (x.strip() for x in (spec or "").split(",")):
         if not item:
@@ -79,18 +80,18 @@ def parse_reward_weights(spec: str) -> dict:
         name, sep, val = item.partition(":")
         name = name.strip().lower()
         if name not in REWARD_NAMES:
-            raise SystemExit("--scst_reward: unknown metric %r (known: %s)" % (name, ", ".join(REWARD_NAMES)))
+            raise SystemExit(flag + ": unknown metric %r (known: %s)" % (name, ", ".join(REWARD_NAMES)))
         if name in got:
-            raise SystemExit("--scst_reward: %r is given twice" % name)
+            raise SystemExit(flag + ": %r is given twice" % name)
         try:
             w = float(val) if sep else 1.0
         except ValueError:
-            raise SystemExit("--scst_reward: the weight of %r, %r, is not a number" % (name, val))
+            raise SystemExit(flag + ": the weight of %r, %r, is not a number" % (name, val))
         if not (w >= 0.0) or math.isinf(w):
-            raise SystemExit("--scst_reward: the weight of %r must be a finite number >= 0, got %r" % (name, val))
+            raise SystemExit(flag + ": the weight of %r must be a finite number >= 0, got %r" % (name, val))
         got[name] = w
     if not got:
-        raise SystemExit("--scst_reward: no metric given")
+        raise SystemExit(flag + ": no metric given")
     return {k: got[k] for k in REWARD_NAMES if k in got}
 
 
@@ -122,6 +123,57 @@ def reward_mix(weights: dict, table, seq: torch.Tensor, refs: torch.Tensor, nref
     if reward is None:
         reward = torch.zeros(seq.shape[0], device=seq.device, dtype=torch.float32)
     return reward, parts
+
+
+def utility_coefficients(utility: dict, who: str = "metrics.consensus") -> list:
+    """a utility mix in parse_reward_weights' form -> its six coefficients in the order of REWARD_NAMES; an unknown name, a weight that
+    is negative or not finite, or a mix without a positive weight raises RuntimeError"""
+    unknown = [k for k in (utility or {}) if k not in REWARD_NAMES]
+    if unknown:
+        raise RuntimeError(f"{who}: utility names unknown metrics {unknown} (known: {', '.join(REWARD_NAMES)})")
+    coef = [float((utility or {}).get(k, 0.0)) for k in REWARD_NAMES]
+    if any(not (c >= 0.0) or math.isinf(c) for c in coef):
+        raise RuntimeError(f"{who}: utility weights must be finite numbers >= 0, got {dict(utility)}")
+    if not any(c > 0.0 for c in coef):
+        raise RuntimeError(f"{who}: utility weights nothing -- give at least one of {', '.join(REWARD_NAMES)} a weight > 0")
+    return coef
+
+
+def consensus(cand: torch.Tensor, per_clip: int, utility: dict, table=None, log_weights: Optional[torch.Tensor] = None,
+              live: Optional[torch.Tensor] = None, want_pairs: bool = False) -> dict:
+    """Consensus (minimum-Bayes-risk) selection under a mix of utilities and weighted candidates (csrc/consensus_mix.hip; DESIGN
+    section 7, "Weighted candidates and utility mixes").  cand [rows, T] int64 on the device, per_clip consecutive candidates per clip;
+    utility: {name: weight} over REWARD_NAMES (parse_reward_weights' form); table: a cvc.cider.CiderD, needed when cider is weighted;
+    log_weights [rows] (None: uniform): the candidates' log-weights as references, e.g. alpha * the model's log-prob of the caption;
+    live [rows] (None: every row counts).
+      u(i, j) = sum_k weight_k * metric_k(row i as the candidate, row j as its only reference), added in the order of REWARD_NAMES
+      utility[i] = sum_j w_j u(i, j) / sum_j w_j over the clip's other live rows, w_j = exp(logw_j - max logw)
+    -> dict(utility [rows] fp32, pick [clips] int32 (the first live row with the largest utility), best [clips, T] int64 (, pairs
+    [clips, per_clip, per_clip, 6] fp32: the raw pair metrics)), all on the device: one launch, no host read."""
+    from . import hip
+    from .cider import MAX_T, MAX_PER_CLIP
+    coef = utility_coefficients(utility)
+    if cand.dim() != 2 or cand.shape[1] > MAX_T:
+        raise RuntimeError(f"metrics.consensus: cand {tuple(cand.shape)}; the kernel takes rows of at most T = {MAX_T} words")
+    if int(per_clip) > MAX_PER_CLIP:
+        raise RuntimeError(f"metrics.consensus: {int(per_clip)} candidates per clip; the kernel takes at most per_clip = {MAX_PER_CLIP}")
+    keys = idf = None
+    idf_unseen, sigma = 0.0, 6.0
+    if coef[0] > 0.0:
+        if table is None:
+            raise RuntimeError("metrics.consensus: utility weights cider, which needs table, a cvc.cider.CiderD (the idf table); there "
+                               "is none")
+        if table.keys is None or table.keys.device != cand.device:
+            table.to(cand.device)
+        keys, idf, idf_unseen, sigma = table.keys, table.idf, table.idf_unseen, table.sigma
+    u, pick, best, pairs = hip.consensus_mix(cand.contiguous(), int(per_clip), coef, keys, idf, idf_unseen, sigma,
+                                             live=None if live is None else live.to(torch.int32).contiguous(),
+                                             logw=None if log_weights is None else log_weights.to(torch.float32).reshape(-1).contiguous(),
+                                             want_pairs=want_pairs)
+    out = dict(utility=u, pick=pick, best=best)
+    if want_pairs:
+        out["pairs"] = pairs
+    return out
 
 
 class DeviceScorer:

@@ -142,6 +142,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         self.consensus_samples = int(getattr(opts, "consensus_samples", 16))
         self.consensus_temperature = float(getattr(opts, "consensus_temperature", 1.0))
         self.consensus_seed = int(getattr(opts, "consensus_seed", 1))
+        # the utility mix ({name: weight} over cvc.metrics.REWARD_NAMES, None: CIDEr-D alone), the candidates' weights as references
+        # ("uniform" / "model": exp(consensus_alpha * the hypothesis' log-prob), beam candidates only), and whether last_consensus
+        # keeps the raw pair metrics (DecodeEngine.consensus; csrc/consensus_mix.hip)
+        self.consensus_utility = getattr(opts, "consensus_utility", None) or None
+        self.consensus_weights = str(getattr(opts, "consensus_weights", None) or "uniform")
+        self.consensus_alpha = 1.0 if getattr(opts, "consensus_alpha", None) is None else float(opts.consensus_alpha)
+        self.consensus_pairs = False
         self.consensus_table = None
         self.last_consensus: Optional[dict] = None
         # decode precision: "fp32", or "bf16" = the six weight matrices of the decode stored as bf16 (DecodeEngine weights_dtype)
@@ -764,7 +771,8 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
                 no_immediate_repeat: Optional[bool] = None, min_len: Optional[int] = None, ban_words=None, bad_endings=None,
                 beam_groups: Optional[int] = None, diversity_lambda: Optional[float] = None, length_penalty: Optional[float] = None,
                 force_words=None, encoded=None, consensus=None, stochastic_beam: Optional[bool] = None,
-                stochastic_tau: Optional[float] = None):
+                stochastic_tau: Optional[float] = None, consensus_utility=None, consensus_weights: Optional[str] = None,
+                consensus_alpha: Optional[float] = None):
         """reference :384-443: exactly seq_length decoder steps from BOS, no EOS early exit, UNK
         suppressed; returns (seq [B,T], att2_weights [B,T,N] post-softmax, None).
         sample_max = 0 (argument, else the model's attribute): every word is sampled from softmax(logits / temperature) without
@@ -798,6 +806,12 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         The candidates are exactly what the same call returns with consensus=False and the same seed; self.last_consensus =
         dict(candidates, pick, utility, live) keeps them (seq [B * n, T] / hypotheses [B, beam, T]) with the picks [B], the utilities
         [B * n] and the live mask the selection used (None: every sample counts / [B, beam] bool: the score is finite), device tensors.
+        consensus_utility / consensus_weights / consensus_alpha (arguments, else the model's attributes, read from opts; CIDEr-D
+        alone, "uniform", 1.0 by default): DecodeEngine.consensus's utility mix ({name: weight} over cvc.metrics.REWARD_NAMES), the
+        candidates' weights as references ("model": exp(alpha * the hypothesis' log-prob); beam candidates only, a sampling call and
+        a stochastic beam raise) and alpha.  At their defaults the selection is the launch it has always been; otherwise it is one
+        launch of cvc_consensus_mix.  last_consensus also holds weights (the log-weights used [B * n], None: uniform) and, with
+        self.consensus_pairs = True, pairs [B, n, n, 6] (the raw pair metrics).
         stochastic_beam / stochastic_tau (arguments, else the model's attributes, read from opts; off by default): stochastic beam
         search with beam_size > 1 -- the engine is built with beam_history=True and stochastic=True, seeded once with seed (else the
         model's sample_seed); the result is a beam decode's (seq, att2_weights, None) of slot 0, an ordinary sample of q_tau, and
@@ -812,6 +826,17 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         if mode is not None and self.consensus_table is None:
             raise RuntimeError("_sample: consensus selection needs model.consensus_table, a cvc.cider.CiderD (Trainer sets the "
                                "training captions' table); there is none")
+        c_util = self.consensus_utility if consensus_utility is None else consensus_utility
+        c_weights = self.consensus_weights if consensus_weights is None else consensus_weights
+        c_alpha = self.consensus_alpha if consensus_alpha is None else float(consensus_alpha)
+        if mode is not None:
+            if c_weights not in ("uniform", "model"):
+                raise RuntimeError(f"_sample: consensus_weights must be 'uniform' or 'model', got {c_weights!r}")
+            if not (c_alpha >= 0.0) or c_alpha == float("inf"):
+                raise RuntimeError(f"_sample: consensus_alpha must be a finite number >= 0, got {c_alpha!r}")
+            if c_util is not None:
+                from .. import metrics
+                metrics.utility_coefficients(c_util, "_sample: consensus_utility")
         if encoded is not None:
             fc_feats, conv_feats, p_conv_feats, pool_feats, p_pool_feats, pnt_mask = encoded
         else:
@@ -833,6 +858,10 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         stau = self.stochastic_tau if stochastic_tau is None else float(stochastic_tau)
         if stoch and not sampling:
             s_seed = self.sample_seed if seed is None else int(seed)
+        if mode is not None and c_weights == "model" and (sampling or stoch):
+            raise RuntimeError("_sample: consensus_weights = 'model' weights the hypotheses of a beam by the model's probability; the "
+                               "candidates of a sampling decode and of a stochastic beam are draws, whose uniform mean is the "
+                               "expectation already -- use consensus_weights = 'uniform' there")
         if mode is not None and not (n > 1 if (sampling and mode != "beam") else (not sampling and beam > 1)):
             raise RuntimeError(f"_sample: consensus selection needs several candidates per clip -- sample_max = 0 with sample_n > 1, or "
                                f"beam_size > 1 without sampling (got consensus = {mode!r}, sampling = {sampling}, sample_n = {n}, "
@@ -859,7 +888,9 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
         # "consensus on" is part of the key although it changes no argument of a sampling engine: a consensus call must not take
         # over the generator state of the previous call's engine (its candidates are what the same call draws without consensus)
         engine = self._decode_engine(
-            "_engine_cache", feats, self.seq_length, extra=(mode is not None,), may_bind=True, beam=beam, sample_n=n, temperature=tau,
+            "_engine_cache", feats, self.seq_length, extra=(mode is not None,) + ((
+                tuple(sorted(c_util.items())) if c_util is not None else None, c_weights, c_alpha) if mode is not None else ()),
+            may_bind=True, beam=beam, sample_n=n, temperature=tau,
             seed=s_seed, weights_dtype=wdtype, top_k=k, top_p=p,
             beam_history=beam > 1 and (any(cons.values()) or groups > 1 or lam != 0.0 or alpha != 0.0 or force_n > 0)
             or (beam > 1 and mode is not None) or stoch,      # (consensus chooses among hypotheses())
@@ -872,9 +903,13 @@ class DecodeAndGroundCaptionerGVDROI(nn.Module):
             self.last_stochastic = dict(zip(("seq", "score", "G", "logq"), (x.clone() for x in engine.hypotheses())))
             self.last_stochastic["state"] = engine.rng_state.clone()     # the generator words this decode drew with (scst_loss(wor=))
         if mode is not None:
-            seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table)
+            seq_c, att_c, logprob_c, pick, utility = engine.consensus(self.consensus_table, c_util, c_weights, c_alpha,
+                                                                      want_pairs=bool(self.consensus_pairs))
             self.last_consensus = dict(candidates=(res[0] if sampling else engine.hypotheses()[0]).clone(), pick=pick, utility=utility,
-                                       live=None if sampling else engine.consensus_live.view(engine.B, -1))
+                                       live=None if sampling else engine.consensus_live.view(engine.B, -1),
+                                       weights=engine.consensus_logw)
+            if self.consensus_pairs:
+                self.last_consensus["pairs"] = engine.consensus_pairs
             return seq_c, att_c, logprob_c
         if sampling or (engine.constrained and beam == 1):
             return res[0].clone(), res[1].clone(), res[2].clone()

@@ -1270,7 +1270,13 @@ class Trainer:
                     seq, _, logprob = model._sample(*args, sample_max=0, temperature=temperature, sample_n=n, seed=seed, top_k=top_k,
                                                     top_p=top_p, consensus=False, **(constraints or {}))
                 if consensus:
-                    utility, pick, _ = model.consensus_table.consensus(seq, n)
+                    from . import metrics as cvc_metrics
+                    mix = getattr(model, "consensus_utility", None)
+                    if cvc_metrics.is_cider_only(mix):
+                        utility, pick, _ = model.consensus_table.consensus(seq, n)
+                    else:                                   # the model's utility mix (--consensus_utility), uniform over the draws
+                        picked = cvc_metrics.consensus(seq, n, mix, model.consensus_table)
+                        utility, pick = picked["utility"], picked["pick"]
                     model.last_consensus = dict(candidates=seq, pick=pick, utility=utility)
                     picks, utils_ = pick.tolist(), utility.view(-1, n).tolist()
                 if diversity:                               # a stochastic beam's fillers (score -inf) are no captions

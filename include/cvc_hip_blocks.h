@@ -633,6 +633,34 @@ int cvc_consensus_cider(const int64_t* cand, const int32_t* live, int rows, int 
                         const float* idf, int G, float idf_unseen, float sigma, float* utility, int32_t* pick, int64_t* best,
                         cvc_stream_t stream);
 
+/* ---- consensus selection under a weighted mix of utilities: the expected utility of every candidate against the clip's other
+ * candidates, each of them ONE reference weighted by its probability, one launch (csrc/consensus_mix.hip; cvc.metrics.consensus,
+ * cvc.decode.DecodeEngine.consensus with a utility mix or weights="model").
+ *   cand, live, per_clip, keys / idf / G / idf_unseen / sigma as cvc_consensus_cider;  logw [rows] fp32 (nullable: uniform), the rows'
+ *   log-weights, any temperature already applied;  coef [6] fp32 on the HOST, >= 0, in the order cider, bleu1, bleu2, bleu3, bleu4,
+ *   rougel (cvc.metrics.REWARD_NAMES).  The table (keys, idf, G, idf_unseen, sigma) is read only with coef[0] > 0.
+ *   Pair metrics, live i != j, row i the candidate and row j its only reference:
+ *     cider(i; j): bit for bit what cvc_cider_d returns for that candidate and that single reference (words up to and including the
+ *       first 0);  bleu_k(i; j), rouge(i; j): bit for bit cvc_caption_overlap's bleu and rouge for them (words before the first 0, the
+ *       brevity penalty against row j's length).  A metric whose coefficient is 0 is not computed.
+ *   u(i, j) = sum_k coef[k] * metric_k(i; j), added in the order of coef;
+ *   w_j = expf(logw_j - max over the clip's live rows of logw): 1 at the maximum, 0 for logw_j = -inf or NaN (such a row is still a
+ *     candidate but counts for nothing as a reference);
+ *   utility [rows] fp32 = (sum_j w_j u(i, j)) / (sum_j w_j) over the live j != i, j ascending, both sums rounded term by term, fp32,
+ *     no contraction; 0 for a dead row, a row without another live row, and a zero denominator.
+ *   pick [clips] int32, best [clips, T] int64: as cvc_consensus_cider, on these utilities.
+ *   pairs [clips, per_clip, per_clip, 6] fp32 (nullable): the six pair metrics, [c, i, j, k] = metric_k(i; j); zeros on the diagonal,
+ *     for dead rows and for metrics with coefficient 0.
+ * One workgroup per clip, every caption's windows, counts, idf weights, norms and lengths built once in LDS; one walk per pair serves
+ * CIDEr-D's and BLEU's counts of all four orders and ROUGE-L's bit-vector LCS.  No atomics, no workspace: a clip's outputs are
+ * bit-reproducible and independent of the other clips.  Launch only (no host read, no allocation): capturable in a HIP graph.
+ * Null pointers (but live, logw, pairs; keys / idf with G = 0 or coef[0] = 0), rows < 1, rows % per_clip != 0, per_clip < 1 or > 32,
+ * T < 1 or > 63, a negative or non-finite coefficient, all coefficients 0, coef[0] > 0 with sigma <= 0 or G < 0 or (G > 0 and a null
+ * table): CVC_E_BADARG, before any launch, nothing written. */
+int cvc_consensus_mix(const int64_t* cand, const int32_t* live, const float* logw, int rows, int T, int per_clip,
+                      const unsigned long long* keys, const float* idf, int G, float idf_unseen, float sigma, const float* coef,
+                      float* utility, int32_t* pick, int64_t* best, float* pairs, cvc_stream_t stream);
+
 /* ---- caption-set diversity: distinct n-grams of a clip's candidate set, every candidate's BLEU statistics against the set's other
  * candidates (mBLEU), distinct captions; one launch (csrc/diversity.hip; cvc.metrics.set_diversity, DecodeEngine.set_diversity).
  *   cand [rows, T] int64, per_clip, live [rows] int32 (nullable: every row is live) as cvc_consensus_cider; a caption's words as
